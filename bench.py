@@ -2,13 +2,14 @@
 """Headline benchmark: images/s of batched YOLO11 inference at 640x640 on MI355X (+ mAP50-95 vs the CPU oracle).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--model s] [--batch 8] [--size 640] [--dtype f16]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 
 Default workload = BASELINE.json config 3, the one the 1/2/4/8-GPU metric is quoted on: yolo11s detect, 640x640,
 batch 8 per GPU, on the x3 plan — fp16 MFMAs on split operands with fp32-equivalent storage, the plan whose detections
 meet the north-star bar (1e-3 px absolute on coordinates, 1e-3 on scores, class exact; the plain f16 plan is ~0.6 px
-and 3e-3 off), reported with its parity against the CPU oracle on the timed batch (`parity`) and beside the f16
-throughput plan measured in the same run (`f16_throughput_plan`).  (`--model n` gives config 2, `--dtype i8`
+and 3e-3 off), reported under `--full` with its parity against the CPU oracle on the timed batch (`parity`)
+and beside the f16 throughput plan measured in the same run (`f16_throughput_plan`).  (`--model n` gives config 2, `--dtype i8`
 config 4, `--model s --task segment --batch 4` config 5.)
 
 One step = one `YOLO11Model.predict(batch)` call (the reference's timed unit: core/model.py:277-282,
@@ -23,10 +24,18 @@ the forward's own input_stats kernel takes the batch max; at N > 1 each rank's s
 all-reduced (MAX) over the ranks every step and handed to the forward (yolomi.dist.enable_global_rule), so the
 decision is the global batch's.
 
-Rank 0 prints ONE JSON line.  Extra fields: `roofline` (conv implicit-GEMM kernels, live HIP-event timing),
-`kernels` (per-kind device time and achieved HBM GB/s of the non-conv kernels), `cpu_baseline` (the oracle on host
-cores, N=1 only, B=1 and B=8 samples), `accuracy` (mAP50-95 of GPU detections against oracle detections as pseudo
-ground truth, N=1 only), `device_images_per_s` (back-to-back graph replays, no host sync).
+Rank 0 prints ONE JSON line.  A plain run does what the headline figure needs and no more: set-up, warm-up, the timed
+steps, the result line.  `--full` adds the rest, each in runs of its own after the timed loop: `device_images_per_s`
+(back-to-back graph replays, no host sync), `roofline` (conv implicit-GEMM kernels, live HIP-event timing), `kernels`
+(per-kind device time and achieved HBM GB/s of the non-conv kernels), `f16_throughput_plan` (x3 runs), `cpu_baseline`
+(the oracle on host cores, N=1 only, B=1 and B=8 samples), `accuracy` (mAP50-95 of GPU detections against oracle
+detections as pseudo ground truth, N=1 only) and `parity`; `--no-roofline`, `--no-f16` and `--no-cpu` drop parts of it.
+
+`--dump-outputs DIR` writes what the last timed predict() returned, per image g of the global batch (rank * batch + b):
+`DIR/boxes_<g>.npy`, float32 (n, 6) rows [x1, y1, x2, y2, conf, cls], and for Segment `DIR/masks_<g>.npy`, float32
+(n, k): the masks at k pixel positions drawn by a generator seeded with g (every pixel while the dump stays within its
+size budget, DUMP_BUDGET_BYTES for the whole batch).  The inputs are functions of the arguments alone, so two builds
+run with the same arguments can be compared file for file.
 """
 from __future__ import annotations
 
@@ -362,6 +371,28 @@ def parity(gpu_dets, gts, conf=0.25, iou=0.7, tol_xy=1e-3, tol_s=1e-3, exact=Non
     return out
 
 
+DUMP_BUDGET_BYTES = 48 << 20  # --dump-outputs: the whole dump (all ranks) stays under this
+
+
+def dump_outputs(res, out_dir, first_image, n_images):
+    """--dump-outputs: the Results of one predict() call as float32 .npy files (layout: the module docstring).
+    `first_image`: the global index of res[0]; `n_images`: the global batch, which shares DUMP_BUDGET_BYTES."""
+    os.makedirs(out_dir, exist_ok=True)
+    per_image = DUMP_BUDGET_BYTES // n_images
+    for b, r in enumerate(res):
+        g = first_image + b
+        boxes = r.boxes.data.cpu().numpy().astype(np.float32)
+        np.save(os.path.join(out_dir, f"boxes_{g:03d}.npy"), boxes)
+        if r.masks is None:
+            continue
+        m = r.masks.data.cpu().numpy()
+        m = m.reshape(m.shape[0], int(np.prod(m.shape[1:])))  # (n, H*W), n = 0 included
+        k = min(m.shape[1], (per_image - boxes.nbytes) // (4 * max(m.shape[0], 1)))
+        if k < m.shape[1]:  # a prefix of one seeded permutation of the pixels: the same positions in every build
+            m = m[:, np.sort(np.random.default_rng(g).permutation(m.shape[1])[:k])]
+        np.save(os.path.join(out_dir, f"masks_{g:03d}.npy"), m.astype(np.float32))
+
+
 def _free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -439,12 +470,18 @@ def main():
     ap.add_argument("--size", type=int, default=640)
     ap.add_argument("--dtype", default="x3", choices=["f16", "f32", "i8", "f8", "x3"],
                     help="plan: x3 (default: split-f16 MFMA, meets the 1e-3 bar), f16, f32, i8, f8")
-    ap.add_argument("--no-f16", action="store_true", help="x3 runs: skip the f16 throughput-plan comparison")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline figure does not need: device-loop "
+                         "throughput, conv roofline and kernel table, the f16 throughput plan (x3 runs), the CPU "
+                         "baseline with accuracy and parity against the oracle")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the detections (and masks) of the last timed step as DIR/<name>.npy, float32")
+    ap.add_argument("--no-f16", action="store_true", help="--full x3 runs: skip the f16 throughput-plan comparison")
     ap.add_argument("--backend", default="qnnpack", choices=["qnnpack", "fbgemm"], help="i8: PTQ qconfig")
     ap.add_argument("--calib-batches", type=int, default=4, help="i8: calibration batches (B images each)")
     ap.add_argument("--cpu-seconds", type=float, default=16.0)
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline, accuracy and parity")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: skip the roofline and the kernel table")
     ap.add_argument("--plumbing", action="store_true", help="CPU/gloo rehearsal of the multi-rank protocol (no GPU)")
     ap.add_argument("--cabi-bcast", action="store_true",
                     help="N > 1: broadcast the weights through the C-ABI's ym_broadcast_weights instead of torch's "
@@ -518,17 +555,8 @@ def main():
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
     elapsed = float(el.item())
     value = world * B * a.steps / elapsed
-
-    # device-side throughput: back-to-back graph replays without the per-batch host sync of predict()
-    eng = model.model.engine
-    for _ in range(5):
-        eng.run(x)
-    torch.cuda.synchronize()
-    td = time.perf_counter()
-    for _ in range(a.steps):
-        eng.run(x)
-    torch.cuda.synchronize()
-    dev_ips = B * a.steps / (time.perf_counter() - td)
+    if a.dump_outputs:
+        dump_outputs(res, a.dump_outputs, rank * B, world * B)
 
     out = {
         "metric": METRIC, "value": round(value, 2), "unit": "images/s", "n_gpus": world, "steps": a.steps,
@@ -541,17 +569,27 @@ def main():
                    "batch_per_gpu": B, "global_batch": B * world, "image_size": a.size,
                    "parallelism": f"dp{world} (batch-sharded, RCCL weight broadcast)",
                    "batch_rule": BATCH_RULE[world > 1]},
-        "device_images_per_s": round(dev_ips * world, 2),
         "init_s": round(init_s, 3),
     }
     Bl = model.model.engine.lane_batch(B)
     out["config"]["lanes"] = -(-B // Bl)
     out["config"]["conv_tiles"] = model.model.engine.tune_source.get((Bl, a.size, a.size), "heuristic")
-    if rank == 0 and not a.no_roofline:
+    if a.full:
+        # device-side throughput: back-to-back graph replays without the per-batch host sync of predict()
+        eng = model.model.engine
+        for _ in range(5):
+            eng.run(x)
+        torch.cuda.synchronize()
+        td = time.perf_counter()
+        for _ in range(a.steps):
+            eng.run(x)
+        torch.cuda.synchronize()
+        out["device_images_per_s"] = round(B * a.steps / (time.perf_counter() - td) * world, 2)
+    if a.full and rank == 0 and not a.no_roofline:
         out["roofline"] = conv_roofline(model, x, a.dtype, out["config"]["workload"])
         out["kernels"] = kernel_table(model, x, a.dtype, out["config"]["workload"])
     f16_dets = None
-    if rank == 0 and world == 1 and a.dtype == "x3" and not a.no_f16:
+    if a.full and rank == 0 and world == 1 and a.dtype == "x3" and not a.no_f16:
         # the f16 throughput plan on the same batch and loop, for the cost of the tolerance
         m16 = YOLO11Model(task=a.task, size=a.model, device=f"cuda:{local}", dtype="f16",
                           weights_blob=pack_model(a.model, a.task, synth_weights(a.model, a.task, 0), "f16"))
@@ -576,7 +614,7 @@ def main():
             "x3_to_f16_ratio": round(value / (B * a.steps / el16), 4),
             "note": "fp16 storage + fp32 accumulation; misses the 1e-3 bar (see parity)"}
         del m16, e16
-    if rank == 0 and world == 1 and not a.no_cpu:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu:
         gdets = [r.boxes.data.cpu().numpy() for r in res]
         base, acc, gts, exact = cpu_baseline(a.model, a.task, gdets, x, a.cpu_seconds, qp)
         out["cpu_baseline"] = base

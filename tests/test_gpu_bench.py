@@ -66,6 +66,36 @@ def test_validator_benchmark_speed_large_batches(tmp_path):
     assert all(c["images_per_second"] > 0 for c in r["configurations"])
 
 
+def test_bench_plain_run_line_and_dump(tmp_path, monkeypatch):
+    """A plain `bench.py` run prints the headline line without the `--full` measurements, times `--steps` steps, and
+    `--dump-outputs` writes one float32 (n, 6) boxes file per image: the detections predict() returns for that batch
+    (bit for bit: no table is committed for this shape, so both processes pin the heuristic conv tiles)."""
+    monkeypatch.setenv("YM_AUTOTUNE", "0")
+    import os
+    import subprocess
+    import sys
+    import numpy as np
+    import bench
+    from core.model import YOLO11Model
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--model", "n", "--batch", "2", "--size", "320", "--dump-outputs", str(tmp_path / "d")],
+                       capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0, p.stderr[-2000:]
+    out = json.loads(p.stdout.strip().splitlines()[-1])
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["dtype"] == "f16x3" and out["higher_is_better"] is True
+    assert out["unit"] == "images/s" and out["value"] == pytest.approx(2 / (out["ms_per_step"] * 1e-3), rel=1e-3)
+    for k in ("device_images_per_s", "roofline", "kernels", "f16_throughput_plan", "cpu_baseline", "accuracy", "parity"):
+        assert k not in out
+    assert sorted(os.listdir(tmp_path / "d")) == ["boxes_000.npy", "boxes_001.npy"]
+    m = YOLO11Model(task="detect", size="n", device="cuda:0", dtype="x3")
+    res = m.predict(bench.synthetic_batch(2, 320, 1000, torch.device("cuda:0")))
+    for b, r in enumerate(res):
+        got = np.load(tmp_path / "d" / f"boxes_{b:03d}.npy")
+        assert got.dtype == np.float32 and got.shape[1] == 6 and len(got) > 0
+        assert np.array_equal(got, r.boxes.data.cpu().numpy())
+
+
 def test_throughput_benchmark_resource_monitor(tmp_path):
     """benchmark_throughput's sustained loop with the resource monitor (reference speed_benchmark.py:243-244): AMD
     SMI samples of the GPUs land in resource_usage and resource_history.json."""

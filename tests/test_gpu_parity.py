@@ -758,7 +758,7 @@ def test_halo_conv_configs_yolo11s_b8(cfg):
         eng._tuned.discard((8, 640, 640))
 
 
-def test_decode_staged_variant_bitwise_equals_register_variant():
+def test_decode_staged_variant_bitwise_equals_register_variant(tmp_path):
     """the LDS-staged decode_anchors<false> (any nc / reg_max; forced with YM_DECODE_STAGED=1 in a child
     process, the switch is read once per process) and the register-direct decode_anchors<true> that every
     nc=80 / reg_max=16 plan takes produce the same detections bit for bit."""
@@ -774,8 +774,7 @@ def test_decode_staged_variant_bitwise_equals_register_variant():
             % (os.path.join(root, "yolo-infer_amd"), root))
     outs = []
     for staged in ("0", "1"):
-        path = os.path.join(root, "gpurun_out", f"decode_{staged}.npy") if os.path.isdir(
-            os.path.join(root, "gpurun_out")) else f"/tmp/decode_{staged}.npy"
+        path = str(tmp_path / f"decode_{staged}.npy")
         env = dict(os.environ, YM_DECODE_STAGED=staged)
         subprocess.run([sys.executable, "-c", code, path], check=True, env=env, timeout=240)
         outs.append(np.load(path))
@@ -784,7 +783,7 @@ def test_decode_staged_variant_bitwise_equals_register_variant():
 
 
 # ------------------------------------------------------------------------------------------------ 1280² (N = 1600)
-def test_f16_1280_attention_and_layers():
+def test_f16_1280_attention_and_layers(tmp_path):
     """benchmark_speed's 1280² size (core/validator.py:188): C2PSA attention over N = 1600 tokens runs the block-wise
     MFMA attention (csrc/ym_misc.hip attn_psa_flash, online softmax) — equal to the scalar kernel within fp16
     rounding, and every checked layer within the f16 plan's 1e-2 of the oracle."""
@@ -806,8 +805,7 @@ def test_f16_1280_attention_and_layers():
                 l10 = got
     # the same layer with the scalar attention kernel (YM_ATTN_FLASH_OFF is read once per process: a child run)
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = os.path.join(root, "gpurun_out") if os.path.isdir(os.path.join(root, "gpurun_out")) else "/tmp"
-    path = os.path.join(out, "l10_scalar.npy")
+    path = str(tmp_path / "l10_scalar.npy")
     code = ("import sys, numpy as np; sys.path[:0] = [%r, %r];"
             "from tests.golden.make_golden import make_input; from core.model import YOLO11Model;"
             "m = YOLO11Model(size='n', device='cuda:0', dtype='f16'); e = m.model.engine;"

@@ -417,3 +417,30 @@ def test_x3_weight_exp_is_clamped_to_the_loader_range():
     w = np.full((8, 8), 0.03, np.float32)
     assert 2 ** 13 < 0.03 * 2.0 ** x3_weight_exp(w) <= 2 ** 14
     assert x3_weight_exp(np.zeros((8, 8), np.float32)) == 0
+
+
+def test_bench_dump_outputs_layout_and_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 boxes_<g>.npy / masks_<g>.npy per image of the global batch; masks past the
+    size budget keep the same seeded pixel positions from run to run, and the whole dump stays under the budget."""
+    import bench
+    from core.results import Results
+    rng = np.random.default_rng(0)
+    x = torch.zeros(2, 3, 16, 16)
+    boxes = [torch.from_numpy(rng.random((n, 6)).astype(np.float32)) for n in (3, 0)]
+    masks = [torch.from_numpy(rng.random((n, 16, 16)) > 0.5) for n in (3, 0)]
+    res = [Results(x[b], {0: "a"}, boxes[b], masks[b]) for b in range(2)]
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4 * 4 * (3 * 6 + 3 * 100))  # 4 images: 100 of 256 pixels each
+    for d in ("a", "b"):
+        bench.dump_outputs(res, str(tmp_path / d), first_image=4, n_images=4)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["boxes_004.npy", "boxes_005.npy", "masks_004.npy", "masks_005.npy"]
+    got = {n: np.load(tmp_path / "a" / n) for n in names}
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert np.array_equal(got["boxes_004.npy"], boxes[0].numpy()) and got["boxes_005.npy"].shape == (0, 6)
+    assert got["masks_004.npy"].shape == (3, 100) and got["masks_005.npy"].shape[0] == 0
+    idx = np.sort(np.random.default_rng(4).permutation(256)[:100])
+    assert np.array_equal(got["masks_004.npy"], masks[0].numpy().reshape(3, -1)[:, idx].astype(np.float32))
+    assert all(np.array_equal(v, np.load(tmp_path / "b" / n)) for n, v in got.items())
+    assert sum(v.nbytes for v in got.values()) <= bench.DUMP_BUDGET_BYTES
+    bench.dump_outputs([Results(x[0], {0: "a"}, boxes[0])], str(tmp_path / "c"), 0, 1)  # Detect: boxes only
+    assert os.listdir(tmp_path / "c") == ["boxes_000.npy"]

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Markdown table of bench.py lines: python tools/bench_table.py profiles/r03e_bench_*.json"""
+"""Markdown table of `bench.py --full` lines: python tools/bench_table.py profiles/r03e_bench_*.json"""
 import json
 import sys
 

@@ -6,7 +6,7 @@ OUT=gpurun_out/${TAG:-ab}
 mkdir -p "$OUT"
 for arm in A B A B; do
   n=$((n + 1))
-  env ${!arm} timeout -k 10 300 python -u bench.py --no-roofline --steps ${STEPS:-300} $ARGS > "$OUT/ab_${arm}_$n.log" 2>&1
+  env ${!arm} timeout -k 10 300 python -u bench.py --full --no-roofline --steps ${STEPS:-300} $ARGS > "$OUT/ab_${arm}_$n.log" 2>&1
   rc=$?
   echo "[$arm ${!arm}] rc=$rc" >> "$OUT/steps.log"
   if [ $rc -ne 0 ]; then exit $rc; fi

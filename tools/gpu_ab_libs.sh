@@ -20,5 +20,5 @@ for v in A B C A B C; do
 done
 for v in A B C; do
   lib=tools/ab/lib$v.so; [ $v = B ] && lib=yolo-infer_amd/yolomi/libyolomi.so
-  YM_LIB=$lib run "bench_$v" 300 python -u bench.py --steps 50 --warmup 10 --no-cpu --no-f16
+  YM_LIB=$lib run "bench_$v" 300 python -u bench.py --full --steps 50 --warmup 10 --no-cpu --no-f16
 done

@@ -6,7 +6,7 @@ mkdir -p "$OUT"
 for v in old new old new; do
   n=$((n + 1))
   cp abso/$v.so yolo-infer_amd/yolomi/libyolomi.so
-  timeout -k 10 300 python -u bench.py --no-roofline --steps ${STEPS:-300} $ARGS > "$OUT/ab_${v}_$n.log" 2>&1
+  timeout -k 10 300 python -u bench.py --full --no-roofline --steps ${STEPS:-300} $ARGS > "$OUT/ab_${v}_$n.log" 2>&1
   rc=$?
   echo "[$v] rc=$rc" >> "$OUT/steps.log"
   if [ $rc -ne 0 ]; then break; fi

@@ -4,7 +4,7 @@ cd "$(dirname "$0")/.." || exit 1
 mkdir -p gpurun_out/br
 for r in 1 2; do
   for b in 4 1 2 3; do
-    YM_BRANCHES=$b timeout -k 10 300 python -u bench.py --steps 100 --warmup 10 --no-cpu --no-f16 --no-roofline \
+    YM_BRANCHES=$b timeout -k 10 300 python -u bench.py --full --steps 100 --warmup 10 --no-cpu --no-f16 --no-roofline \
       > gpurun_out/br/b${b}_$r.json 2> gpurun_out/br/b${b}_$r.err || exit 1
   done
 done

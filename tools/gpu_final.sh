@@ -20,18 +20,18 @@ for step in ${STEPS:-smoke suite bench_s bench_n bench_seg bench_ptq optable pro
   case $step in
     smoke) run smoke 300 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" ;;
     suite) run suite 1100 python -u -X faulthandler -m pytest tests -m gpu -q -p no:cacheprovider --timeout 300 --timeout-method thread ;;
-    bench_s) run bench_s 400 python -u bench.py ;;
-    bench_n) run bench_n 400 python -u bench.py --model n --no-f16 ;;
-    bench_seg) run bench_seg 400 python -u bench.py --task segment --batch 4 --no-f16 ;;
-    bench_ptq) run bench_n_i8 400 python -u bench.py --model n --dtype i8
-               run bench_n_f8 400 python -u bench.py --model n --dtype f8
-               run bench_n_f16 400 python -u bench.py --model n --dtype f16 --no-cpu ;;
+    bench_s) run bench_s 400 python -u bench.py --full ;;
+    bench_n) run bench_n 400 python -u bench.py --full --model n --no-f16 ;;
+    bench_seg) run bench_seg 400 python -u bench.py --full --task segment --batch 4 --no-f16 ;;
+    bench_ptq) run bench_n_i8 400 python -u bench.py --full --model n --dtype i8
+               run bench_n_f8 400 python -u bench.py --full --model n --dtype f8
+               run bench_n_f16 400 python -u bench.py --full --model n --dtype f16 --no-cpu ;;
     optable) run optable 200 python -u tools/op_table.py --model s --dtype x3 ;;
     files) run files 900 python -u -X faulthandler -m pytest $TEST_FILES -q -p no:cacheprovider --timeout 300 --timeout-method thread ;;
     ktests) run ktests 400 python -u -X faulthandler -m pytest tests/test_gpu_kernels.py -q -p no:cacheprovider --timeout 200 --timeout-method thread ${KTESTS_K:+-k "$KTESTS_K"} ;;
     ab) for v in 0 1 0 1; do  # same-box A/B of an environment switch AB_VAR (e.g. YM_CHAIN, YM_STEMFUSE)
           export "$AB_VAR=$v"
-          run "ab_${AB_VAR}_$v" 300 python -u bench.py --no-cpu --no-f16 --no-roofline --steps 400
+          run "ab_${AB_VAR}_$v" 300 python -u bench.py --full --no-cpu --no-f16 --no-roofline --steps 400
           mv "$OUT/ab_${AB_VAR}_$v.log" "$OUT/ab_${AB_VAR}_${v}_$((++n))"; done
         export "$AB_VAR=1"
         (cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv \
@@ -51,6 +51,7 @@ for step in ${STEPS:-smoke suite bench_s bench_n bench_seg bench_ptq optable pro
           if [ $rc -ne 0 ]; then exit $rc; fi ;;
     prof) (cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv \
              -d "$GRAFT_REPO_ROOT/$OUT/prof" -o run -- python3 "$GRAFT_REPO_ROOT/bench.py" --steps 50 \
+             --full \
              --warmup 10 --no-cpu --no-f16 > "$GRAFT_REPO_ROOT/$OUT/prof_bench.log" 2>&1); rc=$?
           echo "[prof] rc=$rc $(date +%T)" | tee -a "$OUT/steps.log"
           if [ $rc -ne 0 ]; then exit $rc; fi

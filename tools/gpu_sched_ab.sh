@@ -7,7 +7,7 @@ YM_SCHED=crit timeout -k 10 300 python -u -m pytest tests/test_gpu_parity.py -q 
   -k "branch_schedule or graph_replay" > gpurun_out/sched/tests.log 2>&1 || exit 1
 for r in 1 2; do
   for m in def crit; do
-    YM_SCHED=$m timeout -k 10 300 python -u bench.py --steps 100 --warmup 10 --no-cpu --no-f16 --no-roofline \
+    YM_SCHED=$m timeout -k 10 300 python -u bench.py --full --steps 100 --warmup 10 --no-cpu --no-f16 --no-roofline \
       > gpurun_out/sched/${m}_$r.json 2>/dev/null || exit 1
   done
 done

@@ -15,4 +15,4 @@ rm -rf gpurun_out/tuned
 YM_RETABLE_OPS=model.1+cv1,model.3+cv1,model.5+cv1,model.23.cv2.0.1+2,model.23.cv2.1.1+2,model.23.cv2.2.1+2,model.23.proto.cv2+cv3,model.23.cv4.0.1+2,model.23.cv4.1.1+2,model.23.cv4.2.1+2 run retable 400 python -u tools/retable.py
 cp gpurun_out/tuned/*.json yolo-infer_amd/yolomi/tuned/ 2>/dev/null
 run optable 200 python -u tools/op_table.py --model s --dtype x3
-run bench 400 python -u bench.py --steps 100 --warmup 10 --no-cpu
+run bench 400 python -u bench.py --full --steps 100 --warmup 10 --no-cpu

@@ -7,7 +7,7 @@ Forwards are split at the input_stats kernel (the first op of every forward).  P
 last end), the union of kernel-busy intervals (span - union = time no kernel of the forward runs: launch / dependency
 gaps), the sum of kernel durations (sum / union > 1: concurrent branches), and the largest idle gaps with the kernels
 on either side.  Averaged over the last `forwards` forwards (default 20) before the last `skip` ones (default 0; a
-bench.py --steps 50 --warmup 10 run ends with 55 device-loop replays, so skip 55 selects its predict() loop).
+bench.py --full --steps 50 --warmup 10 run ends with 55 device-loop replays, so skip 55 selects its predict() loop).
 """
 import csv
 import glob

@@ -38,13 +38,14 @@ typedef struct {
   int max_h;
   int max_w;
   int scale;  /* 0 = any, else 'n', 's', 'm', 'l' or 'x' */
-  int task;   /* 0 = any, YM_TASK_DETECT, YM_TASK_SEGMENT */
+  int task;   /* 0 = any, YM_TASK_DETECT, YM_TASK_SEGMENT, YM_TASK_POSE */
   int dtype;  /* 0 = any, YM_DTYPE_F16, YM_DTYPE_F32, YM_DTYPE_I8, YM_DTYPE_F8, YM_DTYPE_X3 */
   int reserved[2];
 } ym_model_desc;
 
 #define YM_TASK_DETECT 1
 #define YM_TASK_SEGMENT 2
+#define YM_TASK_POSE 3 /* Detect + keypoint branch; ym_infer rows carry the decoded keypoints (see ym_infer) */
 #define YM_DTYPE_F16 1 /* fp16 storage, fp32 MFMA accumulation (throughput plan) */
 #define YM_DTYPE_F32 2 /* exact-f32 MFMA (parity plan) */
 #define YM_DTYPE_I8 3  /* PTQ int8 (torch.ao qconfig of optimization/quantization/quantizers.py:124-131) */
@@ -115,7 +116,12 @@ int ym_rccl_comm_destroy(void* comm);
  * d_dets: B×max_det×(6+nm) fp32 [x1,y1,x2,y2,conf,cls,(mask coeffs)], rows ordered by NMS keep order;
  * d_counts: B int32 kept counts.  d_dets / d_counts must be device pointers.  The forward of a (shape, input,
  * counts, args) key is captured once as a HIP graph; a later call with other d_dets rows replays it with its NMS
- * nodes re-pointed (no recapture, no copy), so a caller may hand in fresh output rows every call. */
+ * nodes re-pointed (no recapture, no copy), so a caller may hand in fresh output rows every call.
+ * nm, the extras per row: 0 (detect), 32 mask coefficients (segment), or, for pose plans, K*ndim rounded up to a
+ * multiple of 4 (COCO: 17*3 = 51 -> 52): [x1,y1,x2,y2,conf,cls, kpt_0 .. kpt_{K-1}, 0 pad] with kpt_k = (x, y[, v]) in
+ * input pixels (Ultralytics Pose.kpts_decode: x = (raw*2 + grid_x)*stride, v = sigmoid(raw)); not clipped to the
+ * image and not masked by visibility — scale_coords and the Keypoints view do that on the host side.
+ * K and ndim: ym_kpt_shape. */
 int ym_infer(ym_ctx* ctx, const float* d_input, int B, int H, int W, const ym_infer_args* args, float* d_dets,
              int* d_counts, void* stream);
 
@@ -163,6 +169,19 @@ int ym_buffer_info(ym_ctx* ctx, int buf, void** ptr, int* C, int* H, int* W, int
 /* Copy the first `bytes` of plan buffer `buf` (as left by the last ym_infer/ym_profile) to `dst` (host or device
  * pointer); synchronous. */
 int ym_read_buffer(ym_ctx* ctx, int buf, void* dst, size_t bytes);
+
+/* Pose plans: keypoints per detection (K) and values per keypoint (ndim: 2 = x, y; 3 = x, y, visibility) of the loaded
+ * model; both 0 for detect / segment plans. */
+int ym_kpt_shape(ym_ctx* ctx, int* K, int* ndim);
+
+/* Introspection for tests: copy the first `bytes` of a scratch region of the last forward to `dst`; synchronous.
+ * YM_SCRATCH_KEYS: the candidate keys, per image `kstride` (the power of two >= A) uint64 words, score bits << 32 |
+ * ~anchor, in no fixed order; YM_SCRATCH_COUNTS: the B candidate counts (int32); YM_SCRATCH_KPTS (pose plans): the
+ * decoded keypoint rows (B, A, nm) fp32, written for the candidates' anchors only. */
+#define YM_SCRATCH_KEYS 0
+#define YM_SCRATCH_COUNTS 1
+#define YM_SCRATCH_KPTS 2
+int ym_read_scratch(ym_ctx* ctx, int which, void* dst, size_t bytes);
 
 /* Segment plans: instance masks of the detections of the last ym_infer (same B, H, W, stream order), i.e. Ultralytics
  * `ops.process_mask(proto, coef, boxes, (H, W), upsample=True)` per image.  d_dets: the ym_infer output rows;

@@ -4,7 +4,7 @@ Same constructor, `predict`, `benchmark`, `get_model_info`, `.model` surface as 
 (`core/model.py:29-295`), but `predict` runs the hand-written gfx950 path (`yolomi.engine.Engine` → libyolomi.so →
 one HIP-graph replay per batch) instead of delegating to `ultralytics.YOLO.predict` (`core/model.py:133`).
 
-Scope: tasks detect/segment, sizes n/s/m/l/x, `torch.Tensor` sources (BCHW or CHW, H,W % 32 == 0,
+Scope: tasks detect/segment/pose, sizes n/s/m/l/x, `torch.Tensor` sources (BCHW or CHW, H,W % 32 == 0,
 LoadTensor's /255 rule).  There is no CPU fallback: a CPU device or a missing libyolomi.so raises.
 """
 from __future__ import annotations
@@ -99,12 +99,13 @@ class YOLO11Model:
         "obb": "yolo11n-obb.pt",
     }
     SUPPORTED_SIZES = ["n", "s", "m", "l", "x"]
-    HIP_TASKS = ("detect", "segment")
+    HIP_TASKS = ("detect", "segment", "pose")
 
     def __init__(self, model_path: Optional[Union[str, Path]] = None, task: str = "detect", size: str = "n",
                  device: Optional[str] = None, verbose: bool = True, dtype: str = "x3", seed: int = 0,
                  weights_blob: Optional[bytes] = None, qparams: Optional[Dict] = None,
-                 state_dict: Optional[Dict[str, np.ndarray]] = None, weights_from: Optional[tuple] = None):
+                 state_dict: Optional[Dict[str, np.ndarray]] = None, weights_from: Optional[tuple] = None,
+                 kpt_shape: Optional[tuple] = None):
         """Extra keyword arguments over the reference: `dtype` — 'x3' (the default: fp32 activations, every conv GEMM
         as three fp16 MFMAs on hi/lo split operands; meets the reference fp32 path's 1e-3 px / score bar, DESIGN.md
         §3), 'f16' (opt-in throughput mode: fp16 storage + fp32 accumulate, ~0.6 px / 3e-3 off the fp32 path),
@@ -112,7 +113,9 @@ class YOLO11Model:
         optimization.quantization.PostTrainingQuantizer), `seed` of the synthetic weights used when no `model_path`
         is given, `weights_blob` = an already packed model (e.g. received over an RCCL broadcast from rank 0), and
         `state_dict` = weights already in memory, `weights_from` = (rccl comm, root): receive the root rank's model
-        over RCCL, or a yolomi Runtime that already received it (yolomi.dist.rccl_broadcast_model)."""
+        over RCCL, or a yolomi Runtime that already received it (yolomi.dist.rccl_broadcast_model), `kpt_shape` =
+        (K, 2 | 3) of a pose model (default: (17, 3) for synthetic weights; for a checkpoint (nk // 3, 3) when its nk
+        keypoint channels divide by 3, else (nk // 2, 2))."""
         self.task = task
         self.size = size
         self.device = device or self._get_default_device()
@@ -124,6 +127,7 @@ class YOLO11Model:
         self._qparams = qparams
         self._sd = state_dict
         self._weights_from = weights_from
+        self._kpt_shape = tuple(kpt_shape) if kpt_shape is not None else None
         self.optimization_history: List[Dict[str, Any]] = []
         # batch-sharded multi-GPU (yolomi.dist.enable_global_rule): callable x -> (1,) device max of the GLOBAL batch
         self.global_batch_max = None
@@ -160,17 +164,21 @@ class YOLO11Model:
                 sd = _load_state_dict(Path(self.model_path))
             else:  # the reference fetches yolo11{size}.pt by name; offline we synthesise weights of that graph
                 sd = synth_weights(self.size, self.task, self.seed)
-            nc = 80
+            nc = 1 if self.task == "pose" else 80
+            kpt_shape = self._kpt_shape
             if sd and self._blob is None:  # the checkpoint decides the architecture, as YOLO(model_path) does
-                from yolomi.arch import infer_arch
-                scale, task, nc = infer_arch(sd)
+                from yolomi.arch import infer_arch, infer_kpt_shape
+                scale, task, nc = infer_arch(sd, kpt_shape)
+                kpt_shape = infer_kpt_shape(sd, kpt_shape) if task == "pose" else None
                 if (scale, task) != (self.size, self.task):
                     logger.warning(f"{self.model_path or 'state_dict'} holds a yolo11{scale} {task} model "
                                    f"(nc={nc}); using it instead of size={self.size!r} task={self.task!r}")
                     self.size, self.task = scale, task
             engine = Engine(self.size, self.task, sd, dev, self.dtype, blob=self._blob, qparams=self._qparams, nc=nc,
-                            receive=self._weights_from)
+                            receive=self._weights_from, kpt_shape=kpt_shape if self.task == "pose" else None)
             names = COCO_NAMES if nc == 80 else {i: f"class{i}" for i in range(nc)}
+            if self.task == "pose" and nc == 1:
+                names = {0: "person"}
         except Exception as e:
             logger.error(f"Failed to load model: {e}")
             raise
@@ -231,7 +239,8 @@ class YOLO11Model:
                 lazy[0]
             speed = {"preprocess": (t1 - t0) * 1e3, "inference": (time.perf_counter() - t1) * 1e3,
                      "postprocess": 0.0}  # host time of the calls (the forward itself runs asynchronously)
-            return [Results.from_batch(im, b, names, out, lazy, path=f"image{b}.jpg", speed=speed) for b in range(B)]
+            return [Results.from_batch(im, b, names, out, lazy, path=f"image{b}.jpg", speed=speed,
+                                       kpt_shape=eng.kpt_shape) for b in range(B)]
         # the NMS kernel writes this call's rows straight into a fresh tensor (the Results keep views into it)
         out = torch.empty((B, max_det, 6 + eng.nm), dtype=torch.float32, device=im.device)
         dets, counts = eng.run(im, conf=conf, iou=iou, max_det=max_det, classes=classes, agnostic=agnostic,
@@ -274,18 +283,23 @@ class YOLO11Model:
             self._mask_cap = max(16, min(max_det, -(-(5 * max(max(n), 1)) // 64) * 16))  # ceil(1.25 max / 16) * 16
         else:
             n = counts[:B].tolist()  # the device→host sync of a predict call
-        if imsrc is not None:  # ops.scale_boxes back to each original image
-            from yolomi.preprocess import scale_boxes
+        if imsrc is not None:  # ops.scale_boxes (pose: and ops.scale_coords) back to each original image
+            from yolomi.preprocess import scale_boxes, scale_coords
             for b in range(B):
                 if n[b]:
                     scale_boxes(im.shape[2:], out[b, : n[b], :4], imsrc[2][b])
+                    if self.task == "pose":
+                        K, nd = eng.kpt_shape
+                        scale_coords(im.shape[2:], out[b, : n[b], 6:6 + eng.nk].view(n[b], K, nd), imsrc[2][b])
         t2 = time.perf_counter()
         speed = {"preprocess": (t1 - t0) * 1e3, "inference": (t2 - t1) * 1e3, "postprocess": 0.0}
         if masks is None:
             if imsrc is None:
                 return [Results.from_batch(im, b, names, out, n[b], path=f"image{b}.jpg", speed=speed)
                         for b in range(B)]
-            return [Results.from_image(imsrc[0][b], imsrc[1][b], names, out[b, : n[b], :6], speed=speed)
+            return [Results.from_image(imsrc[0][b], imsrc[1][b], names, out[b, : n[b], :6], speed=speed,
+                                       keypoints=(out[b, : n[b], 6:6 + eng.nk].reshape(n[b], *eng.kpt_shape)
+                                                  if self.task == "pose" else None))
                     for b in range(B)]
         res = []  # Segment: the predictor keeps only non-empty masks
         mb = masks.view(torch.bool).reshape(-1, H, W)  # the kernel writes 0/1 bytes: a bool view, no copy

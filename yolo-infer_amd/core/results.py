@@ -116,6 +116,40 @@ class Masks(_TensorView):
         return (self.orig_shape,)
 
 
+class Keypoints(_TensorView):
+    """(n, K, 2 | 3) keypoints of one image (upstream `ultralytics.engine.results.Keypoints`): x, y in the original
+    image's pixels and, with 3 values, the visibility; x and y of a keypoint whose visibility is below 0.5 are zeroed
+    (in place, as upstream does: hand in a tensor you own)."""
+
+    def __init__(self, keypoints, orig_shape):
+        if keypoints.ndim == 2:
+            keypoints = keypoints[None, :]
+        if keypoints.shape[-1] == 3:
+            mask = keypoints[..., 2] < 0.5
+            keypoints[..., :2][mask] = 0
+        super().__init__(keypoints)
+        self.orig_shape = orig_shape
+        self.has_visible = self.data.shape[-1] == 3
+
+    def _extra(self):
+        return (self.orig_shape,)
+
+    @property
+    def xy(self):
+        return self.data[..., :2]
+
+    @property
+    def xyn(self):
+        xy = self.xy.clone() if isinstance(self.xy, torch.Tensor) else np.copy(self.xy)
+        xy[..., 0] /= self.orig_shape[1]
+        xy[..., 1] /= self.orig_shape[0]
+        return xy
+
+    @property
+    def conf(self):
+        return self.data[..., 2] if self.has_visible else None
+
+
 class LazyCounts:
     """The B detection counts of one asynchronous predict() call, still on the device (the words the NMS kernel
     writes behind the call's rows): read to the host once, on the first access by any of the call's Results."""
@@ -138,7 +172,9 @@ class LazyCounts:
 
 class Results:
     def __init__(self, orig_tensor: Optional[torch.Tensor], names: Dict[int, str], boxes: torch.Tensor,
-                 masks: Optional[torch.Tensor] = None, path: str = "image0.jpg", speed=None):
+                 masks: Optional[torch.Tensor] = None, path: str = "image0.jpg", speed=None,
+                 keypoints: Optional[torch.Tensor] = None):
+        """keypoints: (n, K, 2 | 3), already in the original image's coordinates and clipped to it (scale_coords)."""
         self._orig_tensor = orig_tensor
         self._orig_img = None
         self.orig_shape = tuple(orig_tensor.shape[-2:]) if orig_tensor is not None else None
@@ -148,16 +184,19 @@ class Results:
         self.path = path
         self.speed = speed or {"preprocess": None, "inference": None, "postprocess": None}
         self.probs = None
-        self.keypoints = None
+        self._kpts = Keypoints(keypoints, self.orig_shape) if keypoints is not None else None
+        self._ksrc = None
         self.obb = None
 
     @classmethod
     def from_batch(cls, batch: torch.Tensor, b: int, names: Dict[int, str], dets: torch.Tensor, n,
                    path: str = "image0.jpg", speed=None, masks: Optional[torch.Tensor] = None,
-                   moff: int = 0) -> "Results":
+                   moff: int = 0, kpt_shape: Optional[tuple] = None) -> "Results":
         """Image b of a predict() batch: boxes = dets[b, :n, :6], the input slice batch[b] and (Segment) the masks
         masks[moff : moff + n], all taken (as tensor views) on first access, so building the B Results of a call
-        costs no tensor operations.  n: the count, or the call's LazyCounts (read from the device on first access)."""
+        costs no tensor operations.  n: the count, or the call's LazyCounts (read from the device on first access).
+        kpt_shape (Pose): (K, ndim); the keypoints are dets[b, :n, 6 : 6 + K·ndim], copied, clipped to the image
+        (scale_coords with equal shapes) and masked by visibility on first access."""
         r = cls.__new__(cls)
         r._batch, r._b, r._dets, r._n = batch, b, dets, n
         r._orig_tensor_v = None
@@ -169,18 +208,23 @@ class Results:
         r._msrc = (masks, moff) if masks is not None else None
         r.path = path
         r.speed = speed or {"preprocess": None, "inference": None, "postprocess": None}
-        r.probs = r.keypoints = r.obb = None
+        r.probs = r.obb = None
+        r._kpts = None
+        r._ksrc = tuple(kpt_shape) if kpt_shape else None
         return r
 
     @classmethod
     def from_image(cls, img_bgr: np.ndarray, path: str, names: Dict[int, str], boxes: torch.Tensor,
-                   masks: Optional[torch.Tensor] = None, speed=None) -> "Results":
+                   masks: Optional[torch.Tensor] = None, speed=None,
+                   keypoints: Optional[torch.Tensor] = None) -> "Results":
         """An image-file / ndarray source: `orig_img` is the HWC uint8 BGR image as loaded (cv2.imread order),
-        boxes are in its coordinates (already mapped back by scale_boxes)."""
-        r = cls(None, names, boxes, masks=masks, path=path, speed=speed)
+        boxes (and keypoints) are in its coordinates (already mapped back by scale_boxes / scale_coords)."""
+        r = cls(None, names, boxes, masks=masks, path=path, speed=speed, keypoints=keypoints)
         r._orig_img = img_bgr
         r.orig_shape = tuple(img_bgr.shape[:2])
         r.boxes.orig_shape = r.orig_shape
+        if r._kpts is not None:
+            r._kpts.orig_shape = r.orig_shape
         if r.masks is not None:
             r.masks.orig_shape = r.orig_shape
         return r
@@ -223,6 +267,22 @@ class Results:
         self._msrc = None
 
     @property
+    def keypoints(self) -> Optional["Keypoints"]:
+        if self._kpts is None and getattr(self, "_ksrc", None) is not None:
+            K, nd = self._ksrc
+            n = self._count
+            k = self._dets[self._b, :n, 6:6 + K * nd].reshape(n, K, nd).clone()
+            k[..., 0].clamp_(0, self.orig_shape[1])  # ops.scale_coords(shape, kpts, shape): gain 1, pad 0, clip
+            k[..., 1].clamp_(0, self.orig_shape[0])
+            self._kpts = Keypoints(k, self.orig_shape)
+        return self._kpts
+
+    @keypoints.setter
+    def keypoints(self, k):
+        self._kpts = k
+        self._ksrc = None
+
+    @property
     def orig_img(self) -> np.ndarray:
         """HWC uint8 copy of the input image, as upstream `convert_torch2numpy_batch` makes it
         ((x.permute(1,2,0)*255).clamp(0,255).to(uint8)); materialised (one device→host copy) on first access."""
@@ -234,23 +294,29 @@ class Results:
     def __len__(self):
         return len(self.boxes)
 
-    def _like(self, orig_tensor, boxes, masks):
-        r = Results(orig_tensor, self.names, boxes, masks, self.path, self.speed)
+    def _like(self, orig_tensor, boxes, masks, keypoints=None):
+        r = Results(orig_tensor, self.names, boxes, masks, self.path, self.speed, keypoints=keypoints)
         if orig_tensor is None:  # image-file / ndarray source: keep the loaded image and its shape
             r._orig_img = self._orig_img
             r.orig_shape = self.orig_shape
             r.boxes.orig_shape = self.orig_shape
             if r.masks is not None:
                 r.masks.orig_shape = self.orig_shape
+            if r.keypoints is not None:
+                r.keypoints.orig_shape = self.orig_shape
         return r
 
     def __getitem__(self, idx):
+        k = self.keypoints
         return self._like(self._orig_tensor, self.boxes.data[idx],
-                          self.masks.data[idx] if self.masks is not None else None)
+                          self.masks.data[idx] if self.masks is not None else None,
+                          k.data[idx].clone() if k is not None else None)
 
     def cpu(self):
+        k = self.keypoints
         return self._like(self._orig_tensor.cpu() if self._orig_tensor is not None else None, self.boxes.data.cpu(),
-                          self.masks.data.cpu() if self.masks is not None else None)
+                          self.masks.data.cpu() if self.masks is not None else None,
+                          k.data.cpu().clone() if k is not None else None)
 
     def summary(self, normalize=False, decimals=5):
         out = []

@@ -448,6 +448,14 @@ struct NmsArgs {
   unsigned long long* keys2; int presorted;
 };
 
+struct KptArgs {  // Pose: keypoint decode of the NMS candidates (csrc/ym_kpts.hip)
+  const float* anchors; int no_tot, kpt_off;  // (B, A, no_tot) fp32 head rows; raw keypoints at [kpt_off, kpt_off + K·ndim)
+  const unsigned long long* keys; const int* counts;  // decode_anchors' candidate keys (B, kstride) and counts (B)
+  float* out; int nk_pad;                     // (B, A, nk_pad) decoded rows (only the candidates' rows are written)
+  int A, kstride, K, ndim, B;
+  int lvl_W[4], lvl_off[4], nl; float lvl_stride[4];
+};
+
 struct LetterboxArgs {
   const unsigned char* src; int h, w, row_bytes, bgr;  // HWC uint8 image (3 channels), BGR or RGB order
   int uh, uw, top, left;                               // resized (unpadded) size and its offset in the canvas
@@ -488,6 +496,7 @@ hipError_t ym_launch_input_max(const float* x, long n, float* ctl, float* out, h
 hipError_t ym_launch_decode(const DecodeArgs& a, hipStream_t st);
 hipError_t ym_launch_nms(const NmsArgs& a, hipStream_t st);
 hipError_t ym_launch_nms_presort(const NmsArgs& a, hipStream_t st);  // ym_misc.hip: keys sorted by 8 WGs per image
+hipError_t ym_launch_kpts(const KptArgs& a, hipStream_t st);  // ym_kpts.hip: Pose keypoints of the candidates
 hipError_t ym_launch_conv_dma_i8(const ConvArgs& a, int dma_cfg, hipStream_t st);  // ym_conv_dma.hip
 hipError_t ym_launch_conv_dma_chain(const ConvArgs& a0, const ConvArgs& a1, int dma_cfg, int* ctl, int cap,
                                     hipStream_t st);  // csrc/ym_conv_dma.hip: two dependent x3 convs, one launch

@@ -183,6 +183,7 @@ struct ym_ctx {
   int dtype = YM_DT_F16, task = 0, nc = 80, nm = 0, reg_max = 16, nl = 3;
   int strides[4] = {8, 16, 32, 0};
   int input_buf = -1, anchor_buf = -1, proto_buf = -1, no = 0;
+  int kpt_K = 0, kpt_ndim = 0, kpt_off = 0;  // pose plans: keypoints, 2 | 3 values each, raw offset in the anchor row
   float* d_lowres = nullptr;  // Segment mask assembly scratch (ym_masks)
   char* d_misc = nullptr;     // 16 KB: ym_input_max statistics region, ym_broadcast_weights control words
   size_t lowres_bytes = 0;
@@ -206,7 +207,7 @@ struct ym_ctx {
   size_t arena_bytes = 0;
   std::vector<size_t> buf_off;
   size_t off_boxes = 0, off_scores = 0, off_cls = 0, off_keys = 0, off_keys2 = 0, off_counts = 0, off_ctl = 0, off_sboxes = 0,
-         off_sareas = 0, off_sup = 0, off_slab = 0, off_cnt = 0, off_chain = 0, slab_bytes = 0;
+         off_sareas = 0, off_sup = 0, off_slab = 0, off_cnt = 0, off_chain = 0, off_kpts = 0, slab_bytes = 0;
   int A = 0, kstride = 0;
   int lvl_W[4] = {0}, lvl_off[4] = {0};
   hipStream_t cap_stream = nullptr;
@@ -305,6 +306,8 @@ struct ym_ctx {
 namespace {
 
 size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+constexpr int kTaskPose = 2;  // blob header task codes: 0 detect, 1 segment, 2 pose
+const char* task_name(int t) { return t == 0 ? "detect" : t == 1 ? "segment" : t == kTaskPose ? "pose" : "unknown"; }
 
 int ensure_workspace(ym_ctx* c, int B, int H, int W) {
   if (c->d_arena && B <= c->cB && H == c->cH && W == c->cW) return YM_OK;
@@ -349,6 +352,8 @@ int ensure_workspace(ym_ctx* c, int B, int H, int W) {
   c->off_slab = off;   off = align_up(off + kMaxLanes * c->slab_bytes, 256);  // one slab region per lane
   c->off_cnt = off;    off = align_up(off + (size_t)kMaxLanes * kSplitCounters * 4, 256);
   c->off_chain = off;  off = align_up(off + (size_t)kChainCtl * 4, 256);  // persistent chain kernel's counters
+  c->off_kpts = off;  // pose plans: decoded keypoints (B, A, nm) fp32, the rows NMS takes its extras from
+  if (c->task == kTaskPose) off = align_up(off + BA * c->nm * 4, 256);
   c->arena_bytes = off;
   hipError_t e = hipMalloc(&c->d_arena, off);
   if (e != hipSuccess) {
@@ -637,6 +642,22 @@ int launch_op(ym_ctx* c, const Op& op, int B, const float* d_in, const ym_infer_
       a.agnostic = args->agnostic; a.B = B; a.nc = c->nc;
       a.max_wh = args->max_wh; a.img_h = (float)c->cH; a.img_w = (float)c->cW;
       a.iou = args->iou;
+      if (c->task == kTaskPose) {
+        // Pose: decode the candidates' keypoints (behind decode_anchors, before any NMS kernel) into their own
+        // (B, A, nm) rows and let NMS carry its nm extras from there; the raw head rows stay as the convs wrote them
+        KptArgs k{};
+        k.anchors = a.anchors; k.no_tot = a.no_tot; k.kpt_off = c->kpt_off;
+        k.keys = a.keys; k.counts = a.counts;
+        k.out = c->scratch<float>(c->off_kpts, (size_t)c->A * c->nm * 4);
+        k.nk_pad = c->nm; k.A = c->A; k.kstride = c->kstride; k.K = c->kpt_K; k.ndim = c->kpt_ndim; k.B = B;
+        k.nl = c->nl;
+        for (int l = 0; l < c->nl; ++l) {
+          k.lvl_W[l] = c->lvl_W[l]; k.lvl_off[l] = c->lvl_off[l]; k.lvl_stride[l] = (float)c->strides[l];
+        }
+        e = ym_launch_kpts(k, st);
+        if (e != hipSuccess) break;
+        a.anchors = k.out; a.no_tot = c->nm; a.mask_off = 0;
+      }
       // low conf (the validator's 0.001): thousands of candidates per image; sort their keys over several
       // workgroups per image first (conf is part of the graph key: the predict default 0.25 never launches these)
       if (args->conf < kPresortConf && c->kstride >= 16384) {
@@ -907,9 +928,9 @@ int ym_load_weights(ym_ctx* c, const void* blob, size_t bytes) {
   for (int l = 0; l < nl; ++l)
     if (h[8 + l] < 1 || h[8 + l] > 64) return fail(YM_EBLOB, "bad stride %d", h[8 + l]);
   const ym_model_desc& want = c->desc;  // what the creator expects (0 = any)
+  if (task < 0 || task > kTaskPose) return fail(YM_EBLOB, "unknown task %d (detect 0, segment 1, pose 2)", task);
   if (want.task && want.task != task + 1)
-    return fail(YM_EBLOB, "blob task %s, context created for %s", task ? "segment" : "detect",
-                want.task == YM_TASK_SEGMENT ? "segment" : "detect");
+    return fail(YM_EBLOB, "blob task %s, context created for %s", task_name(task), task_name(want.task - 1));
   if (want.dtype && want.dtype != dtype + 1) return fail(YM_EBLOB, "blob dtype %d, context created for %d", dtype + 1, want.dtype);
   if (want.scale && h[19] && want.scale != h[19])
     return fail(YM_EBLOB, "blob scale '%c', context created for '%c'", (char)h[19], (char)want.scale);
@@ -917,6 +938,14 @@ int ym_load_weights(ym_ctx* c, const void* blob, size_t bytes) {
   if (input_buf < 0 || input_buf >= nbuf || anchor_buf < 0 || anchor_buf >= nbuf)
     return fail(YM_EBLOB, "bad input/anchor buffer ids");
   if (task == 1 && (proto_buf < 0 || proto_buf >= nbuf)) return fail(YM_EBLOB, "segment plan without proto buffer");
+  const int kpt_K = h[20], kpt_ndim = h[21], kpt_off = h[22];
+  if (task == kTaskPose) {  // the keypoint slice [kpt_off, kpt_off + nm) of the anchor row; nm = K * ndim padded to 4
+    const int arow = h[kHdr + anchor_buf * kBufRec];  // the anchor buffer's channels (its record is inside the blob)
+    if (kpt_K < 1 || (kpt_ndim != 2 && kpt_ndim != 3) || nm < kpt_K * kpt_ndim || (nm & 3) || kpt_off < 0 ||
+        (kpt_off & 3) || (arow & 3) || kpt_off + nm > arow || h[18] != kpt_off)
+      return fail(YM_EBLOB, "bad pose head geometry (K %d, ndim %d, nm %d, offset %d, row %d)", kpt_K, kpt_ndim, nm,
+                  kpt_off, arow);
+  }
   const int32_t* bp = h + kHdr;
   std::vector<BufDesc> bufs(nbuf);
   for (int i = 0; i < nbuf; ++i) bufs[i] = BufDesc{bp[i * kBufRec], bp[i * kBufRec + 1], bp[i * kBufRec + 2]};
@@ -945,6 +974,8 @@ int ym_load_weights(ym_ctx* c, const void* blob, size_t bytes) {
   c->task = task; c->nc = nc; c->nm = nm; c->reg_max = reg_max; c->nl = nl;
   for (int l = 0; l < nl; ++l) c->strides[l] = h[8 + l];
   c->input_buf = input_buf; c->anchor_buf = anchor_buf; c->proto_buf = proto_buf; c->no = h[18];
+  c->kpt_K = task == kTaskPose ? kpt_K : 0; c->kpt_ndim = task == kTaskPose ? kpt_ndim : 0;
+  c->kpt_off = task == kTaskPose ? kpt_off : 0;
   c->bufs = std::move(bufs);
   c->ops = std::move(ops);
   c->blob_host.assign(static_cast<const char*>(blob), static_cast<const char*>(blob) + bytes);  // ym_broadcast_weights
@@ -1453,6 +1484,34 @@ int ym_read_buffer(ym_ctx* c, int b, void* dst, size_t bytes) {
   HIPCK(hipSetDevice(c->device));
   HIPCK(hipDeviceSynchronize());
   HIPCK(hipMemcpy(dst, c->bptr(b), bytes, hipMemcpyDefault));
+  return YM_OK;
+}
+
+int ym_kpt_shape(ym_ctx* c, int* K, int* ndim) {
+  if (!c) return fail(YM_EINVAL, "null context");
+  if (!c->loaded) return fail(YM_ESTATE, "ym_kpt_shape before ym_load_weights");
+  if (K) *K = c->kpt_K;
+  if (ndim) *ndim = c->kpt_ndim;
+  return YM_OK;
+}
+
+int ym_read_scratch(ym_ctx* c, int which, void* dst, size_t bytes) {
+  if (!c || !dst) return fail(YM_EINVAL, "null context or dst");
+  if (!c->d_arena) return fail(YM_ESTATE, "no workspace yet (run ym_infer first)");
+  size_t off = 0, cap = 0;
+  switch (which) {
+    case YM_SCRATCH_KEYS: off = c->off_keys; cap = (size_t)c->cB * c->kstride * 8; break;
+    case YM_SCRATCH_COUNTS: off = c->off_counts; cap = (size_t)c->cB * 4; break;
+    case YM_SCRATCH_KPTS:
+      if (c->task != kTaskPose) return fail(YM_ESTATE, "YM_SCRATCH_KPTS needs a pose plan");
+      off = c->off_kpts; cap = (size_t)c->cB * c->A * c->nm * 4;
+      break;
+    default: return fail(YM_EINVAL, "unknown scratch region %d", which);
+  }
+  if (bytes > cap) return fail(YM_EINVAL, "read of %zu bytes exceeds region size %zu", bytes, cap);
+  HIPCK(hipSetDevice(c->device));
+  HIPCK(hipDeviceSynchronize());
+  HIPCK(hipMemcpy(dst, c->d_arena + off, bytes, hipMemcpyDefault));
   return YM_OK;
 }
 

@@ -7,6 +7,8 @@ detection); here one (n, 6) copy per Results feeds all three formats:
   * json: `{"detections": [{"class_id", "confidence", "bbox": [x1, y1, x2, y2]}, ...]}` with indent 2;
   * csv: header `class_id,confidence,x1,y1,x2,y2`, one row per detection.
 Values are the fp32 tensor values (printed through Python floats, as the reference's numpy float32 -> float).
+Pose results: the json format adds each detection's "keypoints" ([[x, y(, visibility)], ...]), and `draw_keypoints`
+paints them on an image.
 """
 from __future__ import annotations
 
@@ -28,6 +30,30 @@ def _rows(results: Any) -> List[tuple]:
     return [(int(r[5]), r[4], r[0], r[1], r[2], r[3]) for r in arr]
 
 
+def _keypoints(results: Any):
+    k = getattr(results, "keypoints", None)
+    if k is None or len(k) == 0:
+        return None
+    data = k.data
+    return data.detach().cpu().numpy() if hasattr(data, "detach") else np.asarray(data)
+
+
+def draw_keypoints(image: np.ndarray, results: Any, radius: int = 2, color=(0, 255, 0)) -> np.ndarray:
+    """A copy of the HWC uint8 `image` with a (2·radius + 1)² square at every keypoint of `results.keypoints` (those
+    with visibility below 0.5 are skipped); the image itself when the results carry no keypoints."""
+    kp = _keypoints(results)
+    if kp is None:
+        return image
+    out = np.array(image, copy=True)
+    h, w = out.shape[:2]
+    for x, y, *v in kp.reshape(-1, kp.shape[-1]):
+        if v and v[0] < 0.5:
+            continue
+        xi, yi = int(round(float(x))), int(round(float(y)))
+        out[max(yi - radius, 0):min(yi + radius + 1, h), max(xi - radius, 0):min(xi + radius + 1, w)] = color
+    return out
+
+
 def save_detection_results(results: Any, output_path: str, format: str = "txt") -> None:
     """Save one image's detections to `output_path` as 'txt', 'json' or 'csv' (the reference's formats)."""
     Path(output_path).parent.mkdir(parents=True, exist_ok=True)
@@ -42,6 +68,10 @@ def save_detection_results(results: Any, output_path: str, format: str = "txt") 
     elif fmt == "json":
         dets = [{"class_id": c, "confidence": float(conf), "bbox": [float(x1), float(y1), float(x2), float(y2)]}
                 for c, conf, x1, y1, x2, y2 in rows]
+        kp = _keypoints(results)
+        if kp is not None:
+            for d, k in zip(dets, kp):
+                d["keypoints"] = [[float(v) for v in pt] for pt in k]
         with open(output_path, "w") as f:
             json.dump({"detections": dets}, f, indent=2)
     else:

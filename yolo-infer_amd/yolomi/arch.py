@@ -83,20 +83,30 @@ class Param:
 
 
 class GraphBuilder:
-    def __init__(self, scale: str = "n", task: str = "detect", nc: int = NC, quant: bool = False,
-                 fuse=False):
+    def __init__(self, scale: str = "n", task: str = "detect", nc: Optional[int] = None, quant: bool = False,
+                 fuse=False, kpt_shape: Tuple[int, int] = (17, 3), pad_head: bool = True):
         """quant=True builds the int8 (PTQ) plan: 16-channel storage granules and materialised concats (a concat is
         one quantized tensor with its own observer, so the two-source A loader is replaced by requant copies).
         fuse=True (f16 plans) merges each conv that feeds only a following 1x1 conv into one launch (fuse_pairs)
         and runs C3k's two 1x1 convs on the same input as one GEMM; fuse="merge" only the latter (a GEMM with the two
         weight matrices stacked along N: per output channel the same arithmetic as the two convs); fuse="x3" (x3
         plans) both, the conv → 1x1 pairs sized by the pair layout's doubled storage K (the streaming kernel's x3
-        FUSE mode) and the Bottlenecks on conv_bneck's x3 mode."""
+        FUSE mode) and the Bottlenecks on conv_bneck's x3 mode.
+        nc: classes (default 80; 1 for pose plans).  kpt_shape (pose): (keypoints, 2 | 3).  pad_head=False (pose):
+        the head at its Ultralytics channel counts, for walks over the parameters only (yolomi.synth.calibrate); the
+        plan the GPU runs pads them (Detect)."""
         if scale not in SCALES:
             raise ValueError(f"Unsupported size: {scale}")
-        if task not in ("detect", "segment"):
-            raise ValueError(f"task {task!r} has no HIP plan (supported: detect, segment)")
+        if task not in ("detect", "segment", "pose"):
+            raise ValueError(f"task {task!r} has no HIP plan (supported: detect, segment, pose)")
+        if nc is None:
+            nc = 1 if task == "pose" else NC
         self.scale, self.task, self.nc, self.quant = scale, task, nc, quant
+        self.kpt_shape = (int(kpt_shape[0]), int(kpt_shape[1])) if task == "pose" else None
+        if task == "pose" and (self.kpt_shape[0] < 1 or self.kpt_shape[1] not in (2, 3)
+                               or self.kpt_shape[0] * self.kpt_shape[1] > 64):
+            raise ValueError(f"kpt_shape {kpt_shape}: (K, 2 | 3) with K * ndim <= 64")
+        self.pad_head = bool(pad_head)
         self.depth, self.width, self.max_ch = SCALES[scale]
         self.buffers: List[Buffer] = []
         self.ops: List[Op] = []
@@ -144,10 +154,12 @@ class GraphBuilder:
     def conv(self, prefix: str, src: View, c2: int, k: int, s: int, dst: View, act: bool = True,
              res: Optional[View] = None, src1: Optional[View] = None, up0: bool = False, bn: bool = True,
              bias_kind=None, extra=None, anchor_level: int = -1, shuffle2x2: bool = False,
-             catq: Optional[str] = None):
-        """catq: quantisation name of the concat a two-source conv reads (Ultralytics Concat module / cat tensor)."""
+             catq: Optional[str] = None, pc1: Optional[int] = None, pc2: Optional[int] = None):
+        """catq: quantisation name of the concat a two-source conv reads (Ultralytics Concat module / cat tensor).
+        pc1 / pc2: the parameter's own input / output channels where the plan pads them (pose head): the packer fills
+        the c1 - pc1 input columns and c2 - pc2 output rows (and their bias) with zeros."""
         c1 = src.C + (src1.C if src1 is not None else 0)
-        self._conv_params(prefix, c1, c2, k, 1, bn, bias_kind, extra)
+        self._conv_params(prefix, pc1 or c1, pc2 or c2, k, 1, bn, bias_kind, extra)
         assert dst.C == (4 * c2 if shuffle2x2 else c2) or anchor_level >= 0 or shuffle2x2
         fin = src.buf.f * (2 if s == 2 else 1) // (2 if up0 else 1)
         if self.quant and src1 is not None:  # int8: materialise the concat (requant copies into one tensor)
@@ -271,9 +283,22 @@ class GraphBuilder:
 
     def Detect(self, i: int, xs: List[View]):
         nc = self.nc
-        no = nc + 4 * REG_MAX
-        nm = 32 if self.task == "segment" else 0
+        pose = self.task == "pose"
+        ncp = nc  # class channels of the anchor row
+        if pose:
+            # Pose head layout: the class slice and the keypoint slice of the anchor row are padded to multiples of 4
+            # (COCO pose: [64 box | 4 cls | 52 kpt], pitch 120) and cv4's hidden width to a multiple of 16 (51 -> 64),
+            # with zero weight rows / columns and zero bias packed for the pad channels (yolomi.plan), so every conv
+            # launcher's N % 4, 4-aligned output slice and Cin % 8 conditions hold and the pad channels read 0
+            self.nk = self.kpt_shape[0] * self.kpt_shape[1]
+            pad = (lambda v, d: -(-v // d) * d) if self.pad_head else (lambda v, d: v)
+            ncp, self.nk_pad = pad(nc, 4), pad(self.nk, 4)
+        no = ncp + 4 * REG_MAX
+        nm = self.nk_pad if pose else (32 if self.task == "segment" else 0)
+        # no: offset of the nm extras NMS carries in the anchor row (pose: the raw keypoints; the decoded ones NMS
+        # reads live in the runtime's own (B, A, nm) buffer, csrc/ym_kpts.hip)
         self.no, self.nm = no, nm
+        self.kpt_off = no if pose else -1
         anchor = self.buf(no + nm, 0, "anchors", f32=True)
         self.anchor_buf = anchor
         ch0 = xs[0].C
@@ -318,9 +343,10 @@ class GraphBuilder:
             self.dwconv(f"{p}.cv3.{l}.1.0", self.full(e1), self.full(d2))
             e2 = self.buf(c3, f, f"cv3.{l}.1.1", q=f"{p}.cv3.{l}.1.1")
             self.conv(f"{p}.cv3.{l}.1.1", self.full(d2), c3, 1, 1, self.full(e2))
-            self.conv(f"{p}.cv3.{l}.2", self.full(e2), nc, 1, 1, View(anchor, 4 * REG_MAX, nc), act=False,
+            self.conv(f"{p}.cv3.{l}.2", self.full(e2), ncp, 1, 1, View(anchor, 4 * REG_MAX, ncp), act=False,
                       bn=False, bias_kind="cls_b",
-                      extra=dict(nc=nc, stride=STRIDES[l], shift=_cls_shift(self.scale)), anchor_level=l)
+                      extra=dict(nc=nc, stride=STRIDES[l], shift=_cls_shift(self.scale)), anchor_level=l,
+                      pc2=nc if ncp != nc else None)
             if self.task == "segment":  # mask-coefficient branch cv4: Conv(x,c4,3) → Conv(c4,c4,3) → Conv2d(c4,nm,1)
                 c4 = max(ch0 // 4, nm)
                 m1 = self.buf(c4, f, f"cv4.{l}.0", q=f"{p}.cv4.{l}.0")
@@ -329,6 +355,17 @@ class GraphBuilder:
                 self.conv(f"{p}.cv4.{l}.1", self.full(m1), c4, 3, 1, self.full(m2))
                 self.conv(f"{p}.cv4.{l}.2", self.full(m2), nm, 1, 1, View(anchor, no, nm), act=False, bn=False,
                           anchor_level=l)
+            if pose:  # keypoint branch cv4: Conv(x,c4,3) → Conv(c4,c4,3) → Conv2d(c4,nk,1), as Segment's cv4
+                c4 = max(ch0 // 4, self.nk)
+                c4p = -(-c4 // 16) * 16 if self.pad_head else c4
+                pc4 = c4 if c4p != c4 else None
+                k1 = self.buf(c4p, f, f"cv4.{l}.0", q=f"{p}.cv4.{l}.0")
+                self.conv(f"{p}.cv4.{l}.0", x, c4p, 3, 1, self.full(k1), pc2=pc4)
+                k2 = self.buf(c4p, f, f"cv4.{l}.1", q=f"{p}.cv4.{l}.1")
+                self.conv(f"{p}.cv4.{l}.1", self.full(k1), c4p, 3, 1, self.full(k2), pc1=pc4, pc2=pc4)
+                self.conv(f"{p}.cv4.{l}.2", self.full(k2), self.nk_pad, 1, 1, View(anchor, no, self.nk_pad),
+                          act=False, bn=False, anchor_level=l, pc1=pc4,
+                          pc2=self.nk if self.nk_pad != self.nk else None)
         self.params.append(Param(f"{p}.dfl.conv.weight", (1, REG_MAX, 1, 1), "dfl"))
         self.ops.append(Op("decode", dict(anchor=anchor, nc=nc, nm=nm), f"{p}.decode"))
         self.ops.append(Op("nms", dict(nc=nc, nm=nm), f"{p}.nms"))
@@ -585,19 +622,40 @@ def _cls_shift(scale: str) -> float:
     return CLS_BIAS_SHIFT[scale]
 
 
-def infer_arch(sd) -> Tuple[str, str, int]:
+def infer_kpt_shape(sd, kpt_shape: Optional[Tuple[int, int]] = None) -> Optional[Tuple[int, int]]:
+    """kpt_shape of a pose state dict (None for other tasks): the given one, else from the keypoint conv's nk rows,
+    (nk // 3, 3) when nk % 3 == 0, else (nk // 2, 2) — the checkpoint's tensors do not say which."""
+    import numpy as np
+    if "model.23.cv4.0.2.bias" not in sd or any(k.startswith("model.23.proto.") for k in sd):
+        return None
+    nk = int(np.shape(sd["model.23.cv4.0.2.bias"])[0])
+    if kpt_shape is not None:
+        if int(kpt_shape[0]) * int(kpt_shape[1]) != nk:
+            raise ValueError(f"kpt_shape {tuple(kpt_shape)} does not match the checkpoint's {nk} keypoint channels")
+        return int(kpt_shape[0]), int(kpt_shape[1])
+    if nk % 3 == 0:
+        return nk // 3, 3
+    if nk % 2 == 0:
+        return nk // 2, 2
+    raise ValueError(f"{nk} keypoint channels are neither K x 3 nor K x 2")
+
+
+def infer_arch(sd, kpt_shape: Optional[Tuple[int, int]] = None) -> Tuple[str, str, int]:
     """(scale, task, nc) of an Ultralytics-key state dict: the reference takes the architecture from the checkpoint
     (`YOLO(model_path)`, core/model.py:100-110), so a loaded file decides the plan, not the `size` argument.  The
-    task comes from the Proto keys, nc from the last cls conv, the scale from the graph whose every parameter shape
-    matches."""
+    task comes from the Proto keys (segment) or cv4 without Proto (pose; its kpt_shape: infer_kpt_shape), nc from the
+    last cls conv, the scale from the graph whose every parameter shape matches."""
     import numpy as np
     task = "segment" if any(k.startswith("model.23.proto.") for k in sd) else "detect"
+    if task == "detect" and any(k.startswith("model.23.cv4.") for k in sd):
+        task = "pose"
+    kpt_shape = infer_kpt_shape(sd, kpt_shape) if task == "pose" else None
     key = "model.23.cv3.0.2.bias"
     if key not in sd:
         raise ValueError(f"not a YOLO11 detect/segment state dict (no {key!r})")
     nc = int(np.shape(sd[key])[0])
     for scale in SCALES:
-        g = GraphBuilder(scale, task, nc=nc)
+        g = GraphBuilder(scale, task, nc=nc, **(dict(kpt_shape=kpt_shape) if kpt_shape else {}))
         if all(p.kind in ("count", "dfl") or (p.name in sd and tuple(np.shape(sd[p.name])) == tuple(p.shape))
                for p in g.params):
             return scale, task, nc

@@ -27,8 +27,8 @@ def tune_cache_dir() -> str:
 
 class Engine:
     def __init__(self, scale: str, task: str, state_dict: Dict[str, np.ndarray], device: torch.device,
-                 dtype: str = "f16", blob: Optional[bytes] = None, qparams: Optional[Dict] = None, nc: int = 80,
-                 receive: Optional[tuple] = None):
+                 dtype: str = "f16", blob: Optional[bytes] = None, qparams: Optional[Dict] = None,
+                 nc: Optional[int] = 80, receive: Optional[tuple] = None, kpt_shape: Optional[tuple] = None):
         """dtype: 'x3' (split-f16 MFMA, the f16-tolerance plan), 'f16' (throughput), 'f32' (exact parity mode),
         'i8' (PTQ int8) or 'f8' (PTQ fp8 e4m3); the quantized plans need `qparams` from yolomi.quant.calibrate
         (backend 'fp8' for 'f8'), or a packed `blob`.  receive = (rccl comm, root): this rank's context receives the
@@ -38,8 +38,10 @@ class Engine:
         self.scale, self.task, self.dtype = scale, task, dtype
         self.device = device
         self.qparams = qparams
+        if task == "pose" and dtype in QUANT_DTYPES:
+            raise ValueError(f"pose plans are x3 / f16 / f32: there is no PTQ pose plan (dtype {dtype!r})")
         self.graph = GraphBuilder(scale, task, nc=nc, quant=dtype in QUANT_DTYPES,
-                                  fuse=fuse_default(dtype))
+                                  fuse=fuse_default(dtype), **(dict(kpt_shape=kpt_shape) if kpt_shape else {}))
         dev_index = device.index if device.index is not None else torch.cuda.current_device()
         if isinstance(receive, Runtime):  # a context that already received the root's blob (yolomi.dist)
             if receive.n_ops != len(self.graph.ops) or receive.device_index != dev_index:
@@ -53,7 +55,9 @@ class Engine:
         else:
             self.blob = blob if blob is not None else pack_graph(self.graph, state_dict, dtype, qparams)
             self.rt = Runtime(dev_index, self.blob, scale=scale, task=task, dtype=dtype)
-        self.nm = self.graph.nm
+        self.nm = self.graph.nm  # extras per device row (segment: mask coefficients; pose: K·ndim padded to 4)
+        self.kpt_shape = self.graph.kpt_shape  # pose: (K, ndim); the first nk = K·ndim extras are the keypoints
+        self.nk = self.graph.nk if task == "pose" else 0
         self._out: Dict[int, tuple] = {}
         # Per-shape conv tile tables: on the first call of each (B, H, W) a table is taken from the writable tune
         # cache or the committed `tuned/` directory; failing both, ym_tune measures one on this GPU (and caches it).
@@ -269,6 +273,31 @@ class Engine:
         if self.dtype == "f8":
             return out.view(torch.uint8).view(torch.float8_e4m3fn).float()
         return out.float() + 128.0
+
+    def candidates(self, B: int, H: int, W: int):
+        """The last forward's NMS candidates of the first B images (tests): per image the int64 anchor indices, in
+        no fixed order (the low 32 bits of a candidate key are ~anchor)."""
+        from .arch import STRIDES
+        from .lib import SCRATCH_COUNTS, SCRATCH_KEYS
+        A = sum((H // s) * (W // s) for s in STRIDES)
+        kstride = 1
+        while kstride < A:
+            kstride <<= 1
+        counts = torch.empty((B,), dtype=torch.int32)
+        keys = torch.empty((B, kstride), dtype=torch.int64)
+        self.rt.read_scratch(SCRATCH_COUNTS, counts.data_ptr(), 4 * B)
+        self.rt.read_scratch(SCRATCH_KEYS, keys.data_ptr(), 8 * B * kstride)
+        return [0xFFFFFFFF - (keys[b, : min(int(n), A)] & 0xFFFFFFFF) for b, n in enumerate(counts.tolist())]
+
+    def keypoint_rows(self, B: int, H: int, W: int) -> torch.Tensor:
+        """Pose plans: the decoded keypoint buffer (B, A, nm) of the last forward as a CPU tensor (tests).  Only the
+        candidates' rows (candidates()) were written by that forward."""
+        from .arch import STRIDES
+        from .lib import SCRATCH_KPTS
+        A = sum((H // s) * (W // s) for s in STRIDES)
+        out = torch.empty((B, A, self.nm), dtype=torch.float32)
+        self.rt.read_scratch(SCRATCH_KPTS, out.data_ptr(), out.numel() * 4)
+        return out
 
     def raw_shapes(self, B: int, H: int, W: int) -> Dict[int, tuple]:
         """(rows, cols) of every op's pre-activation output in a calibration run (ym_calibrate)."""

@@ -24,7 +24,8 @@ class ModelDesc(C.Structure):
                 ("dtype", C.c_int), ("reserved", C.c_int * 2)]
 
 
-TASK_CODES = {"detect": 1, "segment": 2}
+TASK_CODES = {"detect": 1, "segment": 2, "pose": 3}
+SCRATCH_KEYS, SCRATCH_COUNTS, SCRATCH_KPTS = 0, 1, 2  # ym_read_scratch regions (include/yolomi.h)
 DTYPE_CODES = {"f16": 1, "f32": 2, "i8": 3, "f8": 4, "x3": 5}
 
 
@@ -71,6 +72,8 @@ def load_library(path: os.PathLike = LIB_PATH):
         "ym_num_buffers": (I, [P]),
         "ym_buffer_info": (I, [P, I, C.POINTER(P), C.POINTER(I), C.POINTER(I), C.POINTER(I), C.POINTER(I)]),
         "ym_read_buffer": (I, [P, I, P, C.c_size_t]),
+        "ym_read_scratch": (I, [P, I, P, C.c_size_t]),
+        "ym_kpt_shape": (I, [P, C.POINTER(I), C.POINTER(I)]),
         "ym_input_max": (I, [P, P, C.c_size_t, P, P]),
         "ym_broadcast_weights": (I, [P, P, I, P]),
         "ym_broadcast_weights_local": (I, [C.POINTER(P), I, I, P]),
@@ -96,7 +99,7 @@ EXPORTED = ("ym_create", "ym_load_weights", "ym_broadcast_weights", "ym_broadcas
             "ym_rccl_comm_destroy", "ym_infer", "ym_input_max", "ym_calibrate", "ym_masks", "ym_masks_slots", "ym_letterbox",
             "ym_profile", "ym_profile_replay", "ym_tune", "ym_get_op_cfg", "ym_set_op_cfg", "ym_num_ops", "ym_op_name",
             "ym_num_buffers", "ym_buffer_info", "ym_read_buffer", "ym_sync", "ym_last_error", "ym_destroy",
-            "ym_version", "ym_num_conv_cfgs", "ym_set_debug")
+            "ym_version", "ym_num_conv_cfgs", "ym_set_debug", "ym_read_scratch", "ym_kpt_shape")
 
 DBG_NMS, DBG_DW_MODE, DBG_DW_TILE, DBG_CHAIN, DBG_CHAIN_LAUNCHES, DBG_STEMFUSE, DBG_ATTN_KB = 1, 2, 3, 4, 5, 6, 7
 DBG_PAIRST, DBG_CONV_CFG = 8, 9  # value + 1 (0: default)  # ym_set_debug keys (include/yolomi.h)
@@ -256,6 +259,15 @@ class Runtime:
 
     def read_buffer(self, buf: int, dst_ptr: int, nbytes: int):
         _check(self.lib.ym_read_buffer(self.ctx, buf, C.c_void_p(dst_ptr), nbytes))
+
+    def read_scratch(self, which: int, dst_ptr: int, nbytes: int):
+        _check(self.lib.ym_read_scratch(self.ctx, which, C.c_void_p(dst_ptr), nbytes))
+
+    def kpt_shape(self):
+        """(K, ndim) of a loaded pose plan; (0, 0) for detect / segment plans."""
+        k, d = C.c_int(), C.c_int()
+        _check(self.lib.ym_kpt_shape(self.ctx, C.byref(k), C.byref(d)))
+        return k.value, d.value
 
     def sync(self):
         _check(self.lib.ym_sync(self.ctx))

@@ -20,6 +20,9 @@ keeps fp32 rows.
 
 Blob layout (int32 little-endian; parsed by `csrc/ym_runtime.cpp:ym_load_weights`):
   header[32] | buffers[nbuf][8] | ops[nop][32] | names[nop][48 bytes] | pad to 256 | weights
+Header: [3] task (0 detect, 1 segment, 2 pose) | [4] nc | [5] nm, the extras NMS carries per row (segment: 32 mask
+coefficients; pose: K·ndim padded to 4) | [18] their offset in the anchor row | pose only: [20] K, [21] ndim, [22] offset
+of the raw keypoints in the anchor row, [23] class channels of the anchor row (nc padded to 4); 0 in other plans.
 Conv op record: [1..5] k, s, Cin, N, act | [6..9] src0 buf, coff, C, up0 | [10..12] src1 | [13..16] dst buf, coff,
 anchor level, pixel shuffle | [17..18] residual | [19..21] weight / bias offsets, Kpad | [22..24] int8 QRec, s_in·s_w,
 int32 bias (f16 / x3 plans: r[24] = 1 + offset of a fused depthwise's [9][C] weights ‖ [C] bias, GraphBuilder.fuse_dw;
@@ -98,6 +101,20 @@ def _dw_weights(key: str, sd):
     return np.ascontiguousarray(w.reshape(C, 9).T).astype(np.float32), b  # [9][C]
 
 
+def _pad_channels(w: np.ndarray, b: np.ndarray, N: int, cin: int):
+    """(N', k, k, cin') weights and (N',) bias → (N, k, k, cin), (N,): zero rows / input columns / bias for the pad
+    channels of a pose head (GraphBuilder.Detect).  A zero-bias pad row of an activated conv outputs SiLU(0) = 0."""
+    n0, c0 = w.shape[0], w.shape[3]
+    if (n0, c0) == (N, cin):
+        return w, b
+    assert n0 <= N and c0 <= cin, (w.shape, N, cin)
+    wp = np.zeros((N,) + w.shape[1:3] + (cin,), w.dtype)
+    wp[:n0, :, :, :c0] = w
+    bp = np.zeros(N, b.dtype)
+    bp[:n0] = b
+    return wp, bp
+
+
 X3_WEXP_MAX = 64  # |s| the runtime accepts for an x3 weight scale 2^s (csrc/ym_runtime.cpp conv_args)
 X3_WMAX_LOG2 = 14  # x3 weight scaling: max |w|·2^s in (2^13, 2^14] (fp16 max 65504; csrc/ym_common.h ConvArgs::wsc)
 
@@ -168,6 +185,11 @@ def pack_graph(g: GraphBuilder, sd: Dict[str, np.ndarray], dtype: str = "f16", q
     f8 = dtype == "f8"
     if quant != bool(g.quant):
         raise ValueError("int8/fp8 blobs need GraphBuilder(quant=True), float blobs quant=False")
+    pose = g.task == "pose"
+    if pose and quant:
+        raise ValueError(f"pose plans are x3 / f16 / f32: there is no PTQ pose plan (dtype {dtype!r})")
+    if pose and not g.pad_head:
+        raise ValueError("GraphBuilder(pad_head=False) is not a plan the GPU runs")
     check_state_dict(g, sd)
     if quant:
         from .quant import (BACKENDS, inv32, post_table, post_table_fp8, qrange, quantize_weight,
@@ -204,6 +226,8 @@ def pack_graph(g: GraphBuilder, sd: Dict[str, np.ndarray], dtype: str = "f16", q
         r[0] = OP_IDS[op.kind]
         if op.kind == "conv":
             w, b = _conv_weights(a, sd)  # (N, k, k, cin)
+            if pose:
+                w, b = _pad_channels(w, b, a["c2"], a["c1"])
             src0 = a["src0"]
             C0 = src0.C
             stem = src0.buf is g.input
@@ -252,6 +276,8 @@ def pack_graph(g: GraphBuilder, sd: Dict[str, np.ndarray], dtype: str = "f16", q
                 if dtype not in ("f16", "x3"):
                     raise ValueError(f"op {op.name}: fused conv pairs are f16 / x3 only")
                 w2, b2 = _conv_weights(pair, sd)  # (N2, k2, k2, N)
+                if pose:
+                    w2, b2 = _pad_channels(w2, b2, pair["c2"], pair["c1"])
                 N2, k2 = w2.shape[0], pair["k"]
                 assert w2.shape[1:] == (k2, k2, N)
                 K2 = k2 * k2 * N
@@ -337,7 +363,7 @@ def pack_graph(g: GraphBuilder, sd: Dict[str, np.ndarray], dtype: str = "f16", q
     wbytes = arena.bytes()
     hdr = [0] * 32
     hdr[0], hdr[1], hdr[2] = MAGIC, VERSION, DTYPES[dtype]
-    hdr[3] = 1 if g.task == "segment" else 0
+    hdr[3] = {"detect": 0, "segment": 1, "pose": 2}[g.task]
     hdr[4], hdr[5], hdr[6], hdr[7] = g.nc, g.nm, REG_MAX, len(STRIDES)
     hdr[8:11] = list(STRIDES)
     hdr[11], hdr[12] = len(g.buffers), len(g.ops)
@@ -346,6 +372,8 @@ def pack_graph(g: GraphBuilder, sd: Dict[str, np.ndarray], dtype: str = "f16", q
     hdr[17] = g.proto_buf.id if g.task == "segment" else -1
     hdr[18] = g.no
     hdr[19] = ord(g.scale)  # checked against ym_model_desc.scale
+    if pose:  # hdr[5] (nm) = nk_pad, the extras NMS carries; K, ndim, keypoint offset in the anchor row, class pad
+        hdr[20:24] = [g.kpt_shape[0], g.kpt_shape[1], g.kpt_off, g.no - 4 * REG_MAX]
     head = struct.pack("<32i", *hdr)
     bufs = b"".join(struct.pack("<8i", b.Cs or b.C, b.f, int(b.f32), 0, 0, 0, 0, 0) for b in g.buffers)
     ops = b"".join(struct.pack("<32i", *rr) for rr in op_recs)

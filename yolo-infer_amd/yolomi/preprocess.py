@@ -91,6 +91,21 @@ def letterbox_batch(rt, imgs: Sequence[np.ndarray], device: torch.device, imgsz:
     return out, [im.shape[:2] for im in imgs]
 
 
+def scale_coords(img1_shape, coords: torch.Tensor, img0_shape) -> torch.Tensor:
+    """ops.scale_coords(img1_shape, coords, img0_shape) (padding=True) + clip_coords, in place on a (..., >=2) tensor
+    of x, y[, visibility] (Pose keypoints): the same gain / pad as scale_boxes, x clipped to [0, w0], y to [0, h0]."""
+    gain = min(img1_shape[0] / img0_shape[0], img1_shape[1] / img0_shape[1])
+    pad = (round((img1_shape[1] - img0_shape[1] * gain) / 2 - 0.1),
+           round((img1_shape[0] - img0_shape[0] * gain) / 2 - 0.1))
+    coords[..., 0] -= pad[0]
+    coords[..., 1] -= pad[1]
+    coords[..., 0] /= gain
+    coords[..., 1] /= gain
+    coords[..., 0].clamp_(0, img0_shape[1])
+    coords[..., 1].clamp_(0, img0_shape[0])
+    return coords
+
+
 def scale_boxes(img1_shape, boxes: torch.Tensor, img0_shape) -> torch.Tensor:
     """ops.scale_boxes(img1_shape, boxes, img0_shape) (padding=True) + clip_boxes, in place on an (n, >=4) tensor."""
     gain = min(img1_shape[0] / img0_shape[0], img1_shape[1] / img0_shape[1])

@@ -141,6 +141,9 @@ _MAXM = {n: _max_normal_moments(n) for n in (25, 81, 169)}
 
 # target: on U[0,1) images roughly DETECT_RATE of anchors have best-class score > 0.25
 DETECT_Z = 5.5
+# pose plans (one class): DETECT_Z counts on the max over 80 class scores; with a single class it leaves no anchor
+# above conf 0.25 (max score ~0.06 on yolo11n).  1.5 sigma gives tens of candidates per U[0,1) image
+POSE_DETECT_Z = 1.5
 SPPF_SHIFT = (2.7, 3.7, 4.2)
 SPPF_VAR = (1.45, 1.27, 1.12)
 ATTN_VAR = 0.6
@@ -195,7 +198,8 @@ def calibrate(graph, sd: Dict[str, np.ndarray], in_mean: float = 0.5, in_var: fl
                 bias_name = key + ".bias"
                 if ".cv3." in key:  # class logits: place the bias DETECT_Z std below the conf=0.25 logit
                     thr = math.log(0.25 / 0.75)
-                    sd[bias_name] = (thr - DETECT_Z * np.sqrt(vo) - mo).astype(np.float32)
+                    z = POSE_DETECT_Z if graph.task == "pose" else DETECT_Z
+                    sd[bias_name] = (thr - z * np.sqrt(vo) - mo).astype(np.float32)
                 mo = mo + sd[bias_name].astype(np.float64)
             if a["act"]:
                 mo, vo = _silu_moments(mo, vo)
@@ -244,7 +248,7 @@ def calibrate(graph, sd: Dict[str, np.ndarray], in_mean: float = 0.5, in_var: fl
 def synth_weights(scale: str = "n", task: str = "detect", seed: int = 0) -> Dict[str, np.ndarray]:
     """Ultralytics-style state dict of synthetic weights with calibrated BN stats for yolo11{scale}[-seg]."""
     from .arch import GraphBuilder
-    g = GraphBuilder(scale, task)
+    g = GraphBuilder(scale, task, pad_head=False)  # (pose: the head at its parameters' own channel counts)
     sd = synth_state_dict([(p.name, p.shape, p.kind, p.extra) for p in g.params], seed)
     calibrate(g, sd)
     return sd

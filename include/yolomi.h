@@ -79,7 +79,13 @@ typedef struct {
   const float* d_batch_max; /* NULL: LoadTensor's /255 rule reduces over d_input (the whole batch).  Else a device
                                pointer to ONE float, the max over the GLOBAL batch (batch-sharded multi-GPU: every
                                rank's ym_input_max, all-reduced MAX), read by the forward instead of its shard */
-  int reserved[4];
+  int multi_label;  /* 1: validation mode, Ultralytics non_max_suppression(multi_label=True): every (anchor, class)
+                       pair whose score exceeds conf is a candidate (not only the anchor's best class), the max_nms
+                       best of them by (score, then lower anchor, then lower class) go through NMS.  Detect plans
+                       only (YM_EINVAL for segment plans); a plan with one class takes the single-label path, as
+                       upstream's `multi_label &= nc > 1`.  max_nms <= 32768 in this mode.  0: the predict path.
+                       Any other value: YM_EINVAL.  (Carved out of reserved[4]: size and offsets are unchanged.) */
+  int reserved[3];
 } ym_infer_args;
 
 /* Replaces `YOLO(model_path)` construction (core/model.py:100-116): create a context on `device`. */
@@ -177,7 +183,9 @@ int ym_kpt_shape(ym_ctx* ctx, int* K, int* ndim);
 /* Introspection for tests: copy the first `bytes` of a scratch region of the last forward to `dst`; synchronous.
  * YM_SCRATCH_KEYS: the candidate keys, per image `kstride` (the power of two >= A) uint64 words, score bits << 32 |
  * ~anchor, in no fixed order; YM_SCRATCH_COUNTS: the B candidate counts (int32); YM_SCRATCH_KPTS (pose plans): the
- * decoded keypoint rows (B, A, nm) fp32, written for the candidates' anchors only. */
+ * decoded keypoint rows (B, A, nm) fp32, written for the candidates' anchors only.
+ * After a multi-label forward (ym_infer_args.multi_label = 1) YM_SCRATCH_COUNTS holds the per-image (anchor, class)
+ * PAIR counts, before the max_nms cut, and YM_SCRATCH_KEYS the unused single-label keys. */
 #define YM_SCRATCH_KEYS 0
 #define YM_SCRATCH_COUNTS 1
 #define YM_SCRATCH_KPTS 2

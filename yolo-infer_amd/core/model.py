@@ -358,7 +358,22 @@ class YOLO11Model:
     def train(self, *a, **k):
         raise NotImplementedError("training is out of scope for the MI355X inference path (SURVEY §2)")
 
-    val = export = train
+    export = train
+
+    def val(self, data=None, imgsz: int = 640, batch: int = 16, conf: float = 0.001, iou: float = 0.7,
+            max_det: int = 300, **ignored):
+        """Ultralytics `model.val(data=...)` for detect plans (reference core/validator.py:141): the val loader's rect
+        batches, `Engine.run(multi_label=True)` per batch, mAP / precision / recall as upstream computes them
+        (yolomi/val.py).  data: a dataset YAML (path / val / names), a directory with images/ and labels/, or a list
+        of (HWC uint8 BGR ndarray, (m, 5) normalised labels).  Returns an object with `.box.map / .map50 / .map75 /
+        .mp / .mr`, `.speed` and `.results_dict`.  Other Ultralytics val keywords are accepted and ignored."""
+        from yolomi.val import run_val
+        if data is None:
+            raise ValueError("val() needs data: a dataset YAML, a directory with images/ and labels/, or a list")
+        if ignored:
+            logger.info(f"val: ignoring {sorted(ignored)}")
+        return run_val(self.model.engine, data, imgsz=int(imgsz), batch=int(batch), conf=float(conf), iou=float(iou),
+                       max_det=int(max_det))
 
     def __repr__(self) -> str:
         return (f"YOLO11Model(task={self.task}, size={self.size}, "

@@ -3,13 +3,16 @@
 `benchmark_speed` (reference `core/validator.py:158-221`) sweeps image sizes x batch sizes, times
 `YOLO11Model.benchmark` (100 predicts after 10 warm-ups, `core/model.py:253-291`), adds `images_per_second`
 (`validator.py:209`), summarises (`:363-386`) and writes `benchmark_results.json` + `benchmark_summary.txt`
-(`:509-545`) — same schema here.  Dataset validation (`validate`/`compare_models`/`cross_validate`) is out of scope
-(needs datasets and the Ultralytics val loop); `evaluate_detections` is the offline mAP used instead.
+(`:509-545`) — same schema here.  `validate` (reference `:86-156`) runs `YOLO11Model.val` (yolomi/val.py: the val
+loader's rect batches, multi-label NMS on the GPU, upstream's mAP / precision / recall) and returns the reference's
+`_process_validation_results` schema; `compare_models` / `cross_validate` stay out of scope.  `evaluate_detections` is
+the offline mAP on detections the caller already holds.
 """
 from __future__ import annotations
 
 import json
 import logging
+import time
 from datetime import datetime
 from pathlib import Path
 from typing import Any, Dict, List, Optional, Union
@@ -43,6 +46,47 @@ class YOLO11Validator:
         fh.setLevel(logging.INFO)
         fh.setFormatter(logging.Formatter("%(asctime)s - %(name)s - %(levelname)s - %(message)s"))
         logger.addHandler(fh)
+
+    def validate(self, data: Union[str, Path], imgsz: int = 640, batch: int = 16, conf: float = 0.001,
+                 iou: float = 0.6, save_json: bool = True, save_hybrid: bool = False, augment: bool = False,
+                 verbose: bool = True, **kwargs) -> Dict[str, Any]:
+        """Reference signature (core/validator.py:86-98).  save_json / save_hybrid / augment are accepted and ignored
+        (no COCO-JSON output, no hybrid labels, no TTA here)."""
+        ignored = {k: v for k, v in (("save_json", save_json), ("save_hybrid", save_hybrid), ("augment", augment)) if v}
+        if ignored:
+            logger.info(f"validate: ignoring {sorted(ignored)} (not implemented on this path)")
+        logger.info(f"Validation parameters: imgsz={imgsz}, batch={batch}, conf={conf}, iou={iou}")
+        t0 = time.time()
+        results = self.model.val(data=data, imgsz=imgsz, batch=batch, conf=conf, iou=iou, verbose=verbose, **kwargs)
+        out = self._process_validation_results(results, time.time() - t0)
+        self.validation_history.append(out)
+        self._save_validation_summary(out)
+        return out
+
+    def _process_validation_results(self, results: Any, validation_time: float) -> Dict[str, Any]:
+        out: Dict[str, Any] = {"timestamp": datetime.now().isoformat(), "validation_time_seconds": validation_time,
+                               "device": self.device, "model_info": self.model.get_model_info()}
+        box = getattr(results, "box", None)
+        if box is not None:
+            pairs = (("mAP50-95", "map"), ("mAP50", "map50"), ("mAP75", "map75"), ("precision", "mp"), ("recall", "mr"))
+            out["box_metrics"] = {k: float(getattr(box, a)) for k, a in pairs if hasattr(box, a)}
+        if hasattr(results, "speed"):
+            out["speed_metrics"] = {k: float(v) for k, v in results.speed.items()}
+        return out
+
+    def _save_validation_summary(self, results: Dict[str, Any]):
+        with open(self.output_dir / "validation_summary.txt", "w") as f:
+            f.write("YOLO11 Validation Summary\n" + "=" * 50 + "\n\n")
+            f.write(f"Timestamp: {results['timestamp']}\n")
+            f.write(f"Validation time: {results['validation_time_seconds']:.2f} seconds\n")
+            f.write(f"Device: {results['device']}\n\nModel Information:\n" + "-" * 20 + "\n")
+            for k, v in results["model_info"].items():
+                f.write(f"  {k}: {v}\n")
+            for title, key in (("Box Detection Metrics", "box_metrics"), ("Speed Metrics", "speed_metrics")):
+                if key in results:
+                    f.write(f"\n{title}:\n" + "-" * (len(title) + 1) + "\n")
+                    for k, v in results[key].items():
+                        f.write(f"  {k}: {v:.4f}\n")
 
     def benchmark_speed(self, test_data, num_runs: int = 100, warmup_runs: int = 10,
                         batch_sizes: List[int] = [1, 8, 16, 32],

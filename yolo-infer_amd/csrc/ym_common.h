@@ -448,6 +448,68 @@ struct NmsArgs {
   unsigned long long* keys2; int presorted;
 };
 
+// ---- shared by the NMS kernels (csrc/ym_misc.hip nms_image, csrc/ym_nms_ml.hip): one definition of the sort and of
+// the IoU arithmetic, so the single-label and the multi-label path cannot drift apart
+constexpr int NMS_T = 1024;  // threads of an NMS / key-sort workgroup
+
+// A step whose stride is <= 64 only pairs elements inside the 128-element run a wave's 64 consecutive i cover (i =
+// tid + NMS_T m), so consecutive such steps need no workgroup barrier: the wave's own LDS operations are in order.
+// A barrier is taken after a step whose stride, or the next step's, is above 64 (LDS layout-independent; n2 a power
+// of two >= 2).
+__device__ __forceinline__ void bitonic_sort_desc(unsigned long long* k, int n2, int tid) {
+  for (int size = 2; size <= n2; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int i = tid; i < (n2 >> 1); i += NMS_T) {
+        const int lo = ((i & ~(stride - 1)) << 1) | (i & (stride - 1));  // (i / stride) * 2 stride + i % stride
+        const int hi = lo + stride;
+        const bool desc = ((lo & size) == 0);
+        const unsigned long long x = k[lo], y = k[hi];
+        if ((x < y) == desc) { k[lo] = y; k[hi] = x; }
+      }
+      const int next = stride > 1 ? stride >> 1 : (size < n2 ? size : 0);  // the next step's stride (0: done)
+      if (stride > 64 || next > 64 || next == 0) {
+        __syncthreads();
+      } else {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      }
+    }
+  }
+}
+
+__device__ __forceinline__ bool iou_gt(const float4 bi, float ai_area, const float4 bj, float aj_area, double thr) {
+  const float xx1 = fmaxf(bi.x, bj.x), yy1 = fmaxf(bi.y, bj.y);
+  const float xx2 = fminf(bi.z, bj.z), yy2 = fminf(bi.w, bj.w);
+  const float w = fmaxf(0.0f, __fsub_rn(xx2, xx1));
+  const float h = fmaxf(0.0f, __fsub_rn(yy2, yy1));
+  const float inter = ym_opaque(w * h);  // one rounding per operation, as torchvision's CPU kernel (no fused FMA)
+  const float ovr = __fdiv_rn(inter, __fsub_rn(__fadd_rn(ai_area, aj_area), inter));
+  return (double)ovr > thr;
+}
+
+// Multi-label candidate stage + top-max_nms selection (csrc/ym_nms_ml.hip; ym_infer_args.multi_label)
+struct MlState {  // per image
+  unsigned long long thr;  // the digits of the cut chosen so far (60-bit key value, lower digits 0); final: the cut
+  int need;                // keys still to take inside the chosen bin
+  int done;                // the cut is final
+  int selcnt;              // keys appended to the image's `sel` row
+  int pad;
+};
+struct MlArgs {
+  const float* anchors; int no_tot, cls_off;  // (B, A, no_tot) fp32 head rows; class logits at [cls_off, cls_off + nc)
+  int A, nc, B;
+  float conf; int has_classes; unsigned int classes[4];
+  int max_nms, cap;          // cap: keys per image row of sel / sel2 (a multiple of 2,048, >= max_nms)
+  int* counts;               // (B) candidate pairs before the cut (YM_SCRATCH_COUNTS)
+  unsigned int* hist;        // (B, 1024)
+  MlState* state;            // (B)
+  unsigned long long* sel;   // (B, cap) selected keys; sorted descending at the end
+  unsigned long long* sel2;  // (B, cap) chunk-sorted keys
+  int* seln;                 // (B) keys selected = min(pairs, max_nms): the NMS kernel's counts
+  FDiv div_nc;               // set by the launcher
+};
+
 struct KptArgs {  // Pose: keypoint decode of the NMS candidates (csrc/ym_kpts.hip)
   const float* anchors; int no_tot, kpt_off;  // (B, A, no_tot) fp32 head rows; raw keypoints at [kpt_off, kpt_off + K·ndim)
   const unsigned long long* keys; const int* counts;  // decode_anchors' candidate keys (B, kstride) and counts (B)
@@ -496,6 +558,10 @@ hipError_t ym_launch_input_max(const float* x, long n, float* ctl, float* out, h
 hipError_t ym_launch_decode(const DecodeArgs& a, hipStream_t st);
 hipError_t ym_launch_nms(const NmsArgs& a, hipStream_t st);
 hipError_t ym_launch_nms_presort(const NmsArgs& a, hipStream_t st);  // ym_misc.hip: keys sorted by 8 WGs per image
+// ym_nms_ml.hip: multi-label candidates -> top max_nms -> sort -> NMS (n: nms_image's arguments, keys / counts / kstride
+// those of the selected keys)
+hipError_t ym_launch_nms_ml(const MlArgs& m, const NmsArgs& n, hipStream_t st);
+const void* ym_nms_ml_kernel();  // its NMS kernel (takes NmsArgs: graph replays re-point its rows as nms_image's)
 hipError_t ym_launch_kpts(const KptArgs& a, hipStream_t st);  // ym_kpts.hip: Pose keypoints of the candidates
 hipError_t ym_launch_conv_dma_i8(const ConvArgs& a, int dma_cfg, hipStream_t st);  // ym_conv_dma.hip
 hipError_t ym_launch_conv_dma_chain(const ConvArgs& a0, const ConvArgs& a1, int dma_cfg, int* ctl, int cap,

@@ -1211,7 +1211,6 @@ __global__ __launch_bounds__(256) void decode_anchors(const DecodeArgs a) {
 // suppress iff IoU > iou (compared in double), keep <= max_det, clip to the image.  Up to NMS_LDS candidates
 // everything (keys, boxes, areas, flags) lives in LDS, so the serial scan costs LDS latency per candidate;
 // larger candidate sets fall back to the same algorithm on global scratch.
-constexpr int NMS_T = 1024;
 constexpr int NMS_LDS = 4096;
 constexpr int NMS_BM = 512;  // bit-matrix path: 512 x 8 words of 64 bits (32 KB) behind the first 512 boxes
 // blocked path (NMS_BM < n, up to NMS_BLK_MAX candidates after max_nms, e.g. the validator's conf 0.001 at 640²: up to
@@ -1234,32 +1233,6 @@ constexpr int NR_BB = 0, NR_BA = NR_BB + 2 * NMS_BLK, NR_BAI = NR_BA + NMS_BLK /
               NR_KB = NR_CCM + NMS_W * NMS_NC, NR_KA = NR_KB + 2 * NMS_KEEP, NR_KNEXT = NR_KA + NMS_KEEP / 2,
               NR_KHEAD = NR_KNEXT + NMS_KEEP / 2, NMS_REG = NR_KHEAD + NMS_NC / 2;
 constexpr int NMS_BLK_MAX = NMS_SORT - NMS_REG;  // candidates (after max_nms) the blocked path takes: 12,224
-
-// A step whose stride is <= 64 only pairs elements inside the 128-element run a wave's 64 consecutive i cover (i =
-// tid + NMS_T m), so consecutive such steps need no workgroup barrier: the wave's own LDS operations are in order.
-// A barrier is taken after a step whose stride, or the next step's, is above 64 (LDS layout-independent; n2 a power
-// of two >= 2).
-__device__ __forceinline__ void bitonic_sort_desc(unsigned long long* k, int n2, int tid) {
-  for (int size = 2; size <= n2; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int i = tid; i < (n2 >> 1); i += NMS_T) {
-        const int lo = ((i & ~(stride - 1)) << 1) | (i & (stride - 1));  // (i / stride) * 2 stride + i % stride
-        const int hi = lo + stride;
-        const bool desc = ((lo & size) == 0);
-        const unsigned long long x = k[lo], y = k[hi];
-        if ((x < y) == desc) { k[lo] = y; k[hi] = x; }
-      }
-      const int next = stride > 1 ? stride >> 1 : (size < n2 ? size : 0);  // the next step's stride (0: done)
-      if (stride > 64 || next > 64 || next == 0) {
-        __syncthreads();
-      } else {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      }
-    }
-  }
-}
 
 // one output row [x1 y1 x2 y2 conf cls coef_0 .. coef_nm-1]: box clipped to the image; a Segment head's nm mask
 // coefficients are fetched as float4s all issued before the first store (a scalar load-store loop waited one memory
@@ -1291,16 +1264,6 @@ __device__ __forceinline__ void write_det(const NmsArgs& a, float* r, size_t anc
   r[3] = fminf(fmaxf(v.w, 0.f), a.img_h);
   r[4] = sc;
   r[5] = (float)cl;
-}
-
-__device__ __forceinline__ bool iou_gt(const float4 bi, float ai_area, const float4 bj, float aj_area, double thr) {
-  const float xx1 = fmaxf(bi.x, bj.x), yy1 = fmaxf(bi.y, bj.y);
-  const float xx2 = fminf(bi.z, bj.z), yy2 = fminf(bi.w, bj.w);
-  const float w = fmaxf(0.0f, __fsub_rn(xx2, xx1));
-  const float h = fmaxf(0.0f, __fsub_rn(yy2, yy1));
-  const float inter = ym_opaque(w * h);  // one rounding per operation, as torchvision's CPU kernel (no fused FMA)
-  const float ovr = __fdiv_rn(inter, __fsub_rn(__fadd_rn(ai_area, aj_area), inter));
-  return (double)ovr > thr;
 }
 
 __global__ __launch_bounds__(NMS_T) void nms_image(const NmsArgs a) {

@@ -79,6 +79,7 @@ constexpr float kPresortConf = 0.1f;  // NMS keys presorted over several workgro
 constexpr int kMaxLanes = 4;           // concurrent batch slices in one forward graph (<= GPU_MAX_HW_QUEUES)
 constexpr size_t kMaxGraphs = 16;      // captured forwards cached per context (the oldest is retired first)
 constexpr size_t kMiscBytes = 16384;  // ym_ctx::d_misc
+constexpr int kMlCap = 32768;  // multi-label mode: selected keys per image (max_nms up to this; csrc/ym_nms_ml.hip)
 
 enum OpKind { OP_INPUT = 1, OP_CONV = 2, OP_DW = 3, OP_SPPF = 4, OP_ATTN = 5, OP_DECODE = 6, OP_NMS = 7, OP_REQ = 8 };
 
@@ -125,7 +126,8 @@ bool find_nms_nodes(GraphEntry& ge) {
     hipGraphNodeType t;
     if (hipGraphNodeGetType(n, &t) != hipSuccess || t != hipGraphNodeTypeKernel) continue;
     hipKernelNodeParams p{};
-    if (hipGraphKernelNodeGetParams(n, &p) != hipSuccess || p.func != ym_nms_kernel()) continue;
+    if (hipGraphKernelNodeGetParams(n, &p) != hipSuccess || (p.func != ym_nms_kernel() && p.func != ym_nms_ml_kernel()))
+      continue;  // (both NMS kernels take one NmsArgs)
     if (!p.kernelParams || !p.kernelParams[0]) return false;
     ge.nms_nodes.push_back(n);
     ge.nms_args.push_back(*static_cast<const NmsArgs*>(p.kernelParams[0]));
@@ -209,6 +211,10 @@ struct ym_ctx {
   size_t off_boxes = 0, off_scores = 0, off_cls = 0, off_keys = 0, off_keys2 = 0, off_counts = 0, off_ctl = 0, off_sboxes = 0,
          off_sareas = 0, off_sup = 0, off_slab = 0, off_cnt = 0, off_chain = 0, off_kpts = 0, slab_bytes = 0;
   int A = 0, kstride = 0;
+  // multi-label mode (ym_infer_args.multi_label): its scratch joins the arena at the first workspace (re)build after a
+  // multi-label call was seen (check_call sets ml_want), so a context that never validates pays nothing
+  bool ml_want = false, ml_have = false;
+  size_t off_ml_sel = 0, off_ml_sel2 = 0, off_ml_hist = 0, off_ml_state = 0, off_ml_seln = 0;
   int lvl_W[4] = {0}, lvl_off[4] = {0};
   hipStream_t cap_stream = nullptr;
   // lanes: the batch is cut into image slices whose op chains are captured as parallel branches of one graph, so
@@ -310,7 +316,7 @@ constexpr int kTaskPose = 2;  // blob header task codes: 0 detect, 1 segment, 2 
 const char* task_name(int t) { return t == 0 ? "detect" : t == 1 ? "segment" : t == kTaskPose ? "pose" : "unknown"; }
 
 int ensure_workspace(ym_ctx* c, int B, int H, int W) {
-  if (c->d_arena && B <= c->cB && H == c->cH && W == c->cW) return YM_OK;
+  if (c->d_arena && B <= c->cB && H == c->cH && W == c->cW && (!c->ml_want || c->ml_have)) return YM_OK;
   const int nB = (H == c->cH && W == c->cW && B < c->cB) ? c->cB : B;
   c->clear_graphs();
   if (c->d_arena) {
@@ -354,6 +360,14 @@ int ensure_workspace(ym_ctx* c, int B, int H, int W) {
   c->off_chain = off;  off = align_up(off + (size_t)kChainCtl * 4, 256);  // persistent chain kernel's counters
   c->off_kpts = off;  // pose plans: decoded keypoints (B, A, nm) fp32, the rows NMS takes its extras from
   if (c->task == kTaskPose) off = align_up(off + BA * c->nm * 4, 256);
+  c->ml_have = c->ml_want;
+  if (c->ml_have) {  // B * max_nms-scaled: two key rows, the select histogram and state per image
+    c->off_ml_sel = off;   off = align_up(off + (size_t)nB * kMlCap * 8, 256);
+    c->off_ml_sel2 = off;  off = align_up(off + (size_t)nB * kMlCap * 8, 256);
+    c->off_ml_hist = off;  off = align_up(off + (size_t)nB * 1024 * 4, 256);
+    c->off_ml_state = off; off = align_up(off + (size_t)nB * sizeof(MlState), 256);
+    c->off_ml_seln = off;  off = align_up(off + (size_t)nB * 4, 256);
+  }
   c->arena_bytes = off;
   hipError_t e = hipMalloc(&c->d_arena, off);
   if (e != hipSuccess) {
@@ -658,6 +672,26 @@ int launch_op(ym_ctx* c, const Op& op, int B, const float* d_in, const ym_infer_
         if (e != hipSuccess) break;
         a.anchors = k.out; a.no_tot = c->nm; a.mask_off = 0;
       }
+      if (args->multi_label && c->nc > 1) {
+        // every (anchor, class) pair above conf: candidates, the max_nms best, their sort and the NMS in
+        // csrc/ym_nms_ml.hip (decode_anchors has written the boxes; its own keys go unused)
+        MlArgs m{};
+        m.anchors = a.anchors; m.no_tot = a.no_tot; m.cls_off = 4 * c->reg_max;
+        m.A = c->A; m.nc = c->nc; m.B = B;
+        m.conf = args->conf; m.has_classes = args->has_classes;
+        for (int i = 0; i < 4; ++i) m.classes[i] = args->classes[i];
+        m.max_nms = args->max_nms; m.cap = kMlCap;
+        m.counts = c->scratch<int>(c->off_counts, 4);
+        m.hist = c->scratch<unsigned int>(c->off_ml_hist, 1024 * 4);
+        m.state = c->scratch<MlState>(c->off_ml_state, sizeof(MlState));
+        m.sel = c->scratch<unsigned long long>(c->off_ml_sel, (size_t)kMlCap * 8);
+        m.sel2 = c->scratch<unsigned long long>(c->off_ml_sel2, (size_t)kMlCap * 8);
+        m.seln = c->scratch<int>(c->off_ml_seln, 4);
+        a.keys = m.sel; a.kstride = kMlCap; a.counts = m.seln;
+        a.scores = nullptr; a.cls = nullptr;
+        e = ym_launch_nms_ml(m, a, st);
+        break;
+      }
       // low conf (the validator's 0.001): thousands of candidates per image; sort their keys over several
       // workgroups per image first (conf is part of the graph key: the predict default 0.25 never launches these)
       if (args->conf < kPresortConf && c->kstride >= 16384) {
@@ -686,6 +720,15 @@ int check_call(ym_ctx* c, const float* d_in, int B, int H, int W, const ym_infer
   if (args->max_det < 1 || args->max_nms < 1) return fail(YM_EINVAL, "max_det/max_nms must be >= 1");
   if (args->max_det > 1024) return fail(YM_EINVAL, "max_det %d > 1024 is not supported", args->max_det);
   if (args->counts_after_dets != 0 && args->counts_after_dets != 1) return fail(YM_EINVAL, "counts_after_dets is 0 or 1");
+  if (args->multi_label != 0 && args->multi_label != 1) return fail(YM_EINVAL, "multi_label is 0 or 1");
+  if (args->multi_label && c->nc > 1) {  // (nc == 1: the single-label path, as upstream's multi_label &= nc > 1)
+    if (c->task != 0)
+      return fail(YM_EINVAL, "multi_label: %s plans are not supported (validation mode is for detect plans)",
+                  task_name(c->task));
+    if (c->nc > 128) return fail(YM_EINVAL, "multi_label: nc %d > 128 is not supported", c->nc);
+    if (args->max_nms > kMlCap) return fail(YM_EINVAL, "multi_label: max_nms %d > %d is not supported", args->max_nms, kMlCap);
+    c->ml_want = true;
+  }
   c->call_B = B;  // (launch_forward sets it again; eager per-op paths launch the NMS op directly)
   return YM_OK;
 }

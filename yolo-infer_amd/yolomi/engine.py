@@ -152,7 +152,7 @@ class Engine:
     def run(self, x: torch.Tensor, conf=0.25, iou=0.7, max_det=300, classes: Optional[Sequence[int]] = None,
             agnostic=False, in_eps=None, use_graph=True, max_nms=30000, max_wh=7680.0, lanes=None,
             batch_max: Optional[torch.Tensor] = None, dets_out: Optional[torch.Tensor] = None,
-            counts_after: bool = False):
+            counts_after: bool = False, multi_label=False):
         """x: (B,3,H,W) float32 contiguous on this device. Returns the engine-owned (dets, counts) tensors, or
         (dets_out, counts) when the caller hands in its own (>= B, max_det, 6 + nm) fp32 rows (predict(): a fresh
         tensor per call, written by the NMS kernel directly — a cached graph re-points its NMS nodes, no copy).
@@ -160,7 +160,9 @@ class Engine:
         rank takes LoadTensor's /255 decision from it instead of from its own shard).
         counts_after (with dets_out = the first B*max_det rows of a flat buffer, see rows_buffer): the NMS also writes
         this call's B detection counts as int32 words right behind those rows, so the caller can read them later
-        (predict() reads them lazily: no host sync per call)."""
+        (predict() reads them lazily: no host sync per call).
+        multi_label: validation mode — every (anchor, class) pair above conf is an NMS candidate (Ultralytics
+        non_max_suppression(multi_label=True)); detect plans."""
         assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4 and x.shape[1] == 3
         B, _, H, W = x.shape
         if in_eps is None:
@@ -172,13 +174,14 @@ class Engine:
             assert batch_max.is_cuda and batch_max.dtype == torch.float32 and batch_max.numel() >= 1
             bm = batch_max.data_ptr()
         akey = (conf, iou, max_det, max_nms, agnostic, max_wh, in_eps, tuple(classes) if classes is not None else None,
-                use_graph, lanes, bm, counts_after)
+                use_graph, lanes, bm, counts_after, multi_label)
         args = self._args_cache.get(akey)
         if args is None:
             if len(self._args_cache) > 64:
                 self._args_cache.clear()
             args = self._args_cache[akey] = Runtime.make_args(conf, iou, max_det, max_nms, agnostic, max_wh, in_eps,
-                                                              classes, use_graph, lanes, bm, counts_after)
+                                                              classes, use_graph, lanes, bm, counts_after,
+                                                              multi_label)
         dets, counts = self.outputs(B, max_det)
         if dets_out is not None:
             assert (dets_out.is_cuda and dets_out.dtype == torch.float32 and dets_out.is_contiguous()
@@ -288,6 +291,15 @@ class Engine:
         self.rt.read_scratch(SCRATCH_COUNTS, counts.data_ptr(), 4 * B)
         self.rt.read_scratch(SCRATCH_KEYS, keys.data_ptr(), 8 * B * kstride)
         return [0xFFFFFFFF - (keys[b, : min(int(n), A)] & 0xFFFFFFFF) for b, n in enumerate(counts.tolist())]
+
+    def candidate_counts(self, B: int):
+        """The last forward's per-image candidate counts (YM_SCRATCH_COUNTS): anchors above conf, or after a
+        multi_label run the (anchor, class) pairs above conf, before the max_nms cut."""
+        from .lib import SCRATCH_COUNTS
+        counts = torch.empty((B,), dtype=torch.int32)
+        torch.cuda.synchronize(self.device)
+        self.rt.read_scratch(SCRATCH_COUNTS, counts.data_ptr(), 4 * B)
+        return counts.tolist()
 
     def keypoint_rows(self, B: int, H: int, W: int) -> torch.Tensor:
         """Pose plans: the decoded keypoint buffer (B, A, nm) of the last forward as a CPU tensor (tests).  Only the

@@ -37,7 +37,7 @@ class InferArgs(C.Structure):
     _fields_ = [("conf", C.c_float), ("max_wh", C.c_float), ("iou", C.c_double), ("max_det", C.c_int),
                 ("max_nms", C.c_int), ("agnostic", C.c_int), ("in_eps", C.c_float), ("has_classes", C.c_int),
                 ("classes", C.c_uint32 * 4), ("use_graph", C.c_int), ("lanes", C.c_int), ("counts_after_dets", C.c_int),
-                ("d_batch_max", C.c_void_p), ("reserved", C.c_int * 4)]
+                ("d_batch_max", C.c_void_p), ("multi_label", C.c_int), ("reserved", C.c_int * 3)]
 
 
 _lib = None
@@ -186,8 +186,12 @@ class Runtime:
 
     @staticmethod
     def make_args(conf=0.25, iou=0.7, max_det=300, max_nms=30000, agnostic=False, max_wh=7680.0, in_eps=1.1920929e-07,
-                  classes=None, use_graph=True, lanes=1, batch_max_ptr=0, counts_after_dets=False) -> InferArgs:
+                  classes=None, use_graph=True, lanes=1, batch_max_ptr=0, counts_after_dets=False,
+                  multi_label=False) -> InferArgs:
+        """multi_label: validation mode (ym_infer_args.multi_label); an int other than 0 / 1 is passed through (and
+        rejected by the library)."""
         a = InferArgs()
+        a.multi_label = int(multi_label)
         a.counts_after_dets = int(bool(counts_after_dets))
         a.d_batch_max = batch_max_ptr or None
         a.conf, a.iou, a.max_det, a.max_nms = float(conf), float(iou), int(max_det), int(max_nms)

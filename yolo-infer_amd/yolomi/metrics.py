@@ -1,10 +1,12 @@
-"""Offline detection metrics: mAP50 / mAP50-95.
+"""Offline detection metrics: mAP50 / mAP50-95, precision / recall.
 
 Semantics of the numbers the reference reads from Ultralytics val (`core/validator.py:339-352`:
 `results.box.map`, `.map50`, `.map75`, `.mp`, `.mr`): per class, predictions sorted by confidence, a prediction is
 a TP at IoU threshold t as upstream `BaseValidator.match_predictions` decides it (ultralytics 8.3.x,
 engine/validator.py); AP = area under the 101-point COCO-interpolated precision envelope; mAP = mean over classes
-present in the ground truth, mAP50-95 = mean over t ∈ {0.50, 0.55, ..., 0.95}.
+present in the ground truth, mAP50-95 = mean over t ∈ {0.50, 0.55, ..., 0.95}.  Precision / recall (`.mp`, `.mr`) are
+upstream `ap_per_class`'s: per class the IoU-0.5 precision and recall curves over a 1000-point confidence grid, read at
+the confidence that maximises the smoothed class-mean F1, then averaged over classes.
 """
 from __future__ import annotations
 
@@ -60,8 +62,42 @@ def compute_ap(recall: np.ndarray, precision: np.ndarray) -> float:
     return float(((y[1:] + y[:-1]) / 2 * np.diff(x)).sum())
 
 
+def smooth(y: np.ndarray, f: float = 0.05) -> np.ndarray:
+    """Upstream metrics.smooth: box filter of fraction f (odd length), the ends padded with the end values."""
+    nf = round(len(y) * f * 2) // 2 + 1
+    p = np.ones(nf // 2)
+    yp = np.concatenate((p * y[0], y, p * y[-1]), 0)
+    return np.convolve(yp, np.ones(nf) / nf, mode="valid")
+
+
+def precision_recall(tp50: np.ndarray, conf: np.ndarray, pc: np.ndarray, gc: np.ndarray):
+    """Upstream ap_per_class's (mp, mr): tp50 (n,) bool at IoU 0.5, conf / pc (n,) sorted by confidence descending,
+    gc the ground-truth classes.  A class without predictions has precision and recall 0."""
+    classes = np.unique(gc)
+    if len(classes) == 0:
+        return 0.0, 0.0
+    px = np.linspace(0, 1, 1000)
+    p_curve = np.zeros((len(classes), 1000))
+    r_curve = np.zeros((len(classes), 1000))
+    for ci, c in enumerate(classes):
+        sel = pc == c
+        n_gt = int((gc == c).sum())
+        if sel.sum() == 0 or n_gt == 0:
+            continue
+        tpc = tp50[sel].astype(np.float64).cumsum()
+        fpc = (1 - tp50[sel].astype(np.float64)).cumsum()
+        recall = tpc / (n_gt + 1e-16)
+        precision = tpc / (tpc + fpc)
+        r_curve[ci] = np.interp(-px, -conf[sel], recall, left=0)
+        p_curve[ci] = np.interp(-px, -conf[sel], precision, left=1)
+    f1 = 2 * p_curve * r_curve / (p_curve + r_curve + 1e-16)
+    i = int(smooth(f1.mean(0), 0.1).argmax())
+    return float(p_curve[:, i].mean()), float(r_curve[:, i].mean())
+
+
 def evaluate(preds: List[np.ndarray], gts: List[np.ndarray]) -> Dict[str, float]:
-    """preds/gts: per-image (n,6) arrays [x1,y1,x2,y2,conf,cls] (gt conf ignored). Returns map50, map75, map."""
+    """preds/gts: per-image (n,6) arrays [x1,y1,x2,y2,conf,cls] (gt conf ignored). Returns map50, map75, map, and
+    precision / recall (precision_recall)."""
     tps, confs, pcls, gcls = [], [], [], []
     for p, g in zip(preds, gts):
         p = np.asarray(p, np.float64).reshape(-1, 6)
@@ -76,6 +112,7 @@ def evaluate(preds: List[np.ndarray], gts: List[np.ndarray]) -> Dict[str, float]
     gc = np.concatenate(gcls) if gcls else np.zeros(0)
     order = np.argsort(-conf, kind="stable")
     tp, pc = tp[order], pc[order]
+    mp, mr = precision_recall(tp[:, 0], conf[order], pc, gc)
     classes = np.unique(gc)
     ap = np.zeros((len(classes), len(IOUV)))
     for ci, c in enumerate(classes):
@@ -90,5 +127,6 @@ def evaluate(preds: List[np.ndarray], gts: List[np.ndarray]) -> Dict[str, float]
         for k in range(len(IOUV)):
             ap[ci, k] = compute_ap(recall[:, k], precision[:, k])
     if len(classes) == 0:
-        return {"map50": 0.0, "map75": 0.0, "map": 0.0}
-    return {"map50": float(ap[:, 0].mean()), "map75": float(ap[:, 5].mean()), "map": float(ap.mean())}
+        return {"map50": 0.0, "map75": 0.0, "map": 0.0, "precision": 0.0, "recall": 0.0}
+    return {"map50": float(ap[:, 0].mean()), "map75": float(ap[:, 5].mean()), "map": float(ap.mean()),
+            "precision": mp, "recall": mr}

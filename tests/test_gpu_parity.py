@@ -681,21 +681,18 @@ def test_blob_validation_reload_and_desc():
     checked against the blob."""
     import struct
     from yolomi.lib import Runtime, YMError
-    from yolomi.plan import pack_model
+    from yolomi.plan import field_offset, pack_model, unpack_blob
     bn = pack_model("n", "detect", synth_weights("n", "detect", 0), "f16")
     bs = pack_model("s", "detect", synth_weights("s", "detect", 0), "f16")
     for kw in (dict(scale="s"), dict(task="segment"), dict(dtype="f32")):
         with pytest.raises(YMError, match="EBLOB"):
             Runtime(0, bn, **kw)
-    h = struct.unpack("<32i", bn[:128])
-    nbuf, nop = h[11], h[12]
-    for field_, val in ((6, nbuf + 7), (19, 0x7FFFFFF0)):  # src buffer id / weight offset of the first conv record
+    h, _, ops, _, _ = unpack_blob(bn)
+    conv = next(i for i, r in enumerate(ops) if r.kind == 2)
+    # src buffer id / weight offset of the first conv record
+    for field_, val in (("src0", h.nbuf + 7), ("w_off", 0x7FFFFFF0)):
         bad = bytearray(bn)
-        for i in range(nop):
-            o = 128 + 32 * nbuf + 128 * i
-            if struct.unpack_from("<i", bad, o)[0] == 2:
-                struct.pack_into("<i", bad, o + 4 * field_, val)
-                break
+        struct.pack_into("<i", bad, field_offset(h, field_, conv), val)
         with pytest.raises(YMError, match="EBLOB"):
             Runtime(0, bytes(bad))
     x = make_input("uniform", (7201, 7202), 640).to(DEV)

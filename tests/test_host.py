@@ -3,7 +3,6 @@
 import json
 import os
 import re
-import struct
 
 import numpy as np
 import pytest
@@ -12,7 +11,7 @@ import torch
 from tests.matching import MatchReport, match_image
 from yolomi.arch import GraphBuilder, param_specs
 from yolomi.metrics import evaluate
-from yolomi.plan import MAGIC, fuse_conv_bn, fuse_default, pack_graph, pack_model, x3_weight_exp
+from yolomi.plan import MAGIC, fuse_conv_bn, fuse_default, pack_graph, pack_model, unpack_blob, x3_weight_exp
 from yolomi.synth import splitmix64, synth_weights, uniform
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -57,17 +56,17 @@ def test_fused_weights_match_oracle_to_one_ulp():
 def test_blob_layout(scale, task, dtype):
     sd = synth_weights(scale, task, 0)
     blob = pack_model(scale, task, sd, dtype)
-    h = struct.unpack("<32i", blob[:128])
+    h, bufs, ops, names, woff = unpack_blob(blob)
     g = GraphBuilder(scale, task, fuse=fuse_default(dtype))
     assert h[0] == MAGIC and h[1] == 1 and h[2] == (0 if dtype == "f16" else 1)
     assert h[3] == (1 if task == "segment" else 0) and h[4] == 80 and h[5] == g.nm and h[6] == 16
     assert h[8:11] == (8, 16, 32) and h[11] == len(g.buffers) and h[12] == len(g.ops)
+    assert (len(bufs), len(ops), len(names)) == (h[11], h[12], h[12])
     meta = 128 + 32 * h[11] + 128 * h[12] + 48 * h[12]
     wb = h[13] | (h[14] << 32)
-    assert len(blob) == (meta + 255) // 256 * 256 + wb
+    assert woff == (meta + 255) // 256 * 256 and len(blob) == woff + wb
     # every conv record: Cin multiple of 8, K padded to the 64-deep kernel step, offsets inside the weight region
-    for i in range(h[12]):
-        r = struct.unpack("<32i", blob[128 + 32 * h[11] + 128 * i: 128 + 32 * h[11] + 128 * (i + 1)])
+    for r in ops:
         if r[0] == 2:
             assert r[3] % 8 == 0 and r[21] % 64 == 0 and r[21] >= r[1] * r[1] * r[3]
             assert 0 <= r[19] < wb and 0 <= r[20] < wb
@@ -101,14 +100,12 @@ def test_x3_blob_packs_pair_chunk_weights():
     sd = synth_weights("n", "detect", 0)
     b32 = pack_graph(GraphBuilder("n", "detect", fuse="merge"), sd, "f32")
     bx3 = pack_graph(GraphBuilder("n", "detect", fuse="merge"), sd, "x3")
-    h = struct.unpack("<32i", bx3[:128])
+    h, _, opsx, _, base = unpack_blob(bx3)
+    h32, _, ops32, _, base32 = unpack_blob(b32)
     assert h[2] == 4
-    nb, nop = h[11], h[12]
-    base = (128 + 32 * nb + 176 * nop + 255) // 256 * 256
-    rec = lambda b, i: struct.unpack("<32i", b[128 + 32 * nb + 128 * i: 128 + 32 * nb + 128 * (i + 1)])  # noqa: E731
+    assert (h32[11], h32[12], base32) == (h[11], h[12], base)
     worst, nconv = 0.0, 0
-    for i in range(nop):
-        r32, rx = rec(b32, i), rec(bx3, i)
+    for r32, rx in zip(ops32, opsx):
         if r32[0] != 2:
             continue
         N, Kpad, K = r32[4], r32[21], r32[1] ** 2 * r32[3]
@@ -143,12 +140,9 @@ def test_x3_fused_pairs_pack_w2(scale):
     assert pairs and any(op.args["pair"]["k"] == 3 for op in pairs) and any(op.args["pair"]["k"] == 1 for op in pairs)
     assert any(op.name == "model.1+cv1" for op in pairs)
     blob = pack_model(scale, "detect", sd, "x3")
-    h = struct.unpack("<32i", blob[:128])
-    nb, nop = h[11], h[12]
-    assert nop == len(g.ops)
-    base = (128 + 32 * nb + 176 * nop + 255) // 256 * 256
-    for i, op in enumerate(g.ops):
-        r = struct.unpack("<32i", blob[128 + 32 * nb + 128 * i: 128 + 32 * nb + 128 * (i + 1)])
+    h, _, recs, _, base = unpack_blob(blob)
+    assert h[12] == len(g.ops) == len(recs)
+    for r, op in zip(recs, g.ops):
         assert bool(r[30]) == bool(op.args.get("pair")), op.name
         if not r[30]:
             continue
@@ -183,11 +177,9 @@ def test_x3_fused_depthwise_pack(scale, monkeypatch):
         assert op.args["src0"].buf.name == d.args["src"].buf.name and op.args["c1"] == d.args["C"]
         assert op.args["k"] == 1 and not op.args.get("pair")
     blob = pack_model(scale, "detect", sd, "x3")
-    h = struct.unpack("<32i", blob[:128])
-    nb, nop = h[11], h[12]
-    base = (128 + 32 * nb + 176 * nop + 255) // 256 * 256
-    for i, op in enumerate(g.ops):
-        r = struct.unpack("<32i", blob[128 + 32 * nb + 128 * i: 128 + 32 * nb + 128 * (i + 1)])
+    _, _, recs, _, base = unpack_blob(blob)
+    assert len(recs) == len(g.ops)
+    for r, op in zip(recs, g.ops):
         assert (r[24] > 0) == bool(op.args.get("dw")), op.name
         if r[24] > 0:
             C = op.args["c1"]
@@ -389,7 +381,7 @@ def test_checkpoint_architecture_is_inferred_and_mismatches_rejected():
     with pytest.raises(ValueError, match="shape"):
         pack_graph(GraphBuilder("n", "detect"), sd20, "f16")
     blob = pack_model("s", "detect", sd_s, "f16")
-    assert struct.unpack("<32i", blob[:128])[19] == ord("s")  # ym_model_desc.scale is checked against this
+    assert unpack_blob(blob)[0][19] == ord("s")  # ym_model_desc.scale is checked against this
 
 
 def test_resource_monitor_contract():

@@ -3,14 +3,13 @@ the CPU restatement (tests/pose_oracle.py) against its golden."""
 import hashlib
 import json
 import os
-import struct
 
 import numpy as np
 import pytest
 import torch
 
 from yolomi.arch import GraphBuilder, infer_arch, infer_kpt_shape
-from yolomi.plan import check_state_dict, fuse_default, pack_graph, pack_model
+from yolomi.plan import check_state_dict, fuse_default, pack_graph, pack_model, unpack_blob
 from yolomi.synth import synth_weights
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -83,11 +82,7 @@ def test_pose_head_layout(fuse):
 
 
 def _records(blob):
-    h = struct.unpack("<32i", blob[:128])
-    ops = [struct.unpack("<32i", blob[128 + 32 * h[11] + 128 * i: 128 + 32 * h[11] + 128 * (i + 1)])
-           for i in range(h[12])]
-    names = [blob[128 + 32 * h[11] + 128 * h[12] + 48 * i:][:48].split(b"\0")[0].decode() for i in range(h[12])]
-    woff = -(-(128 + 32 * h[11] + 176 * h[12]) // 256) * 256
+    h, _, ops, names, woff = unpack_blob(blob)
     return h, dict(zip(names, ops)), woff
 
 
@@ -114,12 +109,25 @@ def test_pose_blob_header_and_zero_padding():
     assert r[4] == 64 and b[:51].all() and not b[51:].any()
 
 
-# sha256 of pack_model(scale, task, synth_weights(scale, task, 0), dtype) on the commit before the pose task
+# sha256 of pack_model(scale, task, synth_weights(scale, task, 0), dtype) on the commit before the pose task (the
+# detect and segment x3 / f16 plans) and on the commit before the blob's slots were named (the others); all twelve are
+# checked by tests/test_plan_format.py
 PARENT_BLOBS = {
     ("n", "detect", "x3"): "a246e70f1b491e5e976cd0579d59153dea0f2f0058840efbb35103b57f4097d2",
     ("n", "detect", "f16"): "9fa916da2e40a79ffb4a8f0f4fccbec5062d9afba929d638d6cae8842423d7f2",
     ("s", "segment", "x3"): "d36a6654fbb913376f4b9de5a3b59046f37901d7b7d07027ab356d5703e2f59d",
     ("s", "segment", "f16"): "0b5102be191732a75f37af8939dc2ceff534be5904ba1dd616c19d16aec4bb0e",
+    ("n", "detect", "f32"): "6440e6b27fac17bad14d138d662943d557ca07fbe7c1650dcf9ea91807ceb99e",
+    ("s", "segment", "f32"): "c516009640fa27d84ba8548d15ad4496c5051e81db9ab2f48a73c68ca0f03fc4",
+    ("n", "pose", "f16"): "564624ae663f3a6564858fc2f544aa94c7457f2d4c4ad4611249561d7358a6b4",
+    ("n", "pose", "f32"): "5b9c9ca7ed1f443da8bf54a7dcd7a548e7344956226ef47a82c8a24651793be1",
+    ("n", "pose", "x3"): "a2c1c2126e1505e4454e8cfadfeb823145928c689165f8bbb1ade5f1b25f62dc",
+}
+# one-byte plans: (fixture under tests/golden whose qparams and weights seed the plan is packed with, dtype) -> sha256
+PARENT_QBLOBS = {
+    ("det_n_i8_qnnpack", "i8"): "8815f7639bf8bb454c3fd65d4fa0dccfd5e8aa9878533b4b0c1d12fbdb9fb59b",
+    ("det_n_i8_fbgemm_320", "i8"): "33d1df4f7e34ce3b14478d23ddd521b1ed47a8911871c9a238347338e9bfe702",
+    ("det_n_f8", "f8"): "37679b55a4f276fa2ac87e6a94f80857939145b27d2115f3d9baeca0535cca3b",
 }
 
 

@@ -3,6 +3,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/yolomi.h"
+#include "ym_plan.h"  // the plan dtypes (YM_DT_*, ym_dt_f32s, ym_dt_q8) and the blob format
+
 typedef _Float16 f16;
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
@@ -10,16 +13,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x8 __attribute__((ext_vector_type(8)));
 
 #define YM_WAVE 64
-
-// Activation storage precision of a plan: f16 (MFMA 32x32x16 f16), f32 (exact-f32 MFMA 32x32x2, parity mode),
-// i8 (PTQ int8: activations stored as q - 128 in int8, weights int8, MFMA 32x32x32 i8 with int32 accumulation), or
-// x3 (fp32 storage, every conv GEMM as three f16 MFMAs on split operands: x = hi + lo with hi = fp16(x),
-// lo = fp16(x - hi); x·w ≈ hi·w_hi + lo·w_hi + hi·w_lo, fp32 accumulation — ~2^-21 relative, the f16 MFMA rate / 3).
-enum { YM_DT_F16 = 0, YM_DT_F32 = 1, YM_DT_I8 = 2, YM_DT_F8 = 3, YM_DT_X3 = 4 };
-// plans whose activations are stored fp32 (the exact-f32 parity plan and the split-f16 plan share every non-GEMM kernel)
-inline bool ym_dt_f32s(int dt) { return dt == YM_DT_F32 || dt == YM_DT_X3; }
-// one-byte quantized plans (int8 affine / fp8 e4m3): same graph, storage and kernels (csrc/ym_quant.h Q8)
-inline bool ym_dt_q8(int dt) { return dt == YM_DT_I8 || dt == YM_DT_F8; }
 
 typedef signed char i8;
 
@@ -286,6 +279,7 @@ struct QRec {
   int pad[4];
   float post[256];       // post[q] = act((q - zc)·s_out) (SiLU in float64, rounded to fp32) or the plain dequant
 };
+static_assert(sizeof(QRec) == kQRecBytes, "the plan validator's QRec size (ym_plan.h)");
 
 // ------------------------------------------------------------------------------------------------------------
 // Kernel argument blocks (plain structs passed by value).

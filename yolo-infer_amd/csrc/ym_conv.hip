@@ -672,7 +672,7 @@ hipError_t launch_id(int id, const ConvArgs& a, int kind, hipStream_t st) {
 
 // Default tile choice when no autotuned choice is given: fill the 256 CUs before making tiles big.
 int choose_cfg(const ConvArgs& a) {
-  const int id = ym_debug_get(9) - 1;  // YM_DBG_CONV_CFG (value + 1): a forced tile configuration (tools/tune)
+  const int id = ym_debug_get(YM_DBG_CONV_CFG) - 1;  // (value + 1): a forced tile configuration (tools/tune)
   if (id >= 0 && id < kNumCfg) return id;
   const long M = a.M, N = a.N;
   const int steps = a.Kpad / KSTEP;

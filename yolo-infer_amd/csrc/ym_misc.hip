@@ -1688,7 +1688,7 @@ hipError_t ym_launch_input_max(const float* x, long n, float* ctl, float* out, h
 // the setter — a launch reads an atomic instead of calling getenv (getenv per launch is not thread-safe
 // against setenv and costs time on every eager forward)
 namespace {
-constexpr int kDbgKeys = 10;  // include/yolomi.h YM_DBG_* keys 1..9
+constexpr int kDbgKeys = YM_DBG_CONV_CFG + 1;  // include/yolomi.h YM_DBG_* keys 1..9
 std::atomic<int>* dbg_slots() {
   static std::atomic<int> v[kDbgKeys] = {};
   static const bool init = [] {
@@ -1697,8 +1697,8 @@ std::atomic<int>* dbg_slots() {
     for (int k = 1; k < kDbgKeys; ++k) {
       if (!names[k]) continue;
       const char* e = getenv(names[k]);
-      // keys 8, 9 hold value + 1 (0: unset — the pair-store default mask, no forced tile configuration)
-      v[k].store(e && *e ? atoi(e) + (k >= 8 ? 1 : 0) : 0);
+      // these two hold value + 1 (0: unset — the pair-store default mask, no forced tile configuration)
+      v[k].store(e && *e ? atoi(e) + (k == YM_DBG_PAIRST || k == YM_DBG_CONV_CFG ? 1 : 0) : 0);
     }
     return true;
   }();
@@ -1726,10 +1726,10 @@ hipError_t ym_launch_dwconv(int dtype, const DwArgs& a, hipStream_t st) {
   static const int env_pxt = [] { const char* e = getenv("YM_DW_PXT"); return e ? atoi(e) : 0; }();
   // YM_DBG_DW_MODE (A/B and tests; read at every launch, i.e. at graph capture): 0 = LDS tiles (default), 1 = row /
   // one-pixel variants, 2 = column strips
-  const int mode = ym_debug_get(2);
+  const int mode = ym_debug_get(YM_DBG_DW_MODE);
   if (mode == 0 && !a.raw) {
     // LDS tile shape (TH x TW pixels x CG chunks; YM_DBG_DW_TILE 0..3 for A/B, read at every launch): 0 = 8 x 16 x 4
-    const int ti = ym_debug_get(3);
+    const int ti = ym_debug_get(YM_DBG_DW_TILE);
     auto go = [&](auto th, auto tw, auto cg) -> hipError_t {
       constexpr int TH = decltype(th)::value, TW = decltype(tw)::value, CG = decltype(cg)::value;
       const long tiles = (long)a.B * ((a.H + TH - 1) / TH) * ((a.W + TW - 1) / TW) * ((a.C / 8 + CG - 1) / CG);
@@ -1840,7 +1840,7 @@ hipError_t launch_attn_x3(const AttnArgs& a, hipStream_t st) {
   const dim3 g(a.B * a.nh * ((a.N + 63) / 64));
   // K fragments of every key tile in flight at once (up to 26 tiles); YM_DBG_ATTN_KB = 1: 8 tiles per round trip
   constexpr int KBALL = NKT <= 26 ? NKT : 16;
-  if (ym_debug_get(7) == 1) hipLaunchKernelGGL((attn_psa_x3<NKT, 8>), g, dim3(256), lds, st, a);
+  if (ym_debug_get(YM_DBG_ATTN_KB) == 1) hipLaunchKernelGGL((attn_psa_x3<NKT, 8>), g, dim3(256), lds, st, a);
   else hipLaunchKernelGGL((attn_psa_x3<NKT, KBALL>), g, dim3(256), lds, st, a);
   return hipGetLastError();
 }
@@ -1891,7 +1891,7 @@ hipError_t ym_launch_decode(const DecodeArgs& a, hipStream_t st) {
 
 hipError_t ym_launch_nms(const NmsArgs& a0, hipStream_t st) {
   NmsArgs a = a0;
-  a.dbg = ym_debug_get(1);  // YM_DBG_NMS (a test switches the blocked path off between eager runs)
+  a.dbg = ym_debug_get(YM_DBG_NMS);  // (a test switches the blocked path off between eager runs)
   hipLaunchKernelGGL(nms_image, dim3(a.B), dim3(NMS_T), 0, st, a);
   return hipGetLastError();
 }

@@ -432,7 +432,7 @@ hipError_t ym_launch_nms_ml(const MlArgs& m0, const NmsArgs& n, hipStream_t st) 
       m.max_nms > m.cap || (long)m.A * 128 >= (1L << 30) || n.nm != 0 || n.max_det > MB_KEEP || n.kstride != m.cap)
     return hipErrorInvalidValue;
   m.div_nc = ym_fdiv(m.nc);
-  const int dbg = ym_debug_get(1);
+  const int dbg = ym_debug_get(YM_DBG_NMS);
   const dim3 ge(((long)m.A * m.nc + ML_EPB - 1) / ML_EPB, m.B);
   hipLaunchKernelGGL(ml_init, dim3(m.B), dim3(NMS_T), 0, st, m);
   for (int level = 0; level < ML_LEVELS; ++level) {

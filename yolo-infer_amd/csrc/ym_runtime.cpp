@@ -20,6 +20,7 @@
 
 #include "../../include/yolomi.h"
 #include "ym_common.h"
+#include "ym_plan.h"
 
 namespace {
 
@@ -71,26 +72,13 @@ int fail(int code, const char* fmt, ...) {
     if (e_ != hipSuccess) return fail(YM_EHIP, "%s: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
   } while (0)
 
-constexpr int32_t kMagic = 0x4C504D59;  // 'YMPL'
-constexpr int kHdr = 32, kBufRec = 8, kOpRec = 32, kNameLen = 48;
 constexpr int kSplitCounters = 16384;  // split-K tiles per conv launch (csrc/ym_conv_dma.hip)
-constexpr int kChainCtl = 4096;
-constexpr float kPresortConf = 0.1f;  // NMS keys presorted over several workgroups below this conf (ym_misc.hip)        // ready counters (+ done, give-up words) of the persistent chain kernel
+constexpr int kChainCtl = 4096;        // ready counters (+ done, give-up words) of the persistent chain kernel
+constexpr float kPresortConf = 0.1f;  // NMS keys presorted over several workgroups below this conf (ym_misc.hip)
 constexpr int kMaxLanes = 4;           // concurrent batch slices in one forward graph (<= GPU_MAX_HW_QUEUES)
 constexpr size_t kMaxGraphs = 16;      // captured forwards cached per context (the oldest is retired first)
 constexpr size_t kMiscBytes = 16384;  // ym_ctx::d_misc
 constexpr int kMlCap = 32768;  // multi-label mode: selected keys per image (max_nms up to this; csrc/ym_nms_ml.hip)
-
-enum OpKind { OP_INPUT = 1, OP_CONV = 2, OP_DW = 3, OP_SPPF = 4, OP_ATTN = 5, OP_DECODE = 6, OP_NMS = 7, OP_REQ = 8 };
-
-struct BufDesc {
-  int C, f, f32;
-};
-
-struct Op {
-  int32_t r[kOpRec];
-  char name[kNameLen];
-};
 
 struct GraphKey {
   int B, H, W;
@@ -296,7 +284,7 @@ struct ym_ctx {
   int buf_H(int b) const { return bufs[b].f == 0 ? 1 : cH / bufs[b].f; }
   int buf_Wd(int b) const { return bufs[b].f == 0 ? A : cW / bufs[b].f; }
   int elem(int b) const { return (bufs[b].f32 || ym_dt_f32s(dtype)) ? 4 : (ym_dt_q8(dtype) ? 1 : 2); }
-  template <typename T> const T* wptr(int32_t off) const {
+  template <typename T> const T* wptr(int32_t off) const {  // a record's *_off slot: unsigned bytes into the weights
     return reinterpret_cast<const T*>(d_weights + (size_t)(uint32_t)off);
   }
   float* raw_of(const Op& op) const { return calib_raw ? calib_raw[&op - ops.data()] : nullptr; }
@@ -312,8 +300,6 @@ struct ym_ctx {
 namespace {
 
 size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-constexpr int kTaskPose = 2;  // blob header task codes: 0 detect, 1 segment, 2 pose
-const char* task_name(int t) { return t == 0 ? "detect" : t == 1 ? "segment" : t == kTaskPose ? "pose" : "unknown"; }
 
 int ensure_workspace(ym_ctx* c, int B, int H, int W) {
   if (c->d_arena && B <= c->cB && H == c->cH && W == c->cW && (!c->ml_want || c->ml_have)) return YM_OK;
@@ -381,120 +367,122 @@ int ensure_workspace(ym_ctx* c, int B, int H, int W) {
 
 // Kernel arguments of a conv op for batch B at the current workspace shape.
 int conv_args(ym_ctx* c, const Op& op, int B, const float* d_in, float in_eps, ConvArgs& a, int& out_f32) {
-      const int32_t* r = op.r;
-      a = ConvArgs{};
-      a.wsc = a.wsc2 = 1.0f;
-      const int pst = ym_debug_get(YM_DBG_PAIRST);  // (value + 1; 0: the default family mask 21)
-      a.pst = pst ? pst - 1 : 21;
-      const int k = r[1], s = r[2], cin = r[3], cout = r[4];
-      const int b0 = r[6], b1 = r[10], bd = r[13], br = r[17];
-      const int up0 = r[9];
-      a.src0 = c->bptr(b0); a.s0_ctot = c->bufs[b0].C; a.s0_coff = r[7]; a.C0 = r[8];
-      if (b0 == c->input_buf) {  // stem: NCHW fp32 source, LoadTensor /255 decided on device from ctl[0]
-        a.src0 = nullptr;
-        a.nchw = d_in;
-        a.ctl = reinterpret_cast<const float*>(c->d_arena + c->off_ctl);
-        a.eps = in_eps;
-        a.wstem = reinterpret_cast<const float*>(c->d_weights + c->off_wstem);
-      }
-      a.s0_W = c->buf_Wd(b0); a.s0_P = c->buf_P(b0); a.up0 = up0;
-      a.Hin = c->buf_H(b0) * (up0 ? 2 : 1);
-      a.Win = c->buf_Wd(b0) * (up0 ? 2 : 1);
-      if (b1 >= 0) {
-        a.src1 = c->bptr(b1); a.s1_ctot = c->bufs[b1].C; a.s1_coff = r[11]; a.C1 = r[12]; a.s1_P = c->buf_P(b1);
-        if (c->buf_H(b1) != a.Hin || c->buf_Wd(b1) != a.Win)
-          return fail(YM_EBLOB, "op %s: concat sources disagree in shape", op.name);
-      }
-      a.k = k; a.s = s; a.pad = k / 2;
-      a.Ho = (a.Hin + 2 * a.pad - k) / s + 1;
-      a.Wo = (a.Win + 2 * a.pad - k) / s + 1;
-      if (cin % 8 || (a.C0 + a.C1) != cin) return fail(YM_EBLOB, "op %s: cin %d not a multiple of 8", op.name, cin);
-      a.Cin8 = cin / 8;
-      if (ym_dt_q8(c->dtype)) {  // int8 / fp8 plans: K chunks of 16 channels (the stem keeps its 8-padded taps)
-        if (b0 != c->input_buf) {
-          if (cin % 16) return fail(YM_EBLOB, "op %s: int8 cin %d not a multiple of 16", op.name, cin);
-          a.Cin8 = cin / 16;
-        }
-        a.q = c->wptr<QRec>(r[22]);
-        a.sasw = c->wptr<float>(r[23]);
-        a.biasi = c->wptr<int>(r[24]);
-        const size_t oi = (size_t)(&op - c->ops.data());
-        if (oi < c->off_wtap.size() && c->off_wtap[oi])
-          a.wtap = reinterpret_cast<const int*>(c->d_weights + c->off_wtap0 + (c->off_wtap[oi] - 1));
-      }
-      if (c->dtype == YM_DT_X3 && b0 != c->input_buf) {  // pair layout: fp16 storage chunks per tap double
-        a.x3 = 1;
-        a.Cin8 = 2 * (cin / 8);
-        // the packed weights are W·2^s (and W2·2^s2): yolomi/plan.py, record slots 22 / 23 (int8 plans only otherwise)
-        if (r[22] < -64 || r[22] > 64 || r[23] < -64 || r[23] > 64)
-          return fail(YM_EBLOB, "op %s: bad x3 weight scale exponents %d / %d", op.name, r[22], r[23]);
-        a.wsc = ldexpf(1.0f, -r[22]);
-        a.wsc2 = ldexpf(1.0f, -r[23]);
-      }
-      a.Kc = k * k * a.Cin8;
-      a.Kpad = r[21];
-      a.N = cout;
-      a.w = c->d_weights + (size_t)(uint32_t)r[19];
-      a.bias = reinterpret_cast<const float*>(c->d_weights + (size_t)(uint32_t)r[20]);
-      a.act = r[5];
-      if (r[30]) {  // fused pair (yolomi/arch.py fuse_pairs): a following 1x1 conv, output in dst/res
-        if (c->dtype != YM_DT_F16 && c->dtype != YM_DT_X3)
-          return fail(YM_EBLOB, "op %s: fused conv pairs are f16 / x3 only", op.name);
-        a.w2 = c->d_weights + (size_t)(uint32_t)r[25];
-        a.bias2 = reinterpret_cast<const float*>(c->d_weights + (size_t)(uint32_t)r[26]);
-        a.N2 = r[27]; a.act2 = r[28]; a.Kpad2 = r[29]; a.k2 = r[30];
-        if ((a.k2 != 1 && a.k2 != 3) || a.N2 <= 0 || a.Kpad2 < a.k2 * a.k2 * cout * (a.x3 ? 2 : 1) || r[31] < 0 || r[31] >= (int)c->bufs.size() || cout % 8 ||
-            c->buf_H(r[31]) != a.Ho || c->buf_Wd(r[31]) != a.Wo || c->bufs[r[31]].C != cout || c->bufs[r[31]].f32)
-          return fail(YM_EBLOB, "op %s: bad fused-pair geometry", op.name);
-        if (ym_conv_num_cfgs_dt(c->dtype) > 255) return fail(YM_EBLOB, "split cfg encoding needs < 256 conv configs");
-      }
-      if (r[24] > 0 && !ym_dt_q8(c->dtype)) {  // fused depthwise (yolomi/arch.py fuse_dw): 1 + offset of [9][C] ‖ [C]
-        if ((c->dtype != YM_DT_F16 && c->dtype != YM_DT_X3) || k != 1 || s != 1 || b1 >= 0 || up0 || r[30])
-          return fail(YM_EBLOB, "op %s: a fused depthwise needs a single-source 1x1 conv of an f16 / x3 plan", op.name);
-        a.dw_w = reinterpret_cast<const float*>(c->d_weights + (size_t)(uint32_t)(r[24] - 1));
-        a.dw_b = a.dw_w + 9 * (size_t)cin;
-        a.dw_act = 1;
-      }
-      a.shuffle = r[16];
-      a.npr = a.shuffle ? cout / 4 : cout;
-      a.dst = c->bptr(bd); a.d_ctot = c->bufs[bd].C; a.d_coff = r[14]; a.d_P = c->buf_P(bd);
-      const int lvl = r[15];
-      if (lvl >= 0) {
-        a.d_pixoff = c->lvl_off[lvl];
-        a.d_W = a.Wo;
-        if (a.Wo != c->lvl_W[lvl]) return fail(YM_EBLOB, "op %s: head level width mismatch", op.name);
-      } else {
-        a.d_pixoff = 0;
-        a.d_W = c->buf_Wd(bd);
-        const int expect = a.shuffle ? 2 : 1;
-        if (c->buf_H(bd) != expect * a.Ho || c->buf_Wd(bd) != expect * a.Wo)
-          return fail(YM_EBLOB, "op %s: output %dx%d does not match dst buffer %dx%d", op.name, a.Ho, a.Wo,
-                      c->buf_H(bd), c->buf_Wd(bd));
-      }
-      if (br >= 0) { a.res = c->bptr(br); a.r_ctot = c->bufs[br].C; a.r_coff = r[18]; a.r_P = c->buf_P(br); }
-      a.M = B * a.Ho * a.Wo;
-      a.fd_hw = ym_fdiv(a.Ho * a.Wo);
-      a.fd_w = ym_fdiv(a.Wo);
-      out_f32 = c->bufs[bd].f32 && c->dtype != YM_DT_F32;  // (x3: fp32 head rows, pair-layout activations)
-      a.raw = c->raw_of(op);
-      // operand extents in storage elements (the LDS-DMA buffer descriptors): fp16 halves of the x3 pairs
-      const long xs = a.x3 ? 2 : 1;
-      a.s0_elems = (b0 == c->input_buf) ? 0 : xs * c->cB * c->buf_P(b0) * c->bufs[b0].C;
-      a.s1_elems = b1 >= 0 ? xs * c->cB * c->buf_P(b1) * c->bufs[b1].C : 0;
-      a.slab = reinterpret_cast<float*>(c->d_arena + c->off_slab + (size_t)c->lane * c->slab_bytes);
-      a.slab_cap = (long)c->slab_bytes;
-      a.cnt = reinterpret_cast<int*>(c->d_arena + c->off_cnt) + (size_t)c->lane * kSplitCounters;
-      a.cnt_cap = kSplitCounters;
-      static const int pf_max = [] { const char* e = getenv("YM_DMA_PF"); return e ? atoi(e) : 0; }();
-      a.pf = a.M <= pf_max;
-      return YM_OK;
+  a = ConvArgs{};
+  a.wsc = a.wsc2 = 1.0f;
+  const int pst = ym_debug_get(YM_DBG_PAIRST);  // (value + 1; 0: the default family mask 21)
+  a.pst = pst ? pst - 1 : 21;
+  const int k = op.k, s = op.s, cin = op.cin, cout = op.n;
+  const int b0 = op.src0, b1 = op.src1, bd = op.dst, br = op.res;
+  const int up0 = op.up0;
+  a.src0 = c->bptr(b0); a.s0_ctot = c->bufs[b0].C; a.s0_coff = op.src0_coff; a.C0 = op.c0;
+  if (b0 == c->input_buf) {  // stem: NCHW fp32 source, LoadTensor /255 decided on device from ctl[0]
+    a.src0 = nullptr;
+    a.nchw = d_in;
+    a.ctl = reinterpret_cast<const float*>(c->d_arena + c->off_ctl);
+    a.eps = in_eps;
+    a.wstem = reinterpret_cast<const float*>(c->d_weights + c->off_wstem);
+  }
+  a.s0_W = c->buf_Wd(b0); a.s0_P = c->buf_P(b0); a.up0 = up0;
+  a.Hin = c->buf_H(b0) * (up0 ? 2 : 1);
+  a.Win = c->buf_Wd(b0) * (up0 ? 2 : 1);
+  if (b1 >= 0) {
+    a.src1 = c->bptr(b1); a.s1_ctot = c->bufs[b1].C; a.s1_coff = op.src1_coff; a.C1 = op.c1; a.s1_P = c->buf_P(b1);
+    if (c->buf_H(b1) != a.Hin || c->buf_Wd(b1) != a.Win)
+      return fail(YM_EBLOB, "op %s: concat sources disagree in shape", op.name);
+  }
+  a.k = k; a.s = s; a.pad = k / 2;
+  a.Ho = (a.Hin + 2 * a.pad - k) / s + 1;
+  a.Wo = (a.Win + 2 * a.pad - k) / s + 1;
+  if (cin % 8 || (a.C0 + a.C1) != cin) return fail(YM_EBLOB, "op %s: cin %d not a multiple of 8", op.name, cin);
+  a.Cin8 = cin / 8;
+  if (ym_dt_q8(c->dtype)) {  // int8 / fp8 plans: K chunks of 16 channels (the stem keeps its 8-padded taps)
+    if (b0 != c->input_buf) {
+      if (cin % 16) return fail(YM_EBLOB, "op %s: int8 cin %d not a multiple of 16", op.name, cin);
+      a.Cin8 = cin / 16;
+    }
+    a.q = c->wptr<QRec>(op.q_off);
+    a.sasw = c->wptr<float>(op.sasw_off);
+    a.biasi = c->wptr<int>(op.biasi_off);
+    const size_t oi = (size_t)(&op - c->ops.data());
+    if (oi < c->off_wtap.size() && c->off_wtap[oi])
+      a.wtap = reinterpret_cast<const int*>(c->d_weights + c->off_wtap0 + (c->off_wtap[oi] - 1));
+  }
+  if (c->dtype == YM_DT_X3 && b0 != c->input_buf) {  // pair layout: fp16 storage chunks per tap double
+    a.x3 = 1;
+    a.Cin8 = 2 * (cin / 8);
+    // the packed weights are W·2^s (and W2·2^s2): yolomi/plan.py
+    const int ws = op.x3_wexp(), ws2 = op.x3_wexp2();
+    if (ws < -64 || ws > 64 || ws2 < -64 || ws2 > 64)
+      return fail(YM_EBLOB, "op %s: bad x3 weight scale exponents %d / %d", op.name, ws, ws2);
+    a.wsc = ldexpf(1.0f, -ws);
+    a.wsc2 = ldexpf(1.0f, -ws2);
+  }
+  a.Kc = k * k * a.Cin8;
+  a.Kpad = op.kpad;
+  a.N = cout;
+  a.w = c->wptr<char>(op.w_off);
+  a.bias = c->wptr<float>(op.b_off);
+  a.act = op.act;
+  if (op.k2) {  // fused pair (yolomi/arch.py fuse_pairs): a following 1x1 conv, output in dst/res
+    if (c->dtype != YM_DT_F16 && c->dtype != YM_DT_X3)
+      return fail(YM_EBLOB, "op %s: fused conv pairs are f16 / x3 only", op.name);
+    a.w2 = c->wptr<char>(op.w2_off);
+    a.bias2 = c->wptr<float>(op.b2_off);
+    a.N2 = op.n2; a.act2 = op.act2; a.Kpad2 = op.kpad2; a.k2 = op.k2;
+    const int mid = op.mid;
+    if ((a.k2 != 1 && a.k2 != 3) || a.N2 <= 0 || a.Kpad2 < a.k2 * a.k2 * cout * (a.x3 ? 2 : 1) || mid < 0 ||
+        mid >= (int)c->bufs.size() || cout % 8 || c->buf_H(mid) != a.Ho || c->buf_Wd(mid) != a.Wo ||
+        c->bufs[mid].C != cout || c->bufs[mid].f32)
+      return fail(YM_EBLOB, "op %s: bad fused-pair geometry", op.name);
+    if (ym_conv_num_cfgs_dt(c->dtype) > 255) return fail(YM_EBLOB, "split cfg encoding needs < 256 conv configs");
+  }
+  if (op.has_fused_dw() && !ym_dt_q8(c->dtype)) {  // fused depthwise (yolomi/arch.py fuse_dw): [9][C] weights ‖ [C] bias
+    if ((c->dtype != YM_DT_F16 && c->dtype != YM_DT_X3) || k != 1 || s != 1 || b1 >= 0 || up0 || op.k2)
+      return fail(YM_EBLOB, "op %s: a fused depthwise needs a single-source 1x1 conv of an f16 / x3 plan", op.name);
+    a.dw_w = c->wptr<float>(op.fused_dw_off());
+    a.dw_b = a.dw_w + 9 * (size_t)cin;
+    a.dw_act = 1;
+  }
+  a.shuffle = op.shuffle;
+  a.npr = a.shuffle ? cout / 4 : cout;
+  a.dst = c->bptr(bd); a.d_ctot = c->bufs[bd].C; a.d_coff = op.dst_coff; a.d_P = c->buf_P(bd);
+  const int lvl = op.level;
+  if (lvl >= 0) {
+    a.d_pixoff = c->lvl_off[lvl];
+    a.d_W = a.Wo;
+    if (a.Wo != c->lvl_W[lvl]) return fail(YM_EBLOB, "op %s: head level width mismatch", op.name);
+  } else {
+    a.d_pixoff = 0;
+    a.d_W = c->buf_Wd(bd);
+    const int expect = a.shuffle ? 2 : 1;
+    if (c->buf_H(bd) != expect * a.Ho || c->buf_Wd(bd) != expect * a.Wo)
+      return fail(YM_EBLOB, "op %s: output %dx%d does not match dst buffer %dx%d", op.name, a.Ho, a.Wo,
+                  c->buf_H(bd), c->buf_Wd(bd));
+  }
+  if (br >= 0) { a.res = c->bptr(br); a.r_ctot = c->bufs[br].C; a.r_coff = op.res_coff; a.r_P = c->buf_P(br); }
+  a.M = B * a.Ho * a.Wo;
+  a.fd_hw = ym_fdiv(a.Ho * a.Wo);
+  a.fd_w = ym_fdiv(a.Wo);
+  out_f32 = c->bufs[bd].f32 && c->dtype != YM_DT_F32;  // (x3: fp32 head rows, pair-layout activations)
+  a.raw = c->raw_of(op);
+  // operand extents in storage elements (the LDS-DMA buffer descriptors): fp16 halves of the x3 pairs
+  const long xs = a.x3 ? 2 : 1;
+  a.s0_elems = (b0 == c->input_buf) ? 0 : xs * c->cB * c->buf_P(b0) * c->bufs[b0].C;
+  a.s1_elems = b1 >= 0 ? xs * c->cB * c->buf_P(b1) * c->bufs[b1].C : 0;
+  a.slab = reinterpret_cast<float*>(c->d_arena + c->off_slab + (size_t)c->lane * c->slab_bytes);
+  a.slab_cap = (long)c->slab_bytes;
+  a.cnt = reinterpret_cast<int*>(c->d_arena + c->off_cnt) + (size_t)c->lane * kSplitCounters;
+  a.cnt_cap = kSplitCounters;
+  static const int pf_max = [] { const char* e = getenv("YM_DMA_PF"); return e ? atoi(e) : 0; }();
+  a.pf = a.M <= pf_max;
+  return YM_OK;
 }
 
-// A fused pair (ConvArgs::w2) run as its two convs: A writes the intermediate buffer (record r[31]), B reads it.
+// A fused pair (ConvArgs::w2) run as its two convs: A writes the intermediate buffer (the record's `mid`), B reads it.
 // The tuner picks this when the two tuned single launches beat every fused variant (op cfg kSplitTag + ...).
 constexpr int kSplitTag = 1 << 20;  // op cfg = kSplitTag + 256 * cfg(A) + cfg(B)
 void split_args(ym_ctx* c, const Op& op, const ConvArgs& a, ConvArgs& A, ConvArgs& Bc) {
-  const int mid = op.r[31];
+  const int mid = op.mid;
   A = a;
   A.w2 = nullptr; A.bias2 = nullptr; A.res = nullptr;
   A.dst = c->bptr(mid); A.d_ctot = c->bufs[mid].C; A.d_coff = 0; A.d_P = c->buf_P(mid); A.d_pixoff = 0;
@@ -525,10 +513,9 @@ hipError_t launch_fused(ym_ctx* c, const Op& op, const ConvArgs& a, int out_f32,
 
 int launch_op(ym_ctx* c, const Op& op, int B, const float* d_in, const ym_infer_args* args, float* d_dets,
               int* d_counts, hipStream_t st) {
-  const int32_t* r = op.r;
   const int dt = c->dtype;
   hipError_t e = hipSuccess;
-  switch (r[0]) {
+  switch (op.kind) {
     case OP_INPUT: {
       PrepArgs a{};
       a.in = d_in;
@@ -554,17 +541,17 @@ int launch_op(ym_ctx* c, const Op& op, int B, const float* d_in, const ym_infer_
     }
     case OP_DW: {
       DwArgs a{};
-      const int bs = r[6], bd = r[13];
-      a.src = c->bptr(bs); a.s_ctot = c->bufs[bs].C; a.s_coff = r[7]; a.s_P = c->buf_P(bs);
-      a.dst = c->bptr(bd); a.d_ctot = c->bufs[bd].C; a.d_coff = r[14]; a.d_P = c->buf_P(bd);
-      a.w = reinterpret_cast<const float*>(c->d_weights + (size_t)(uint32_t)r[19]);
-      a.bias = reinterpret_cast<const float*>(c->d_weights + (size_t)(uint32_t)r[20]);
-      a.C = r[3]; a.act = r[5]; a.H = c->buf_H(bs); a.W = c->buf_Wd(bs); a.B = B;
+      const int bs = op.src0, bd = op.dst;
+      a.src = c->bptr(bs); a.s_ctot = c->bufs[bs].C; a.s_coff = op.src0_coff; a.s_P = c->buf_P(bs);
+      a.dst = c->bptr(bd); a.d_ctot = c->bufs[bd].C; a.d_coff = op.dst_coff; a.d_P = c->buf_P(bd);
+      a.w = c->wptr<float>(op.w_off);
+      a.bias = c->wptr<float>(op.b_off);
+      a.C = op.cin; a.act = op.act; a.H = c->buf_H(bs); a.W = c->buf_Wd(bs); a.B = B;
       if (ym_dt_q8(dt)) {
         a.w = nullptr;
-        a.wq = c->wptr<i8>(r[19]);
-        a.q = c->wptr<QRec>(r[22]);
-        a.sasw = c->wptr<float>(r[23]);
+        a.wq = c->wptr<i8>(op.w_off);
+        a.q = c->wptr<QRec>(op.q_off);
+        a.sasw = c->wptr<float>(op.sasw_off);
       }
       a.raw = c->raw_of(op);
       e = ym_launch_dwconv(dt, a, st);
@@ -572,27 +559,27 @@ int launch_op(ym_ctx* c, const Op& op, int B, const float* d_in, const ym_infer_
     }
     case OP_SPPF: {
       PoolArgs a{};
-      const int bb = r[13];
-      a.buf = c->bptr(bb); a.ctot = c->bufs[bb].C; a.coff = r[7]; a.P = c->buf_P(bb);
-      a.C = r[3]; a.H = c->buf_H(bb); a.W = c->buf_Wd(bb); a.B = B;
+      const int bb = op.sppf_buf();
+      a.buf = c->bptr(bb); a.ctot = c->bufs[bb].C; a.coff = op.sppf_coff(); a.P = c->buf_P(bb);
+      a.C = op.cin; a.H = c->buf_H(bb); a.W = c->buf_Wd(bb); a.B = B;
       e = ym_launch_sppf(dt, a, st);
       break;
     }
     case OP_ATTN: {
       AttnArgs a{};
-      const int bq = r[6], bd = r[13];
-      a.qkv = c->bptr(bq); a.q_ctot = c->bufs[bq].C; a.q_coff = r[7]; a.q_P = c->buf_P(bq);
-      a.dst = c->bptr(bd); a.d_ctot = c->bufs[bd].C; a.d_coff = r[14]; a.d_P = c->buf_P(bd);
-      a.pe_w = reinterpret_cast<const float*>(c->d_weights + (size_t)(uint32_t)r[19]);
-      a.pe_b = reinterpret_cast<const float*>(c->d_weights + (size_t)(uint32_t)r[20]);
-      a.C = r[3]; a.nh = r[4]; a.kd = r[5]; a.hd = r[9];
+      const int bq = op.src0, bd = op.dst;
+      a.qkv = c->bptr(bq); a.q_ctot = c->bufs[bq].C; a.q_coff = op.src0_coff; a.q_P = c->buf_P(bq);
+      a.dst = c->bptr(bd); a.d_ctot = c->bufs[bd].C; a.d_coff = op.dst_coff; a.d_P = c->buf_P(bd);
+      a.pe_w = c->wptr<float>(op.w_off);
+      a.pe_b = c->wptr<float>(op.b_off);
+      a.C = op.cin; a.nh = op.attn_nh(); a.kd = op.attn_kd(); a.hd = op.attn_hd();
       a.H = c->buf_H(bq); a.W = c->buf_Wd(bq); a.N = a.H * a.W; a.B = B;
-      memcpy(&a.scale, &r[21], 4);
+      a.scale = op.attn_scale();
       if (ym_dt_q8(dt)) {
         a.pe_w = nullptr;
-        a.pe_wq = c->wptr<i8>(r[19]);
-        a.q = c->wptr<QRec>(r[22]);
-        a.pe_sasw = c->wptr<float>(r[23]);
+        a.pe_wq = c->wptr<i8>(op.w_off);
+        a.q = c->wptr<QRec>(op.q_off);
+        a.pe_sasw = c->wptr<float>(op.sasw_off);
       }
       a.raw = c->raw_of(op);
       e = ym_launch_attn(dt, a, st);
@@ -601,15 +588,15 @@ int launch_op(ym_ctx* c, const Op& op, int B, const float* d_in, const ym_infer_
     case OP_REQ: {
       if (!ym_dt_q8(dt)) return fail(YM_EBLOB, "op %s: requant in a non-quantized plan", op.name);
       ReqArgs a{};
-      const int bs = r[6], bd = r[13];
-      a.src = static_cast<const i8*>(c->bptr(bs)); a.s_ctot = c->bufs[bs].C; a.s_coff = r[7]; a.s_P = c->buf_P(bs);
-      a.s_W = c->buf_Wd(bs); a.up = r[9];
-      a.dst = static_cast<i8*>(c->bptr(bd)); a.d_ctot = c->bufs[bd].C; a.d_coff = r[14]; a.d_P = c->buf_P(bd);
+      const int bs = op.src0, bd = op.dst;
+      a.src = static_cast<const i8*>(c->bptr(bs)); a.s_ctot = c->bufs[bs].C; a.s_coff = op.src0_coff; a.s_P = c->buf_P(bs);
+      a.s_W = c->buf_Wd(bs); a.up = op.req_up();
+      a.dst = static_cast<i8*>(c->bptr(bd)); a.d_ctot = c->bufs[bd].C; a.d_coff = op.dst_coff; a.d_P = c->buf_P(bd);
       a.d_W = c->buf_Wd(bd);
-      a.C = r[3]; a.H = c->buf_H(bd); a.W = c->buf_Wd(bd); a.B = B;
+      a.C = op.cin; a.H = c->buf_H(bd); a.W = c->buf_Wd(bd); a.B = B;
       if (c->buf_H(bs) * (a.up ? 2 : 1) != a.H || a.s_W * (a.up ? 2 : 1) != a.W)
         return fail(YM_EBLOB, "op %s: requant source/destination shapes disagree", op.name);
-      a.q = c->wptr<QRec>(r[22]);
+      a.q = c->wptr<QRec>(op.q_off);
       e = ym_launch_requant(a, st, dt == YM_DT_F8);
       break;
     }
@@ -704,7 +691,7 @@ int launch_op(ym_ctx* c, const Op& op, int B, const float* d_in, const ym_infer_
       break;
     }
     default:
-      return fail(YM_EBLOB, "unknown op kind %d", r[0]);
+      return fail(YM_EBLOB, "unknown op kind %d", op.kind);
   }
   if (e != hipSuccess) return fail(YM_EHIP, "launch of op %s failed: %s", op.name, hipGetErrorString(e));
   return YM_OK;
@@ -724,7 +711,7 @@ int check_call(ym_ctx* c, const float* d_in, int B, int H, int W, const ym_infer
   if (args->multi_label && c->nc > 1) {  // (nc == 1: the single-label path, as upstream's multi_label &= nc > 1)
     if (c->task != 0)
       return fail(YM_EINVAL, "multi_label: %s plans are not supported (validation mode is for detect plans)",
-                  task_name(c->task));
+                  ym_task_name(c->task));
     if (c->nc > 128) return fail(YM_EINVAL, "multi_label: nc %d > 128 is not supported", c->nc);
     if (args->max_nms > kMlCap) return fail(YM_EINVAL, "multi_label: max_nms %d > %d is not supported", args->max_nms, kMlCap);
     c->ml_want = true;
@@ -785,17 +772,15 @@ static void build_schedule(ym_ctx* c) {
   const int nop = (int)c->ops.size(), nbuf = (int)c->bufs.size();
   const int P_DEC = nbuf, P_OUT = nbuf + 1;  // pseudo buffers: decode scratch, detections
   auto rw = [&](const Op& o, std::vector<int>& rd, std::vector<int>& wr) {
-    const int32_t* r = o.r;
-    rd.clear(); wr.clear();
-    switch (r[0]) {
+    int b[3];
+    rd.assign(b, b + op_reads(o, b));
+    wr.clear();
+    if (op_writes(o) >= 0) wr.push_back(op_writes(o));
+    switch (o.kind) {  // the header's buffers and the pseudo ones
       case OP_INPUT: wr.push_back(c->input_buf); break;
-      case OP_CONV: rd.push_back(r[6]); if (r[10] >= 0) rd.push_back(r[10]); if (r[17] >= 0) rd.push_back(r[17]);
-                    wr.push_back(r[13]); break;
-      case OP_DW: case OP_ATTN: case OP_REQ: rd.push_back(r[6]); wr.push_back(r[13]); break;
-      case OP_SPPF: rd.push_back(r[13]); wr.push_back(r[13]); break;
       case OP_DECODE: rd.push_back(c->anchor_buf); wr.push_back(P_DEC); break;
       case OP_NMS: rd.push_back(P_DEC); rd.push_back(c->anchor_buf); wr.push_back(P_OUT); break;
-      default: rd.push_back(-2); break;  // unknown: serialise behind everything
+      default: break;
     }
   };
   const int S = kMaxLanes;
@@ -825,24 +810,18 @@ static void build_schedule(ym_ctx* c) {
   const bool crit = sched && !strcmp(sched, "crit");
   std::vector<double> fin(nop, 0.0), sfin(S, 0.0);
   auto est_us = [&](const Op& o) {
-    const int32_t* r = o.r;
     double macs = 0;
-    if (r[0] == OP_CONV && r[13] >= 0 && r[13] < nbuf) {
-      const int f = c->bufs[r[13]].f > 0 ? c->bufs[r[13]].f : 8;  // output stride (head rows: level stride unknown)
+    if (o.kind == OP_CONV) {
+      const int f = c->bufs[o.dst].f > 0 ? c->bufs[o.dst].f : 8;  // output stride (head rows: level stride unknown)
       const double px = 8.0 * (640.0 / f) * (640.0 / f);
-      macs = px * r[1] * r[1] * (double)r[3] * r[4] * (r[30] ? 2 : 1);
+      macs = px * o.k * o.k * (double)o.cin * o.n * (o.k2 ? 2 : 1);
     }
     return 6.0 + macs / 40e6;
   };
   for (int i = 0; i < nop; ++i) {
     rw(c->ops[i], rd, wr);
-    std::vector<int> deps;
-    bool all = false;
-    for (int b : rd) {
-      if (b == -2) all = true;
-      else if (b >= 0 && b < nbuf + 2) deps.insert(deps.end(), writers[b].begin(), writers[b].end());
-    }
-    if (all) for (int j = 0; j < i; ++j) deps.push_back(j);
+    std::vector<int> deps;  // (every buffer id of a loaded plan is in range: ym_plan_parse)
+    for (int b : rd) deps.insert(deps.end(), writers[b].begin(), writers[b].end());
     int jmax = -1;
     for (int j : deps) jmax = j > jmax ? j : jmax;
     int s = -1;
@@ -873,7 +852,7 @@ static void build_schedule(ym_ctx* c) {
     tail[s] = i;
     known[s][s] = i;
     snap[i] = known[s];
-    for (int b : wr) if (b >= 0 && b < nbuf + 2) writers[b].push_back(i);
+    for (int b : wr) writers[b].push_back(i);
   }
   c->nbr = used;
 }
@@ -885,123 +864,17 @@ static float e4m3_value(uint8_t b) {
   return (b & 0x80) ? -v : v;
 }
 
-// Structural check of a parsed plan before it is committed to a context: buffer ids and channel views
-// [coff, coff + C) of every op record inside their buffers, every weight / bias / quantisation record inside the
-// weight section.  The kernels index device memory with these values, so a malformed blob must fail here
-// (YM_EBLOB), never inside a launch.
-static int validate_plan(const std::vector<BufDesc>& bufs, const std::vector<Op>& ops, int dtype, size_t wbytes,
-                         int input_buf) {
-  const int nbuf = (int)bufs.size();
-  for (int i = 0; i < nbuf; ++i)
-    if (bufs[i].C <= 0 || bufs[i].C > (1 << 16) || bufs[i].f < 0 || bufs[i].f > 64)
-      return fail(YM_EBLOB, "buffer %d: bad geometry (C %d, f %d)", i, bufs[i].C, bufs[i].f);
-  // (x3 plans: Kpad counts the fp16 [hi | lo] storage K of the pair-chunk weight rows; their fp32 stem rows are
-  // checked again where they are read)
-  const size_t esz = dtype == YM_DT_F32 ? 4 : ((dtype == YM_DT_F16 || dtype == YM_DT_X3) ? 2 : 1);
-  for (const Op& o : ops) {
-    const int32_t* r = o.r;
-    auto buf_ok = [&](int b, bool opt) { return (opt && b == -1) || (b >= 0 && b < nbuf); };
-    auto w_ok = [&](int32_t off, size_t n) { return (size_t)(uint32_t)off + n <= wbytes; };
-    // a channel view [coff, coff + C) of buffer b (b == -1: absent, when optional)
-    auto view_ok = [&](int b, int coff, int C, bool opt) {
-      if (opt && b == -1) return true;
-      return buf_ok(b, false) && coff >= 0 && C > 0 && (long)coff + C <= bufs[b].C;
-    };
-    bool ok = true;
-    const size_t qrec = sizeof(QRec);
-    switch (r[0]) {
-      case OP_INPUT: case OP_DECODE: case OP_NMS: break;  // no operands besides the header's input/anchor buffers
-      case OP_CONV: {
-        const int N = r[4], Kpad = r[21], fused = r[30];
-        const int Nout = fused ? r[27] : N;  // the channels the launch writes (a fused pair: its second conv's)
-        const int Cd = r[16] ? Nout / 4 : Nout;  // pixel shuffle (ConvTranspose2d 2x2): N/4 channels per pixel
-        const int C1 = r[10] >= 0 ? r[12] : 0;
-        ok = N > 0 && Kpad > 0 && Kpad <= (1 << 16) && r[3] == r[8] + C1 && view_ok(r[6], r[7], r[8], false) &&
-             view_ok(r[10], r[11], r[12], true) && view_ok(r[13], r[14], Cd, false) &&
-             view_ok(r[17], r[18], Nout, true) && (r[6] != input_buf || (r[7] == 0 && r[10] == -1)) &&
-             w_ok(r[19], (size_t)N * Kpad * esz) && w_ok(r[20], (size_t)N * 4);
-        if (ok && ym_dt_q8(dtype)) ok = w_ok(r[22], qrec) && w_ok(r[23], (size_t)N * 4) && w_ok(r[24], (size_t)N * 4);
-        else if (ok && r[24] > 0) ok = w_ok(r[24] - 1, (size_t)10 * r[3] * 4);  // fused depthwise weights + bias
-        if (ok && fused) {
-          const int N2 = r[27], K2 = r[29];
-          ok = N2 > 0 && K2 > 0 && K2 <= (1 << 16) && buf_ok(r[31], false) && w_ok(r[25], (size_t)N2 * K2 * 2) &&
-               w_ok(r[26], (size_t)N2 * 4);
-        }
-        break;
-      }
-      case OP_DW: case OP_ATTN: {
-        const int C = r[3];
-        // attention: the (q, k, v) channels of every head after q_coff; the output slice is C wide
-        const int Cin = r[0] == OP_ATTN ? r[4] * (2 * r[5] + r[9]) : C;
-        ok = C > 0 && view_ok(r[6], r[7], Cin, false) && view_ok(r[13], r[14], C, false) &&
-             (r[0] == OP_DW || (r[4] > 0 && r[4] * r[9] == C)) &&
-             w_ok(r[19], (size_t)9 * C * (ym_dt_q8(dtype) ? 1 : 4)) && w_ok(r[20], (size_t)C * 4);
-        if (ok && ym_dt_q8(dtype)) ok = w_ok(r[22], qrec) && w_ok(r[23], (size_t)C * 4);
-        break;
-      }
-      case OP_SPPF: ok = r[3] > 0 && view_ok(r[13], r[7], 4 * r[3], false); break;  // y0 and the 3 pooled slices
-      case OP_REQ:
-        ok = r[3] > 0 && view_ok(r[6], r[7], r[3], false) && view_ok(r[13], r[14], r[3], false) && w_ok(r[22], qrec);
-        break;
-      default: return fail(YM_EBLOB, "op %s: unknown op kind %d", o.name, r[0]);
-    }
-    if (!ok) return fail(YM_EBLOB, "op %s: buffer id, channel view or weight range out of bounds", o.name);
-  }
-  return YM_OK;
-}
-
 int ym_load_weights(ym_ctx* c, const void* blob, size_t bytes) {
   if (!c || !blob) return fail(YM_EINVAL, "null argument");
   HIPCK(hipSetDevice(c->device));
-  const int32_t* h = static_cast<const int32_t*>(blob);
-  if (bytes < kHdr * 4 || h[0] != kMagic || h[1] != 1) return fail(YM_EBLOB, "bad blob magic/version");
-  // everything is parsed into locals and validated; the context changes only once the whole blob checks out
-  const int nbuf = h[11], nop = h[12];
-  if (nbuf < 1 || nbuf > 4096 || nop < 1 || nop > 4096) return fail(YM_EBLOB, "bad buffer/op counts (%d, %d)", nbuf, nop);
-  const size_t wbytes = (size_t)(uint32_t)h[13] | ((size_t)(uint32_t)h[14] << 32);
-  const size_t need = (size_t)kHdr * 4 + (size_t)nbuf * kBufRec * 4 + (size_t)nop * (kOpRec * 4 + kNameLen);
-  const size_t woff = align_up(need, 256);
-  if (wbytes > bytes || bytes < woff + wbytes) return fail(YM_EBLOB, "blob truncated (%zu < %zu)", bytes, woff + wbytes);
-  const int dtype = h[2];
-  if (dtype != YM_DT_F16 && !ym_dt_f32s(dtype) && !ym_dt_q8(dtype)) return fail(YM_EBLOB, "unknown dtype %d", dtype);
-  const int task = h[3], nc = h[4], nm = h[5], reg_max = h[6], nl = h[7];
-  if (nl < 1 || nl > 4) return fail(YM_EBLOB, "bad level count");
-  if (nc < 1 || nc > 128 || nm < 0 || nm > 64 || reg_max < 1 || reg_max > 64)
-    return fail(YM_EBLOB, "bad head geometry (nc %d, nm %d, reg_max %d)", nc, nm, reg_max);
-  for (int l = 0; l < nl; ++l)
-    if (h[8 + l] < 1 || h[8 + l] > 64) return fail(YM_EBLOB, "bad stride %d", h[8 + l]);
-  const ym_model_desc& want = c->desc;  // what the creator expects (0 = any)
-  if (task < 0 || task > kTaskPose) return fail(YM_EBLOB, "unknown task %d (detect 0, segment 1, pose 2)", task);
-  if (want.task && want.task != task + 1)
-    return fail(YM_EBLOB, "blob task %s, context created for %s", task_name(task), task_name(want.task - 1));
-  if (want.dtype && want.dtype != dtype + 1) return fail(YM_EBLOB, "blob dtype %d, context created for %d", dtype + 1, want.dtype);
-  if (want.scale && h[19] && want.scale != h[19])
-    return fail(YM_EBLOB, "blob scale '%c', context created for '%c'", (char)h[19], (char)want.scale);
-  const int input_buf = h[15], anchor_buf = h[16], proto_buf = h[17];
-  if (input_buf < 0 || input_buf >= nbuf || anchor_buf < 0 || anchor_buf >= nbuf)
-    return fail(YM_EBLOB, "bad input/anchor buffer ids");
-  if (task == 1 && (proto_buf < 0 || proto_buf >= nbuf)) return fail(YM_EBLOB, "segment plan without proto buffer");
-  const int kpt_K = h[20], kpt_ndim = h[21], kpt_off = h[22];
-  if (task == kTaskPose) {  // the keypoint slice [kpt_off, kpt_off + nm) of the anchor row; nm = K * ndim padded to 4
-    const int arow = h[kHdr + anchor_buf * kBufRec];  // the anchor buffer's channels (its record is inside the blob)
-    if (kpt_K < 1 || (kpt_ndim != 2 && kpt_ndim != 3) || nm < kpt_K * kpt_ndim || (nm & 3) || kpt_off < 0 ||
-        (kpt_off & 3) || (arow & 3) || kpt_off + nm > arow || h[18] != kpt_off)
-      return fail(YM_EBLOB, "bad pose head geometry (K %d, ndim %d, nm %d, offset %d, row %d)", kpt_K, kpt_ndim, nm,
-                  kpt_off, arow);
-  }
-  const int32_t* bp = h + kHdr;
-  std::vector<BufDesc> bufs(nbuf);
-  for (int i = 0; i < nbuf; ++i) bufs[i] = BufDesc{bp[i * kBufRec], bp[i * kBufRec + 1], bp[i * kBufRec + 2]};
-  const int32_t* op = bp + (size_t)nbuf * kBufRec;
-  const char* names = reinterpret_cast<const char*>(op + (size_t)nop * kOpRec);
-  std::vector<Op> ops(nop);
-  for (int i = 0; i < nop; ++i) {
-    memcpy(ops[i].r, op + (size_t)i * kOpRec, kOpRec * 4);
-    memcpy(ops[i].name, names + (size_t)i * kNameLen, kNameLen);
-    ops[i].name[kNameLen - 1] = 0;
-  }
-  int rc = validate_plan(bufs, ops, dtype, wbytes, input_buf);
-  if (rc) return rc;
+  // the blob is parsed and validated into `plan`; the context changes only once the whole blob checks out
+  Plan plan;
+  std::string err;
+  if (int rc = ym_plan_parse(blob, bytes, &c->desc, plan, err)) return fail(rc, "%s", err.c_str());
+  const PlanHeader& h = plan.h;
+  const int dtype = h.dtype;
+  const bool pose = h.task == kTaskPose;
+  const size_t woff = plan.woff, wbytes = plan.wbytes;
   // commit: a reload drops the previous plan's workspace, graphs and per-shape tile tables (they index its ops and
   // buffers); the weights are replaced below
   c->loaded = false;
@@ -1014,13 +887,13 @@ int ym_load_weights(ym_ctx* c, const void* blob, size_t bytes) {
   c->buf_off.clear();
   c->cfgs.clear();
   c->dtype = dtype;
-  c->task = task; c->nc = nc; c->nm = nm; c->reg_max = reg_max; c->nl = nl;
-  for (int l = 0; l < nl; ++l) c->strides[l] = h[8 + l];
-  c->input_buf = input_buf; c->anchor_buf = anchor_buf; c->proto_buf = proto_buf; c->no = h[18];
-  c->kpt_K = task == kTaskPose ? kpt_K : 0; c->kpt_ndim = task == kTaskPose ? kpt_ndim : 0;
-  c->kpt_off = task == kTaskPose ? kpt_off : 0;
-  c->bufs = std::move(bufs);
-  c->ops = std::move(ops);
+  c->task = h.task; c->nc = h.nc; c->nm = h.nm; c->reg_max = h.reg_max; c->nl = h.nl;
+  for (int l = 0; l < h.nl; ++l) c->strides[l] = h.stride(l);
+  c->input_buf = h.input_buf; c->anchor_buf = h.anchor_buf; c->proto_buf = h.proto_buf; c->no = h.no;
+  c->kpt_K = pose ? h.kpt_k : 0; c->kpt_ndim = pose ? h.kpt_ndim : 0;
+  c->kpt_off = pose ? h.kpt_off : 0;
+  c->bufs = std::move(plan.bufs);
+  c->ops = std::move(plan.ops);
   c->blob_host.assign(static_cast<const char*>(blob), static_cast<const char*>(blob) + bytes);  // ym_broadcast_weights
   build_schedule(c);
   while (c->op_ev.size() < c->ops.size()) {
@@ -1037,12 +910,12 @@ int ym_load_weights(ym_ctx* c, const void* blob, size_t bytes) {
   // (both exact in fp32).
   std::vector<float> wstem;
   for (const Op& o : c->ops) {
-    if (o.r[0] != OP_CONV || o.r[6] != c->input_buf) continue;
-    const int N = o.r[4], Kpad = o.r[21];
-    if (o.r[1] != 3 || o.r[3] != 8 || Kpad < 72) return fail(YM_EBLOB, "op %s: unexpected stem geometry", o.name);
-    const char* w = static_cast<const char*>(blob) + woff + (size_t)(uint32_t)o.r[19];
-    const size_t esz = ym_dt_f32s(c->dtype) ? 4 : (c->dtype == YM_DT_F16 ? 2 : 1);
-    if ((size_t)(uint32_t)o.r[19] + (size_t)N * Kpad * esz > wbytes) return fail(YM_EBLOB, "stem weights out of range");
+    if (o.kind != OP_CONV || o.src0 != c->input_buf) continue;
+    const int N = o.n, Kpad = o.kpad;
+    if (o.k != 3 || o.cin != 8 || Kpad < 72) return fail(YM_EBLOB, "op %s: unexpected stem geometry", o.name);
+    const char* w = static_cast<const char*>(blob) + woff + (size_t)(uint32_t)o.w_off;
+    if ((size_t)(uint32_t)o.w_off + (size_t)N * Kpad * weight_elem_bytes(dtype, true) > wbytes)
+      return fail(YM_EBLOB, "stem weights out of range");
     wstem.assign((size_t)27 * N, 0.f);
     for (int n = 0; n < N; ++n)
       for (int t = 0; t < 27; ++t) {
@@ -1063,10 +936,10 @@ int ym_load_weights(ym_ctx* c, const void* blob, size_t bytes) {
   if (dtype == YM_DT_I8) {
     for (size_t i = 0; i < c->ops.size(); ++i) {
       const Op& o = c->ops[i];
-      if (o.r[0] != OP_CONV || o.r[6] == c->input_buf || o.r[1] != 3) continue;
-      const int N = o.r[4], Kpad = o.r[21], cin = o.r[3], cs = (cin + 15) / 16 * 16;
-      if (9 * cs > Kpad || (size_t)(uint32_t)o.r[19] + (size_t)N * Kpad > wbytes) continue;
-      const int8_t* w = reinterpret_cast<const int8_t*>(static_cast<const char*>(blob) + woff + (size_t)(uint32_t)o.r[19]);
+      if (o.kind != OP_CONV || o.src0 == c->input_buf || o.k != 3) continue;
+      const int N = o.n, Kpad = o.kpad, cs = (o.cin + 15) / 16 * 16;
+      if (9 * cs > Kpad || (size_t)(uint32_t)o.w_off + (size_t)N * Kpad * weight_elem_bytes(dtype, false) > wbytes) continue;
+      const int8_t* w = reinterpret_cast<const int8_t*>(static_cast<const char*>(blob) + woff + (size_t)(uint32_t)o.w_off);
       c->off_wtap[i] = wtap.size() * 4 + 1;  // + 1: 0 means none (relative to off_wtap0, 4-byte units * 4)
       for (int t = 0; t < 9; ++t)
         for (int n = 0; n < N; ++n) {
@@ -1107,7 +980,7 @@ static int try_chain(ym_ctx* c, size_t i, int B, const float* d_in, const ym_inf
   rc = YM_OK;
   if (ym_debug_get(YM_DBG_CHAIN) != 1 || c->dtype != YM_DT_X3 || i + 1 >= c->ops.size() || c->lane != 0) return 0;
   const Op &o0 = c->ops[i], &o1 = c->ops[i + 1];
-  if (o0.r[0] != OP_CONV || o1.r[0] != OP_CONV || o0.r[30] || o1.r[30]) return 0;
+  if (o0.kind != OP_CONV || o1.kind != OP_CONV || o0.k2 || o1.k2) return 0;
   if (c->nbr > 1 && (c->br_of[i] != 0 || c->br_of[i + 1] != 0 || !c->br_wait[i + 1].empty())) return 0;
   const int cf0 = c->op_cfg((long)i, B), cf1 = c->op_cfg((long)i + 1, B);
   const int dma = cf0 - 17;  // LDS-DMA ids follow the 17 first-generation configurations (csrc/ym_conv.hip)
@@ -1134,21 +1007,13 @@ static int try_stem_fuse(ym_ctx* c, size_t i, int B, const float* d_in, const ym
   rc = YM_OK;
   if (ym_debug_get(YM_DBG_STEMFUSE) != 1 || c->dtype != YM_DT_X3 || i + 1 >= c->ops.size()) return 0;
   const Op &o0 = c->ops[i], &o1 = c->ops[i + 1];
-  if (o0.r[0] != OP_CONV || o1.r[0] != OP_CONV || o0.r[6] != c->input_buf || !o1.r[30] || o1.r[6] != o0.r[13])
-    return 0;
+  if (o0.kind != OP_CONV || o1.kind != OP_CONV || o0.src0 != c->input_buf || !o1.k2 || o1.src0 != o0.dst) return 0;
   if (c->nbr > 1 && (c->br_of[i] != c->br_of[i + 1] || !c->br_wait[i + 1].empty())) return 0;
-  const int sb = o0.r[13];
   for (size_t j = 0; j < c->ops.size(); ++j) {  // the stem's output: op i + 1 must be its only reader
     if (j == i + 1) continue;
-    const int32_t* r = c->ops[j].r;
-    bool reads = false;
-    switch (r[0]) {
-      case OP_CONV: reads = r[6] == sb || r[10] == sb || r[17] == sb; break;
-      case OP_DW: case OP_ATTN: case OP_REQ: reads = r[6] == sb; break;
-      case OP_SPPF: reads = r[13] == sb; break;
-      default: break;
-    }
-    if (reads) return 0;
+    int rd[3];
+    const int n = op_reads(c->ops[j], rd);
+    if (std::find(rd, rd + n, o0.dst) != rd + n) return 0;
   }
   ConvArgs a0{}, a1{};
   int f0 = 0, f1 = 0;
@@ -1197,7 +1062,7 @@ static int launch_forward(ym_ctx* c, const float* d_in, int B, const ym_infer_ar
     return YM_OK;
   }
   size_t o = 0;
-  for (o = 0; o < c->ops.size() && c->ops[o].r[0] == OP_INPUT; ++o)
+  for (o = 0; o < c->ops.size() && c->ops[o].kind == OP_INPUT; ++o)
     if ((rc = launch_op(c, c->ops[o], B, d_in, args, d_dets, d_counts, st))) return rc;
   if (L > 1) HIPCK(hipEventRecord(c->fork_ev, st));
   const size_t in_img = (size_t)3 * c->cH * c->cW, det_img = (size_t)args->max_det * (6 + c->nm);
@@ -1369,7 +1234,7 @@ int ym_profile_replay(ym_ctx* c, const float* d_in, int B, int H, int W, const y
   HIPCK(hipEventCreate(&e1));
   for (size_t i = 0; i < c->ops.size(); ++i) {
     const Op& op = c->ops[i];
-    const int k = op.r[0];
+    const int k = op.kind;
     op_ms[i] = -1.f;
     // input (resets counters), decode (appends candidates) and NMS (consumes them) are not idempotent: skipped
     if (k != OP_CONV && k != OP_DW && k != OP_SPPF && k != OP_ATTN) continue;
@@ -1423,7 +1288,7 @@ int ym_tune(ym_ctx* c, const float* d_in, int B, int H, int W, const ym_infer_ar
   const bool tune_log = tl && *tl && *tl != '0';
   for (size_t i = 0; i < c->ops.size(); ++i) {
     const Op& op = c->ops[i];
-    if (op.r[0] != OP_CONV) continue;
+    if (op.kind != OP_CONV) continue;
     ConvArgs a;
     int out_f32 = 0;
     if ((rc = conv_args(c, op, B, d_in, args->in_eps, a, out_f32))) return rc;
@@ -1488,7 +1353,7 @@ int ym_get_op_cfg(ym_ctx* c, int B, int H, int W, int* cfg, int n) {
 int ym_set_op_cfg(ym_ctx* c, int B, int H, int W, const int* cfg, int n) {
   if (!c || !cfg || n != (int)c->ops.size()) return fail(YM_EINVAL, "cfg array must hold %zu entries", c ? c->ops.size() : 0);
   for (int i = 0; i < n; ++i) {
-    if (cfg[i] >= kSplitTag && c->ops[i].r[0] == OP_CONV && c->ops[i].r[30] &&
+    if (cfg[i] >= kSplitTag && c->ops[i].kind == OP_CONV && c->ops[i].k2 &&
         ((cfg[i] - kSplitTag) >> 8) < ym_conv_num_cfgs_dt(c->dtype) &&
         ((cfg[i] - kSplitTag) & 255) < ym_conv_num_cfgs_dt(c->dtype))
       continue;  // a fused pair run as two launches
@@ -1759,7 +1624,7 @@ static int bcast_check(const unsigned long long h1[2], bool is_root, int root) {
   if (h1[0] == 0)
     return fail(YM_ESTATE, is_root ? "the root context has no weights to broadcast"
                                    : "the root rank %d has no weights to broadcast", root);
-  if (h1[0] < kHdr * 4 || h1[0] > (1ull << 34)) return fail(YM_EBLOB, "broadcast blob size %llu", h1[0]);
+  if (h1[0] < sizeof(PlanHeader) || h1[0] > (1ull << 34)) return fail(YM_EBLOB, "broadcast blob size %llu", h1[0]);
   if (h1[1]) return fail(YM_ENOMEM, "%llu rank(s) could not allocate the %zu-byte staging buffer", h1[1], kBcastChunk);
   return YM_OK;
 }

@@ -15,24 +15,16 @@ s_in·s_w per output channel and the int32 zero-point correction Σ_k (128 - z_i
 x3 plans (dtype "x3", the parity plan benched): activations in the pair layout of csrc/ym_common.h (every 8-channel
 chunk as fp16 hi = fp16(x) then lo = fp16(x - hi)); every conv weight row except the stem's likewise, [hi x8 | lo x8]
 per K chunk, of the weights scaled by a power of two 2^s (max |w·2^s| in (2^13, 2^14], so the lo parts stay normal;
-s in record slot 22, W2's in slot 23), so r[21] (Kpad) counts fp16 storage elements: 2·K padded to 64.  The stem
+the record's x3 exponents), so kpad counts fp16 storage elements: 2·K padded to 64.  The stem
 keeps fp32 rows.
 
-Blob layout (int32 little-endian; parsed by `csrc/ym_runtime.cpp:ym_load_weights`):
-  header[32] | buffers[nbuf][8] | ops[nop][32] | names[nop][48 bytes] | pad to 256 | weights
-Header: [3] task (0 detect, 1 segment, 2 pose) | [4] nc | [5] nm, the extras NMS carries per row (segment: 32 mask
-coefficients; pose: K·ndim padded to 4) | [18] their offset in the anchor row | pose only: [20] K, [21] ndim, [22] offset
-of the raw keypoints in the anchor row, [23] class channels of the anchor row (nc padded to 4); 0 in other plans.
-Conv op record: [1..5] k, s, Cin, N, act | [6..9] src0 buf, coff, C, up0 | [10..12] src1 | [13..16] dst buf, coff,
-anchor level, pixel shuffle | [17..18] residual | [19..21] weight / bias offsets, Kpad | [22..24] int8 QRec, s_in·s_w,
-int32 bias (f16 / x3 plans: r[24] = 1 + offset of a fused depthwise's [9][C] weights ‖ [C] bias, GraphBuilder.fuse_dw;
-0: none) | [25..31] fused successor conv (f16 plans, GraphBuilder.fuse_pairs): W2 / bias2 offsets, N2, act2, Kpad2,
-its kernel size k2 (1: streaming FUSE; 3: Bottleneck kernel), intermediate buffer (used when the tuner runs the pair as
-two launches).
+Blob layout: `csrc/ym_plan.h` (PlanHeader, OpRec) describes every slot; HDR_FIELDS and OP_FIELDS below name them with
+the same words, in the same order.
 """
 from __future__ import annotations
 
 import struct
+from collections import namedtuple
 from typing import Dict, List
 
 import numpy as np
@@ -45,6 +37,17 @@ OP_IDS = {"input": 1, "conv": 2, "dwconv": 3, "sppf": 4, "attn": 5, "decode": 6,
 DTYPES = {"f16": 0, "f32": 1, "i8": 2, "f8": 3, "x3": 4}
 QUANT_DTYPES = ("i8", "f8")  # one-byte PTQ plans: int8 affine (torch.ao qconfig) and fp8 e4m3 (yolomi/quant.py)
 BK = 64  # conv K is padded to the kernel K step (csrc/ym_conv.hip KSTEP)
+
+# The 32 header and 32 op-record slots by name: the members of PlanHeader / OpRec in csrc/ym_plan.h, in blob order
+HDR_FIELDS = ("magic", "version", "dtype", "task", "nc", "nm", "reg_max", "nl", "stride0", "stride1", "stride2", "nbuf",
+              "nop", "wbytes_lo", "wbytes_hi", "input_buf", "anchor_buf", "proto_buf", "no", "scale", "kpt_k",
+              "kpt_ndim", "kpt_off", "cls_pad") + tuple(f"rsv{i}" for i in range(24, 32))
+OP_FIELDS = ("kind", "k", "s", "cin", "n", "act", "src0", "src0_coff", "c0", "up0", "src1", "src1_coff", "c1", "dst",
+             "dst_coff", "level", "shuffle", "res", "res_coff", "w_off", "b_off", "kpad", "q_off", "sasw_off",
+             "biasi_off", "w2_off", "b2_off", "n2", "act2", "kpad2", "k2", "mid")
+# records: named access (r.kpad), tuple indexing (r[21]); slots not given are 0
+Header = namedtuple("Header", HDR_FIELDS, defaults=(0,) * 32)
+OpRecord = namedtuple("OpRecord", OP_FIELDS, defaults=(0,) * 32)
 
 
 def fuse_conv_bn(w: np.ndarray, gamma, beta, mean, var, eps=1e-3):
@@ -218,12 +221,11 @@ def pack_graph(g: GraphBuilder, sd: Dict[str, np.ndarray], dtype: str = "f16", q
             return float(np.float32(s_)), int(z_)
     np_dt = np.float16 if dtype == "f16" else np.float32
     arena = _WeightArena()
-    op_recs: List[List[int]] = []
+    op_recs: List[OpRecord] = []
     names: List[bytes] = []
     for op in g.ops:
         a = op.args
-        r = [0] * 32
-        r[0] = OP_IDS[op.kind]
+        r = {"kind": OP_IDS[op.kind]}  # OP_FIELDS slots of this op
         if op.kind == "conv":
             w, b = _conv_weights(a, sd)  # (N, k, k, cin)
             if pose:
@@ -253,24 +255,25 @@ def pack_graph(g: GraphBuilder, sd: Dict[str, np.ndarray], dtype: str = "f16", q
                 Kpad = (K2 + BK - 1) // BK * BK  # the 64-deep storage step (32 logical K)
                 wp = np.zeros((N, Kpad), np.float16)
                 wp[:, :K2] = x3_pair_rows(w.reshape(N, K), ws)
-                r[22] = ws
+                r["q_off"] = ws  # (x3 plans: the slot holds the exponent)
             src1 = a["src1"]
             C1 = src1.C if src1 is not None else 0
             dst, res = a["dst"], a["res"]
-            r[1:6] = [a["k"], a["s"], C0 + C1, N, int(bool(a["act"]))]
-            r[6:10] = [src0.buf.id, src0.coff, C0, int(bool(a["up0"]))]
-            r[10:13] = [src1.buf.id, src1.coff, C1] if src1 is not None else [-1, 0, 0]
-            r[13:17] = [dst.buf.id, dst.coff, a["anchor_level"], int(bool(a["shuffle2x2"]))]
-            r[17:19] = [res.buf.id, res.coff] if res is not None else [-1, 0]
-            r[19] = arena.add(wp if quant or wp.dtype == np.float16 else wp.astype(np_dt))  # (x3 stem: fp32)
-            r[20] = arena.add(b.astype(np.float32))
-            r[21] = Kpad
-            if a.get("dw") is not None:  # fused depthwise (GraphBuilder.fuse_dw): r[24] = 1 + offset of [9][C] ‖ bias [C]
+            r.update(k=a["k"], s=a["s"], cin=C0 + C1, n=N, act=int(bool(a["act"])))
+            r.update(src0=src0.buf.id, src0_coff=src0.coff, c0=C0, up0=int(bool(a["up0"])))
+            r.update(src1=src1.buf.id if src1 is not None else -1, src1_coff=src1.coff if src1 is not None else 0, c1=C1)
+            r.update(dst=dst.buf.id, dst_coff=dst.coff, level=a["anchor_level"], shuffle=int(bool(a["shuffle2x2"])))
+            r.update(res=res.buf.id if res is not None else -1, res_coff=res.coff if res is not None else 0)
+            r["w_off"] = arena.add(wp if quant or wp.dtype == np.float16 else wp.astype(np_dt))  # (x3 stem: fp32)
+            r["b_off"] = arena.add(b.astype(np.float32))
+            r["kpad"] = Kpad
+            if a.get("dw") is not None:  # fused depthwise (GraphBuilder.fuse_dw): 1 + offset of [9][C] ‖ bias [C]
                 if dtype not in ("f16", "x3"):
                     raise ValueError(f"op {op.name}: fused depthwise convs are f16 / x3 only")
                 w9, bdw = _dw_weights(a["dw"]["wkey"], sd)
                 assert w9.shape == (9, C0)
-                r[24] = 1 + arena.add(np.concatenate([w9.reshape(-1), np.asarray(bdw, np.float32)]).astype(np.float32))
+                r["biasi_off"] = 1 + arena.add(
+                    np.concatenate([w9.reshape(-1), np.asarray(bdw, np.float32)]).astype(np.float32))
             pair = a.get("pair")
             if pair is not None:  # fused successor (GraphBuilder.fuse_pairs): W2 [N2][Kpad2], K = (ky, kx, this conv's N)
                 if dtype not in ("f16", "x3"):
@@ -286,14 +289,14 @@ def pack_graph(g: GraphBuilder, sd: Dict[str, np.ndarray], dtype: str = "f16", q
                     Kpad2 = (2 * K2 + BK - 1) // BK * BK
                     w2h = np.zeros((N2, Kpad2), np.float16)
                     w2h[:, :2 * K2] = x3_pair_rows(w2.reshape(N2, K2), ws2)
-                    r[23] = ws2
+                    r["sasw_off"] = ws2  # (x3 plans: W2's exponent)
                 else:
                     Kpad2 = (K2 + BK - 1) // BK * BK
                     w2p = np.zeros((N2, Kpad2), np.float32)
                     w2p[:, :K2] = w2.reshape(N2, K2)
                     w2h = w2p.astype(np.float16)
-                r[25], r[26] = arena.add(w2h), arena.add(b2.astype(np.float32))
-                r[27:32] = [N2, int(bool(pair["act"])), Kpad2, k2, pair["mid"].buf.id]
+                r.update(w2_off=arena.add(w2h), b2_off=arena.add(b2.astype(np.float32)))
+                r.update(n2=N2, act2=int(bool(pair["act"])), kpad2=Kpad2, k2=k2, mid=pair["mid"].buf.id)
             if quant:
                 s_in, z_in = qp("act:input" if stem else src0.buf.qkey)
                 so, zo = qp("out:" + a["wkey"])
@@ -305,14 +308,13 @@ def pack_graph(g: GraphBuilder, sd: Dict[str, np.ndarray], dtype: str = "f16", q
                             z_r, s_in, z_in, inv32(s_in))
                 biasi = np.zeros(N, np.int64) if (stem or f8) else (128 - z_in) * wp.astype(np.int64).sum(1)
                 assert np.abs(biasi).max() < 2 ** 31
-                r[22] = arena.add(np.frombuffer(rec, np.uint8))
-                r[23] = arena.add((np.float32(s_in) * sw).astype(np.float32))
-                r[24] = arena.add(biasi.astype(np.int32))
+                r["q_off"] = arena.add(np.frombuffer(rec, np.uint8))
+                r["sasw_off"] = arena.add((np.float32(s_in) * sw).astype(np.float32))
+                r["biasi_off"] = arena.add(biasi.astype(np.int32))
         elif op.kind == "dwconv":
             w9, b = _dw_weights(a["wkey"], sd)
-            r[3], r[5] = a["C"], int(bool(a["act"]))
-            r[6], r[7] = a["src"].buf.id, a["src"].coff
-            r[13], r[14] = a["dst"].buf.id, a["dst"].coff
+            r.update(cin=a["C"], act=int(bool(a["act"])))
+            r.update(src0=a["src"].buf.id, src0_coff=a["src"].coff, dst=a["dst"].buf.id, dst_coff=a["dst"].coff)
             if quant:
                 wq, sw = qweight(np.ascontiguousarray(w9.T), per_channel)  # (C, 9): per output channel
                 s_in, z_in = qp(a["src"].buf.qkey)
@@ -320,21 +322,19 @@ def pack_graph(g: GraphBuilder, sd: Dict[str, np.ndarray], dtype: str = "f16", q
                 s_b, z_b = qp(a["dst"].buf.qkey)
                 rec = _qrec(inv32(so), zo, qlo, qhi, 0, post(so, zo, bool(a["act"])), inv32(s_b), z_b,
                             s_in=s_in, z_in=z_in)
-                r[19], r[20] = arena.add(np.ascontiguousarray(wq.T)), arena.add(b)
-                r[22] = arena.add(np.frombuffer(rec, np.uint8))
-                r[23] = arena.add((np.float32(s_in) * sw).astype(np.float32))
+                r.update(w_off=arena.add(np.ascontiguousarray(wq.T)), b_off=arena.add(b))
+                r["q_off"] = arena.add(np.frombuffer(rec, np.uint8))
+                r["sasw_off"] = arena.add((np.float32(s_in) * sw).astype(np.float32))
             else:
-                r[19], r[20] = arena.add(w9), arena.add(b)
-        elif op.kind == "sppf":
-            r[3] = a["C"]
-            r[7] = a["src"].coff
-            r[13] = a["dst"].id
-        elif op.kind == "attn":
+                r.update(w_off=arena.add(w9), b_off=arena.add(b))
+        elif op.kind == "sppf":  # pooled in place: the dst slot names the buffer, the src0_coff slot y0's offset in it
+            r.update(cin=a["C"], src0_coff=a["src"].coff, dst=a["dst"].id)
+        elif op.kind == "attn":  # heads, key dim and value dim per head in the n, act and up0 slots
             w9, b = _dw_weights(a["wkey"], sd)
-            r[3], r[4], r[5], r[9] = a["C"], a["nh"], a["kd"], a["hd"]
-            r[6], r[7] = a["qkv"].buf.id, a["qkv"].coff
-            r[13], r[14] = a["dst"].buf.id, a["dst"].coff
-            r[21] = struct.unpack("<i", struct.pack("<f", float(np.float32(a["kd"] ** -0.5))))[0]
+            r.update(cin=a["C"], n=a["nh"], act=a["kd"], up0=a["hd"])
+            r.update(src0=a["qkv"].buf.id, src0_coff=a["qkv"].coff, dst=a["dst"].buf.id, dst_coff=a["dst"].coff)
+            # the kpad slot: the fp32 bits of the attention scale
+            r["kpad"] = struct.unpack("<i", struct.pack("<f", float(np.float32(a["kd"] ** -0.5))))[0]
             if quant:
                 wq, sw = qweight(np.ascontiguousarray(w9.T), per_channel)
                 s_in, z_in = qp(a["qkv"].buf.qkey)
@@ -342,41 +342,56 @@ def pack_graph(g: GraphBuilder, sd: Dict[str, np.ndarray], dtype: str = "f16", q
                 s_b, z_b = qp(a["dst"].buf.qkey)
                 rec = _qrec(inv32(so), zo, qlo, qhi, 0, post(so, zo, False), inv32(s_b), z_b, s_in=s_in,
                             z_in=z_in)
-                r[19], r[20] = arena.add(np.ascontiguousarray(wq.T)), arena.add(b)
-                r[22] = arena.add(np.frombuffer(rec, np.uint8))
-                r[23] = arena.add((np.float32(s_in) * sw).astype(np.float32))
+                r.update(w_off=arena.add(np.ascontiguousarray(wq.T)), b_off=arena.add(b))
+                r["q_off"] = arena.add(np.frombuffer(rec, np.uint8))
+                r["sasw_off"] = arena.add((np.float32(s_in) * sw).astype(np.float32))
             else:
-                r[19], r[20] = arena.add(w9), arena.add(b)
+                r.update(w_off=arena.add(w9), b_off=arena.add(b))
         elif op.kind == "requant":
             src, dst = a["src"], a["dst"]
-            r[3] = dst.C
-            r[6], r[7], r[9] = src.buf.id, src.coff, int(bool(a["up"]))
-            r[13], r[14] = dst.buf.id, dst.coff
+            r.update(cin=dst.C, src0=src.buf.id, src0_coff=src.coff, up0=int(bool(a["up"])))
+            r.update(dst=dst.buf.id, dst_coff=dst.coff)
             s_in, z_in = qp(src.buf.qkey)
             s_b, z_b = qp(dst.buf.qkey)
             rec = _qrec(1.0, 0, qlo, qhi, 0, np.zeros(256, np.float32), inv32(s_b), z_b, s_in=s_in, z_in=z_in)
-            r[22] = arena.add(np.frombuffer(rec, np.uint8))
-        op_recs.append(r)
+            r["q_off"] = arena.add(np.frombuffer(rec, np.uint8))
+        op_recs.append(OpRecord(**r))
         nm = op.name.encode()[:47]
         names.append(nm + b"\0" * (48 - len(nm)))
 
     wbytes = arena.bytes()
-    hdr = [0] * 32
-    hdr[0], hdr[1], hdr[2] = MAGIC, VERSION, DTYPES[dtype]
-    hdr[3] = {"detect": 0, "segment": 1, "pose": 2}[g.task]
-    hdr[4], hdr[5], hdr[6], hdr[7] = g.nc, g.nm, REG_MAX, len(STRIDES)
-    hdr[8:11] = list(STRIDES)
-    hdr[11], hdr[12] = len(g.buffers), len(g.ops)
-    hdr[13], hdr[14] = len(wbytes) & 0xFFFFFFFF, len(wbytes) >> 32
-    hdr[15], hdr[16] = g.input.id, g.anchor_buf.id
-    hdr[17] = g.proto_buf.id if g.task == "segment" else -1
-    hdr[18] = g.no
-    hdr[19] = ord(g.scale)  # checked against ym_model_desc.scale
-    if pose:  # hdr[5] (nm) = nk_pad, the extras NMS carries; K, ndim, keypoint offset in the anchor row, class pad
-        hdr[20:24] = [g.kpt_shape[0], g.kpt_shape[1], g.kpt_off, g.no - 4 * REG_MAX]
+    assert len(STRIDES) == 3  # the header's stride slots
+    hdr = Header(
+        magic=MAGIC, version=VERSION, dtype=DTYPES[dtype], task={"detect": 0, "segment": 1, "pose": 2}[g.task],
+        nc=g.nc, nm=g.nm, reg_max=REG_MAX, nl=len(STRIDES), stride0=STRIDES[0], stride1=STRIDES[1], stride2=STRIDES[2],
+        nbuf=len(g.buffers), nop=len(g.ops), wbytes_lo=len(wbytes) & 0xFFFFFFFF, wbytes_hi=len(wbytes) >> 32,
+        input_buf=g.input.id, anchor_buf=g.anchor_buf.id, proto_buf=g.proto_buf.id if g.task == "segment" else -1,
+        no=g.no, scale=ord(g.scale))  # (scale: checked against ym_model_desc.scale)
+    if pose:  # nm = nk_pad, the extras NMS carries
+        hdr = hdr._replace(kpt_k=g.kpt_shape[0], kpt_ndim=g.kpt_shape[1], kpt_off=g.kpt_off, cls_pad=g.no - 4 * REG_MAX)
     head = struct.pack("<32i", *hdr)
     bufs = b"".join(struct.pack("<8i", b.Cs or b.C, b.f, int(b.f32), 0, 0, 0, 0, 0) for b in g.buffers)
     ops = b"".join(struct.pack("<32i", *rr) for rr in op_recs)
     meta = head + bufs + ops + b"".join(names)
     meta += b"\0" * ((-len(meta)) % 256)
     return meta + wbytes
+
+
+def field_offset(header: Header, field: str, op: int = None) -> int:
+    """Byte offset in the blob of a header slot (op None) or of a slot of op record `op`."""
+    if op is None:
+        return 4 * HDR_FIELDS.index(field)
+    return 128 + 32 * header.nbuf + 128 * op + 4 * OP_FIELDS.index(field)
+
+
+def unpack_blob(blob: bytes):
+    """(header, buffers, ops, names, woff) of a packed blob: a Header, the (C, f, f32) of every buffer, an OpRecord and
+    a name per op, and the byte offset of the weight section (a record's *_off slots count from there)."""
+    h = Header(*struct.unpack_from("<32i", blob, 0))
+    o_buf, o_op = 128, 128 + 32 * h.nbuf
+    o_name = o_op + 128 * h.nop
+    buffers = [struct.unpack_from("<3i", blob, o_buf + 32 * i) for i in range(h.nbuf)]
+    ops = [OpRecord(*struct.unpack_from("<32i", blob, o_op + 128 * i)) for i in range(h.nop)]
+    names = [blob[o_name + 48 * i: o_name + 48 * (i + 1)].split(b"\0")[0].decode() for i in range(h.nop)]
+    return h, buffers, ops, names, -(-(o_name + 48 * h.nop) // 256) * 256
+

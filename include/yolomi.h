@@ -218,6 +218,38 @@ int ym_masks_slots(ym_ctx* ctx, const float* d_dets, int B, int max_det, const i
 int ym_letterbox(ym_ctx* ctx, const void* d_src, int h, int w, int row_bytes, int bgr, int uh, int uw, int top,
                  int left, float* d_dst, int Hn, int Wn, void* stream);
 
+/* Test-time augmentation for detect plans (Ultralytics predict / val with augment=True, DetectionModel._predict_augment):
+ * three passes at scales (1, 0.83, 0.67), the middle one mirrored along W, their decoded heads de-scaled, de-flipped,
+ * clipped (_clip_augmented: pass 0 loses its last A0 / 21 anchors, pass 2 its first (A2 / 21) * 16) and concatenated in
+ * pass order in front of ONE NMS.  A context holds one workspace shape, so the caller keeps one context per pass, all
+ * loaded with the same blob, and issues on one stream:
+ *   ym_tta_scale(pass 1), ym_tta_scale(pass 2)         the scaled inputs (pass 0 reads d_input itself)
+ *   ym_tta_forward(ctx_p, pass p's input) for p = 0..2  the forward up to and including the anchor decode, no NMS
+ *   ym_tta_nms(ctx_0, ctx_1, ctx_2, ...)                merge + NMS into d_dets / d_counts, as ym_infer writes them
+ * Everything is asynchronous on `stream`; once the three shapes have been seen, a call allocates nothing and captures
+ * no graph.
+ *
+ * ym_tta_shape: pass `pass` (0..2) of an H x W input is Hs x Ws, of which hc x wc = int(H s) x int(W s) is resized
+ * content and the rest (right, bottom) pad.
+ * ym_tta_scale: d_out (B x 3 x Hs x Ws fp32) = scale_img(flip ? x.flip(3) : x, s, gs = 32) of the NORMALISED batch:
+ * LoadTensor's /255 rule (*d_max > 1 + in_eps, d_max = ym_input_max of the batch or the global batch max) is applied to
+ * every tap, then torch's bilinear resize (align_corners = False), then the 0.447 pad.  pass is 1 or 2. */
+int ym_tta_shape(int H, int W, int pass, int* Hs, int* Ws, int* hc, int* wc);
+int ym_tta_scale(ym_ctx* ctx, const float* d_input, int B, int H, int W, int pass, const float* d_max, float in_eps,
+                 float* d_out, void* stream);
+/* ym_infer without its NMS stage (and without outputs): the context's decode scratch then holds this pass's boxes,
+ * scores and classes for ym_tta_nms.  args as for ym_infer; multi_label is ignored here (ym_tta_nms takes it). */
+int ym_tta_forward(ym_ctx* ctx, const float* d_input, int B, int H, int W, const ym_infer_args* args, void* stream);
+/* Merge and NMS of the three passes' last ym_tta_forward (B images; pass p ran at ym_tta_shape(H, W, p)); H x W is the
+ * full-size frame boxes are reported in and clipped to.  d_dets / d_counts and every field of args as for ym_infer
+ * (multi_label = 1: the validator's multi-label NMS over the merged set); the merged scratch belongs to ctxs[0].
+ * YM_EINVAL unless the three contexts hold the same detect plan. */
+int ym_tta_nms(ym_ctx* const* ctxs, int B, int H, int W, const ym_infer_args* args, float* d_dets, int* d_counts,
+               void* stream);
+/* Introspection for tests: the B candidate counts of the last ym_tta_nms of `ctx` (merged anchors above conf, or the
+ * (anchor, class) pairs before the max_nms cut after a multi-label call); synchronous. */
+int ym_tta_counts(ym_ctx* ctx, int* dst, int B);
+
 int ym_sync(ym_ctx* ctx);
 const char* ym_last_error(void);
 void ym_destroy(ym_ctx* ctx);

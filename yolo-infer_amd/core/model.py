@@ -219,10 +219,15 @@ class YOLO11Model:
         max_det = int(kwargs.get("max_det", 300))
         classes = kwargs.get("classes", None)
         agnostic = bool(kwargs.get("agnostic_nms", False))
+        augment = bool(kwargs.get("augment", False))
+        if augment and self.task != "detect":  # as upstream: only the Detect head is augmented
+            logger.warning(f"augment=True is not supported for {self.task} models: predicting at a single scale")
+            augment = False
         t0 = time.perf_counter()
         im, eps, imsrc = self._as_batch(source, int(kwargs.get("imgsz", 640)))
         t1 = time.perf_counter()
         eng = self.model.engine
+        run = eng.run_tta if augment else eng.run  # test-time augmentation: three scaled passes, one NMS
         bm = self.global_batch_max(im) if self.global_batch_max is not None and imsrc is None else None
         B = im.shape[0]
         names = self.model.names
@@ -232,8 +237,8 @@ class YOLO11Model:
             # first access (one device->host read shared by the call's B Results), and back-to-back predict() calls
             # queue their forwards with no host gap between them.
             out, cnt = eng.rows_buffer(B, max_det)
-            eng.run(im, conf=conf, iou=iou, max_det=max_det, classes=classes, agnostic=agnostic, in_eps=eps,
-                    batch_max=bm, dets_out=out, counts_after=True)
+            run(im, conf=conf, iou=iou, max_det=max_det, classes=classes, agnostic=agnostic, in_eps=eps,
+                batch_max=bm, dets_out=out, counts_after=True)
             lazy = LazyCounts(cnt, torch.cuda.current_stream(im.device))
             if kwargs.get("sync", False):  # per-call latency loops: return only once the forward is done
                 lazy[0]
@@ -243,8 +248,8 @@ class YOLO11Model:
                                        kpt_shape=eng.kpt_shape) for b in range(B)]
         # the NMS kernel writes this call's rows straight into a fresh tensor (the Results keep views into it)
         out = torch.empty((B, max_det, 6 + eng.nm), dtype=torch.float32, device=im.device)
-        dets, counts = eng.run(im, conf=conf, iou=iou, max_det=max_det, classes=classes, agnostic=agnostic,
-                               in_eps=eps, batch_max=bm, dets_out=out)
+        dets, counts = run(im, conf=conf, iou=iou, max_det=max_det, classes=classes, agnostic=agnostic,
+                           in_eps=eps, batch_max=bm, dets_out=out)
         masks = None
         if self.task == "segment":  # process_mask(upsample=True) on the GPU, in letterboxed coordinates
             # the masks of the first `cap` detections per image are enqueued behind the forward, reading the device
@@ -361,19 +366,20 @@ class YOLO11Model:
     export = train
 
     def val(self, data=None, imgsz: int = 640, batch: int = 16, conf: float = 0.001, iou: float = 0.7,
-            max_det: int = 300, **ignored):
+            max_det: int = 300, augment: bool = False, **ignored):
         """Ultralytics `model.val(data=...)` for detect plans (reference core/validator.py:141): the val loader's rect
         batches, `Engine.run(multi_label=True)` per batch, mAP / precision / recall as upstream computes them
         (yolomi/val.py).  data: a dataset YAML (path / val / names), a directory with images/ and labels/, or a list
         of (HWC uint8 BGR ndarray, (m, 5) normalised labels).  Returns an object with `.box.map / .map50 / .map75 /
-        .mp / .mr`, `.speed` and `.results_dict`.  Other Ultralytics val keywords are accepted and ignored."""
+        .mp / .mr`, `.speed` and `.results_dict`.  augment=True: every batch goes through the test-time-augmented run
+        (Engine.run_tta).  Other Ultralytics val keywords are accepted and ignored."""
         from yolomi.val import run_val
         if data is None:
             raise ValueError("val() needs data: a dataset YAML, a directory with images/ and labels/, or a list")
         if ignored:
             logger.info(f"val: ignoring {sorted(ignored)}")
         return run_val(self.model.engine, data, imgsz=int(imgsz), batch=int(batch), conf=float(conf), iou=float(iou),
-                       max_det=int(max_det))
+                       max_det=int(max_det), augment=bool(augment))
 
     def __repr__(self) -> str:
         return (f"YOLO11Model(task={self.task}, size={self.size}, "

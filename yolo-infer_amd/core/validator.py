@@ -50,13 +50,15 @@ class YOLO11Validator:
     def validate(self, data: Union[str, Path], imgsz: int = 640, batch: int = 16, conf: float = 0.001,
                  iou: float = 0.6, save_json: bool = True, save_hybrid: bool = False, augment: bool = False,
                  verbose: bool = True, **kwargs) -> Dict[str, Any]:
-        """Reference signature (core/validator.py:86-98).  save_json / save_hybrid / augment are accepted and ignored
-        (no COCO-JSON output, no hybrid labels, no TTA here)."""
-        ignored = {k: v for k, v in (("save_json", save_json), ("save_hybrid", save_hybrid), ("augment", augment)) if v}
+        """Reference signature (core/validator.py:86-98).  augment is forwarded to model.val (test-time augmentation);
+        save_json / save_hybrid are accepted and ignored (no COCO-JSON output, no hybrid labels here)."""
+        ignored = {k: v for k, v in (("save_json", save_json), ("save_hybrid", save_hybrid)) if v}
         if ignored:
             logger.info(f"validate: ignoring {sorted(ignored)} (not implemented on this path)")
         logger.info(f"Validation parameters: imgsz={imgsz}, batch={batch}, conf={conf}, iou={iou}")
         t0 = time.time()
+        if augment:  # (only when asked for: a model whose val() predates the keyword keeps working)
+            kwargs = dict(kwargs, augment=True)
         results = self.model.val(data=data, imgsz=imgsz, batch=batch, conf=conf, iou=iou, verbose=verbose, **kwargs)
         out = self._process_validation_results(results, time.time() - t0)
         self.validation_history.append(out)

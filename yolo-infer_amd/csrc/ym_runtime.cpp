@@ -21,6 +21,7 @@
 #include "../../include/yolomi.h"
 #include "ym_common.h"
 #include "ym_plan.h"
+#include "ym_tta.h"
 
 namespace {
 
@@ -82,6 +83,7 @@ constexpr int kMlCap = 32768;  // multi-label mode: selected keys per image (max
 
 struct GraphKey {
   int B, H, W;
+  int skip_nms;  // 1: a ym_tta_forward capture (no NMS stage)
   const void* in;
   const void* dets;
   const void* counts;
@@ -212,6 +214,16 @@ struct ym_ctx {
   int lane = 0, lane_img0 = 0;  // lane / first image of the ops being launched
   int call_B = 0;               // images of the forward being launched (all lanes)
   std::vector<GraphEntry> graphs;
+  // test-time augmentation: ym_tta_forward launches the forward without its NMS stage; the merged candidate set and the
+  // NMS scratch over it (ym_tta_nms) belong to the first pass's context and are rebuilt only when the shape changes
+  bool skip_nms = false;
+  struct TtaWs {
+    int B = 0, H = 0, W = 0, Am = 0, kstride = 0, nc = 0;
+    bool ml = false;
+    char* d = nullptr;
+    size_t off_boxes = 0, off_scores = 0, off_cls = 0, off_keys = 0, off_keys2 = 0, off_counts = 0, off_sboxes = 0,
+           off_sareas = 0, off_sup = 0, off_rows = 0, off_sel = 0, off_sel2 = 0, off_hist = 0, off_state = 0, off_seln = 0;
+  } tta;
   // the previous forward: every forward of a context uses the same arena, NMS scratch, split-K slabs /
   // counters and input_stats ticket, so a forward launched on another stream than the previous one first waits for
   // it (ym_infer: hipStreamWaitEvent); last_ev is the replayed graph's `done` event or fwd_ev (eager forwards)
@@ -263,6 +275,7 @@ struct ym_ctx {
     if (d_weights) (void)hipFree(d_weights);
     if (d_lowres) (void)hipFree(d_lowres);
     if (d_misc) (void)hipFree(d_misc);
+    if (tta.d) (void)hipFree(tta.d);
     if (cap_stream) (void)hipStreamDestroy(cap_stream);
     for (int l = 0; l < kMaxLanes; ++l) {
       if (lane_streams[l]) (void)hipStreamDestroy(lane_streams[l]);
@@ -620,6 +633,7 @@ int launch_op(ym_ctx* c, const Op& op, int B, const float* d_in, const ym_infer_
       break;
     }
     case OP_NMS: {
+      if (c->skip_nms) break;  // ym_tta_forward: the passes' candidates are merged first (ym_tta_nms)
       NmsArgs a{};
       a.anchors = reinterpret_cast<const float*>(c->bptr(c->anchor_buf));
       a.no_tot = c->bufs[c->anchor_buf].C;
@@ -1094,8 +1108,9 @@ static int launch_forward(ym_ctx* c, const float* d_in, int B, const ym_infer_ar
   return YM_OK;
 }
 
-int ym_infer(ym_ctx* c, const float* d_in, int B, int H, int W, const ym_infer_args* args, float* d_dets,
-             int* d_counts, void* stream) {
+// ym_infer, and (c->skip_nms set by the caller) ym_tta_forward
+static int infer_impl(ym_ctx* c, const float* d_in, int B, int H, int W, const ym_infer_args* args, float* d_dets,
+                      int* d_counts, void* stream) {
   int rc = check_call(c, d_in, B, H, W, args, d_dets, d_counts);
   if (rc) return rc;
   HIPCK(hipSetDevice(c->device));
@@ -1114,6 +1129,7 @@ int ym_infer(ym_ctx* c, const float* d_in, int B, int H, int W, const ym_infer_a
   GraphKey key;
   memset(&key, 0, sizeof(key));
   key.B = B; key.H = H; key.W = W; key.in = d_in; key.dets = nullptr; key.counts = d_counts; key.args = *args;
+  key.skip_nms = c->skip_nms ? 1 : 0;
   GraphKey key_d = key;  // the key of a graph whose NMS nodes could not be re-pointed
   key_d.dets = d_dets;
   for (auto& g : c->graphs) {
@@ -1158,6 +1174,226 @@ int ym_infer(ym_ctx* c, const float* d_in, int B, int H, int W, const ym_infer_a
   HIPCK(hipEventRecord(ge.done, st));
   c->last_ev = ge.done;
   c->last_st = st;
+  return YM_OK;
+}
+
+int ym_infer(ym_ctx* c, const float* d_in, int B, int H, int W, const ym_infer_args* args, float* d_dets,
+             int* d_counts, void* stream) {
+  if (c) c->skip_nms = false;
+  return infer_impl(c, d_in, B, H, W, args, d_dets, d_counts, stream);
+}
+
+// ---------------------------------------------------------------------------------- test-time augmentation
+int ym_tta_shape(int H, int W, int pass, int* Hs, int* Ws, int* hc, int* wc) {
+  if (H < 32 || W < 32 || H % 32 || W % 32 || pass < 0 || pass >= kTtaPasses)
+    return fail(YM_EINVAL, "ym_tta_shape: H and W are positive multiples of 32, pass is 0..%d", kTtaPasses - 1);
+  int v[4];
+  ym_tta_pass_shape(H, W, pass, v[0], v[1], v[2], v[3]);
+  if (Hs) *Hs = v[0];
+  if (Ws) *Ws = v[1];
+  if (hc) *hc = v[2];
+  if (wc) *wc = v[3];
+  return YM_OK;
+}
+
+int ym_tta_scale(ym_ctx* c, const float* d_in, int B, int H, int W, int pass, const float* d_max, float in_eps,
+                 float* d_out, void* stream) {
+  if (!c || !d_in || !d_max || !d_out) return fail(YM_EINVAL, "null argument");
+  if (B < 1 || H < 32 || W < 32 || H % 32 || W % 32 || pass < 1 || pass >= kTtaPasses)
+    return fail(YM_EINVAL, "ym_tta_scale: input (%d,3,%d,%d), pass %d (H, W multiples of 32; pass 1 or 2)", B, H, W, pass);
+  HIPCK(hipSetDevice(c->device));
+  TtaScaleArgs a{};
+  a.in = d_in; a.B = B; a.H = H; a.W = W; a.out = d_out;
+  ym_tta_pass_shape(H, W, pass, a.Hs, a.Ws, a.hc, a.wc);
+  a.flip = kTtaFlip[pass]; a.batch_max = d_max; a.eps = in_eps;
+  const hipError_t e = ym_launch_tta_scale(a, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail(YM_EHIP, "tta scale launch: %s", hipGetErrorString(e));
+  return YM_OK;
+}
+
+int ym_tta_forward(ym_ctx* c, const float* d_in, int B, int H, int W, const ym_infer_args* args, void* stream) {
+  if (!c || !args) return fail(YM_EINVAL, "null argument");
+  if (c->loaded && c->task != 0)
+    return fail(YM_EINVAL, "test-time augmentation: %s plans are not supported (detect plans only)", ym_task_name(c->task));
+  ym_infer_args fa = *args;  // one capture serves the single- and the multi-label NMS that follows
+  fa.multi_label = 0;
+  fa.counts_after_dets = 0;
+  // (the NMS stage is the only reader of the outputs: any device words do, they are never written)
+  float* nodets = reinterpret_cast<float*>(c->d_misc + 12288);
+  c->skip_nms = true;
+  const int rc = infer_impl(c, d_in, B, H, W, &fa, nodets, reinterpret_cast<int*>(nodets), stream);
+  c->skip_nms = false;
+  return rc;
+}
+
+// the merged scratch of ctxs[0] for B images of an H x W frame: Am merged anchors, multi-label regions on demand
+static int ensure_tta(ym_ctx* c, int B, int H, int W, int Am, bool ml) {
+  ym_ctx::TtaWs& t = c->tta;
+  if (t.d && B <= t.B && H == t.H && W == t.W && Am == t.Am && c->nc == t.nc && (!ml || t.ml)) return YM_OK;
+  if (t.d) {
+    HIPCK(hipDeviceSynchronize());  // an earlier merge / NMS on any stream may still use the old scratch
+    HIPCK(hipFree(t.d));
+    t.d = nullptr;
+  }
+  const int nB = (H == t.H && W == t.W && Am == t.Am && B < t.B) ? t.B : B;
+  t.ml = ml || (t.ml && H == t.H && W == t.W);
+  t.B = 0;
+  t.H = H; t.W = W; t.Am = Am; t.nc = c->nc;
+  t.kstride = 1;
+  while (t.kstride < Am) t.kstride <<= 1;
+  const size_t BA = (size_t)nB * Am;
+  size_t off = 0;
+  t.off_boxes = off;  off = align_up(off + BA * 16, 256);
+  t.off_scores = off; off = align_up(off + BA * 4, 256);
+  t.off_cls = off;    off = align_up(off + BA * 4, 256);
+  t.off_keys = off;   off = align_up(off + (size_t)nB * t.kstride * 8, 256);
+  t.off_keys2 = off;  off = align_up(off + (size_t)nB * t.kstride * 8, 256);
+  t.off_counts = off; off = align_up(off + (size_t)nB * 4, 256);
+  t.off_sboxes = off; off = align_up(off + BA * 16, 256);
+  t.off_sareas = off; off = align_up(off + BA * 4, 256);
+  t.off_sup = off;    off = align_up(off + BA, 256);
+  if (t.ml) {
+    t.off_rows = off;  off = align_up(off + BA * c->nc * 4, 256);
+    t.off_sel = off;   off = align_up(off + (size_t)nB * kMlCap * 8, 256);
+    t.off_sel2 = off;  off = align_up(off + (size_t)nB * kMlCap * 8, 256);
+    t.off_hist = off;  off = align_up(off + (size_t)nB * 1024 * 4, 256);
+    t.off_state = off; off = align_up(off + (size_t)nB * sizeof(MlState), 256);
+    t.off_seln = off;  off = align_up(off + (size_t)nB * 4, 256);
+  }
+  const hipError_t e = hipMalloc(&t.d, off);
+  if (e != hipSuccess) {
+    t.d = nullptr;
+    return fail(YM_ENOMEM, "tta scratch hipMalloc(%zu) failed: %s", off, hipGetErrorString(e));
+  }
+  HIPCK(hipMemset(t.d, 0, off));
+  t.B = nB;
+  return YM_OK;
+}
+
+int ym_tta_nms(ym_ctx* const* ctxs, int B, int H, int W, const ym_infer_args* args, float* d_dets, int* d_counts,
+               void* stream) {
+  if (!ctxs || !args || !d_dets || !d_counts) return fail(YM_EINVAL, "null pointer argument");
+  if (B < 1 || H < 32 || W < 32 || H % 32 || W % 32)
+    return fail(YM_EINVAL, "input shape (%d,3,%d,%d): H and W must be positive multiples of 32", B, H, W);
+  ym_ctx* c = ctxs[0];
+  for (int p = 0; p < kTtaPasses; ++p) {
+    ym_ctx* q = ctxs[p];
+    if (!q) return fail(YM_EINVAL, "null context for pass %d", p);
+    if (!q->loaded) return fail(YM_ESTATE, "ym_tta_nms before ym_load_weights (pass %d)", p);
+    for (int r = 0; r < p; ++r)
+      if (ctxs[r] == q) return fail(YM_EINVAL, "passes %d and %d share a context: every pass needs its own workspace", r, p);
+    if (q->task != 0)
+      return fail(YM_EINVAL, "test-time augmentation: %s plans are not supported (detect plans only)", ym_task_name(q->task));
+    if (q->device != c->device || q->dtype != c->dtype || q->nc != c->nc || q->reg_max != c->reg_max || q->nl != c->nl ||
+        q->no != c->no || q->nm != 0 || memcmp(q->strides, c->strides, sizeof(c->strides)) ||
+        q->bufs[q->anchor_buf].C != c->bufs[c->anchor_buf].C)
+      return fail(YM_EINVAL, "pass %d's context does not hold the plan of pass 0", p);
+    int Hs, Ws, hc, wc;
+    ym_tta_pass_shape(H, W, p, Hs, Ws, hc, wc);
+    if (!q->d_arena || q->cB < B || q->cH != Hs || q->cW != Ws)
+      return fail(YM_ESTATE, "pass %d: ym_tta_nms must follow ym_tta_forward of (%d,3,%d,%d) (workspace %dx%dx%d)", p, B, Hs,
+                  Ws, q->cB, q->cH, q->cW);
+  }
+  if (args->max_det < 1 || args->max_nms < 1) return fail(YM_EINVAL, "max_det/max_nms must be >= 1");
+  if (args->max_det > 1024) return fail(YM_EINVAL, "max_det %d > 1024 is not supported", args->max_det);
+  if (args->counts_after_dets != 0 && args->counts_after_dets != 1) return fail(YM_EINVAL, "counts_after_dets is 0 or 1");
+  if (args->multi_label != 0 && args->multi_label != 1) return fail(YM_EINVAL, "multi_label is 0 or 1");
+  const bool ml = args->multi_label && c->nc > 1;
+  if (ml && c->nc > 128) return fail(YM_EINVAL, "multi_label: nc %d > 128 is not supported", c->nc);
+  if (ml && args->max_nms > kMlCap) return fail(YM_EINVAL, "multi_label: max_nms %d > %d is not supported", args->max_nms, kMlCap);
+  HIPCK(hipSetDevice(c->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  // _clip_augmented (g = 21 = 1 + 4 + 16 grid points per stride-32 cell): pass 0 without its last A / 21 anchors,
+  // the last pass without its first (A / 21) * 16
+  TtaMergeArgs m{};
+  int Am = 0;
+  for (int p = 0; p < kTtaPasses; ++p) {
+    ym_ctx* q = ctxs[p];
+    TtaPass& P = m.p[p];
+    P.A = q->A;
+    P.first = p == kTtaPasses - 1 ? (q->A / 21) * 16 : 0;
+    P.keep = p == 0 ? q->A - q->A / 21 : q->A - P.first;
+    P.base = Am;
+    Am += P.keep;
+    P.anchors = reinterpret_cast<const float*>(q->d_arena + q->buf_off[q->anchor_buf]);
+    P.boxes = reinterpret_cast<const float4*>(q->d_arena + q->off_boxes);
+    P.scores = reinterpret_cast<const float*>(q->d_arena + q->off_scores);
+    P.cls = reinterpret_cast<const int*>(q->d_arena + q->off_cls);
+    for (int l = 0; l < q->nl; ++l) { P.lvl_W[l] = q->lvl_W[l]; P.lvl_off[l] = q->lvl_off[l]; }
+    P.s = (float)kTtaRatio[p];
+    P.flip = kTtaFlip[p];
+  }
+  if (int rc = ensure_tta(c, B, H, W, Am, ml)) return rc;
+  const ym_ctx::TtaWs& t = c->tta;
+  if (int rc = c->order_after_last(st)) return rc;  // (the scratch's previous user: ctxs[0]'s last call)
+  m.no_tot = c->bufs[c->anchor_buf].C; m.nc = c->nc; m.reg_max = c->reg_max; m.nl = c->nl;
+  for (int l = 0; l < c->nl; ++l) m.lvl_stride[l] = (float)c->strides[l];
+  m.boxes = reinterpret_cast<float4*>(t.d + t.off_boxes);
+  m.scores = reinterpret_cast<float*>(t.d + t.off_scores);
+  m.cls = reinterpret_cast<int*>(t.d + t.off_cls);
+  m.keys = reinterpret_cast<unsigned long long*>(t.d + t.off_keys);
+  m.counts = reinterpret_cast<int*>(t.d + t.off_counts);
+  m.rows = ml ? reinterpret_cast<float*>(t.d + t.off_rows) : nullptr;
+  m.Am = Am; m.kstride = t.kstride; m.B = B;
+  m.conf = args->conf; m.has_classes = args->has_classes;
+  for (int i = 0; i < 4; ++i) m.classes[i] = args->classes[i];
+  m.img_w = (float)W;
+  if (!ml) HIPCK(hipMemsetAsync(m.counts, 0, (size_t)B * 4, st));
+  hipError_t e = ym_launch_tta_merge(m, st);
+  if (e != hipSuccess) return fail(YM_EHIP, "tta merge launch: %s", hipGetErrorString(e));
+  NmsArgs a{};
+  a.boxes = m.boxes; a.scores = m.scores; a.cls = m.cls; a.keys = m.keys; a.counts = m.counts;
+  a.sboxes = reinterpret_cast<float4*>(t.d + t.off_sboxes);
+  a.sareas = reinterpret_cast<float*>(t.d + t.off_sareas);
+  a.sup = reinterpret_cast<unsigned char*>(t.d + t.off_sup);
+  a.dets = d_dets; a.out_counts = d_counts;
+  a.counts2 = args->counts_after_dets ? reinterpret_cast<int*>(d_dets + (size_t)B * args->max_det * 6) : nullptr;
+  a.A = Am; a.kstride = t.kstride; a.nm = 0; a.max_det = args->max_det; a.max_nms = args->max_nms;
+  a.agnostic = args->agnostic; a.B = B; a.nc = c->nc;
+  a.max_wh = args->max_wh; a.img_h = (float)H; a.img_w = (float)W;
+  a.iou = args->iou;
+  if (ml) {
+    MlArgs k{};
+    k.anchors = m.rows; k.no_tot = c->nc; k.cls_off = 0;
+    k.A = Am; k.nc = c->nc; k.B = B;
+    k.conf = args->conf; k.has_classes = args->has_classes;
+    for (int i = 0; i < 4; ++i) k.classes[i] = args->classes[i];
+    k.max_nms = args->max_nms; k.cap = kMlCap;
+    k.counts = m.counts;
+    k.hist = reinterpret_cast<unsigned int*>(t.d + t.off_hist);
+    k.state = reinterpret_cast<MlState*>(t.d + t.off_state);
+    k.sel = reinterpret_cast<unsigned long long*>(t.d + t.off_sel);
+    k.sel2 = reinterpret_cast<unsigned long long*>(t.d + t.off_sel2);
+    k.seln = reinterpret_cast<int*>(t.d + t.off_seln);
+    a.keys = k.sel; a.kstride = kMlCap; a.counts = k.seln;
+    a.scores = nullptr; a.cls = nullptr;
+    e = ym_launch_nms_ml(k, a, st);
+  } else {
+    if (args->conf < kPresortConf && t.kstride >= 16384) {  // as the plain path: low conf, thousands of candidates
+      a.keys2 = reinterpret_cast<unsigned long long*>(t.d + t.off_keys2);
+      a.presorted = 1;
+      e = ym_launch_nms_presort(a, st);
+    }
+    if (e == hipSuccess) e = ym_launch_nms(a, st);
+  }
+  if (e != hipSuccess) return fail(YM_EHIP, "tta NMS launch: %s", hipGetErrorString(e));
+  // the merge read every pass's arena: a later forward of any of them on another stream waits for this call
+  for (int p = 0; p < kTtaPasses; ++p) {
+    ym_ctx* q = ctxs[p];
+    if (!q->fwd_ev) HIPCK(hipEventCreateWithFlags(&q->fwd_ev, hipEventDisableTiming));
+    HIPCK(hipEventRecord(q->fwd_ev, st));
+    q->last_ev = q->fwd_ev;
+    q->last_st = st;
+  }
+  return YM_OK;
+}
+
+int ym_tta_counts(ym_ctx* c, int* dst, int B) {
+  if (!c || !dst || B < 1) return fail(YM_EINVAL, "bad ym_tta_counts arguments");
+  if (!c->tta.d || B > c->tta.B) return fail(YM_ESTATE, "no merged scratch for %d images yet (run ym_tta_nms first)", B);
+  HIPCK(hipSetDevice(c->device));
+  HIPCK(hipDeviceSynchronize());
+  HIPCK(hipMemcpy(dst, c->tta.d + c->tta.off_counts, (size_t)B * 4, hipMemcpyDefault));
   return YM_OK;
 }
 

@@ -69,6 +69,9 @@ class Engine:
         self.lanes = int(os.environ.get("YM_LANES", "1"))
         self._tuned = set()
         self._args_cache = {}
+        self._tta = None      # run_tta: [self, pass 1's engine, pass 2's engine]
+        self._tta_in = {}     # (pass, B, H, W) -> that pass's scaled input
+        self._tta_max = None  # (1,) device word: the batch max of the call
         self.tune_source: Dict[tuple, str] = {}
 
     def broadcast_weights(self, comm: int, root: int = 0):
@@ -197,6 +200,92 @@ class Engine:
             self._prepare_shape(x[:Bl], Bl, H, W, args, dets, counts, stream)
         self.rt.infer(x.data_ptr(), B, H, W, args, dets.data_ptr(), counts.data_ptr(), stream)
         return dets, counts
+
+    def _tta_engines(self):
+        """The three passes' engines (this one, then two more contexts holding the same packed model: a context has
+        one workspace shape, and the passes' shapes must coexist), created on the first augmented call."""
+        if self._tta is None:
+            if self.task != "detect":
+                raise ValueError(f"test-time augmentation is for detect plans (got task {self.task!r})")
+            if self.dtype in QUANT_DTYPES:
+                raise ValueError(f"test-time augmentation is not supported for the quantized {self.dtype!r} plans "
+                                 f"(their activation ranges were calibrated at full scale); use x3, f16 or f32")
+            if self.blob is None:
+                raise ValueError("test-time augmentation needs the packed model on the host: this engine received its "
+                                 "weights over RCCL and kept no blob")
+            subs = [Engine(self.scale, self.task, {}, self.device, self.dtype, blob=self.blob, qparams=self.qparams,
+                           nc=self.graph.nc) for _ in range(2)]
+            for e in subs:
+                e.autotune, e.lanes = self.autotune, self.lanes
+            self._tta = [self] + subs
+        return self._tta
+
+    def run_tta(self, x: torch.Tensor, conf=0.25, iou=0.7, max_det=300, classes: Optional[Sequence[int]] = None,
+                agnostic=False, in_eps=None, use_graph=True, max_nms=30000, max_wh=7680.0, lanes=None,
+                batch_max: Optional[torch.Tensor] = None, dets_out: Optional[torch.Tensor] = None,
+                counts_after: bool = False, multi_label=False):
+        """run() with test-time augmentation (Ultralytics augment=True, detect plans): the forward at scales 1, 0.83
+        (mirrored) and 0.67, the three decoded heads merged in front of one NMS (csrc/ym_tta.hip).  Arguments and
+        return value as run().  Everything is queued on the current stream; after the first call of a shape nothing
+        is allocated and no graph is captured."""
+        from .tta import pass_shapes
+        assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4 and x.shape[1] == 3
+        engines = self._tta_engines()
+        B, _, H, W = x.shape
+        if in_eps is None:
+            in_eps = torch.finfo(torch.float32).eps
+        lanes = self.lanes if lanes is None else lanes
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        if batch_max is not None:
+            assert batch_max.is_cuda and batch_max.dtype == torch.float32 and batch_max.numel() >= 1
+            bm = batch_max
+        else:  # LoadTensor's statistic once: the scaled views and pass 0's forward read the same word
+            if self._tta_max is None:
+                self._tta_max = torch.empty((1,), dtype=torch.float32, device=self.device)
+            bm = self.input_max(x, out=self._tta_max)
+        shapes = pass_shapes(H, W)
+        xs = [x]
+        for p in (1, 2):
+            Hs, Ws = shapes[p][:2]
+            xp = self._tta_in.get((p, B, H, W))
+            if xp is None:
+                xp = self._tta_in[(p, B, H, W)] = torch.empty((B, 3, Hs, Ws), dtype=torch.float32, device=self.device)
+            self.rt.tta_scale(x.data_ptr(), B, H, W, p, bm.data_ptr(), in_eps, xp.data_ptr(), stream)
+            xs.append(xp)
+        cl = tuple(classes) if classes is not None else None
+        akey = ("tta", conf, iou, max_det, max_nms, agnostic, max_wh, in_eps, cl, use_graph, lanes, bm.data_ptr(),
+                counts_after, multi_label)
+        args = self._args_cache.get(akey)
+        if args is None:
+            if len(self._args_cache) > 64:
+                self._args_cache.clear()
+            mk = lambda bmp, ca, ml: Runtime.make_args(conf, iou, max_det, max_nms, agnostic, max_wh, in_eps, classes,
+                                                       use_graph, lanes, bmp, ca, ml)
+            # pass 0's forward (the caller's values, the given max), the scaled passes' (already normalised), the NMS
+            args = self._args_cache[akey] = (mk(bm.data_ptr(), False, False), mk(0, False, False),
+                                             mk(0, counts_after, multi_label))
+        dets, counts = self.outputs(B, max_det)
+        if dets_out is not None:
+            assert (dets_out.is_cuda and dets_out.dtype == torch.float32 and dets_out.is_contiguous()
+                    and dets_out.dim() == 3 and dets_out.shape[0] >= B and tuple(dets_out.shape[1:]) == tuple(dets.shape[1:]))
+            dets = dets_out
+        if counts_after:
+            need = dets_out.storage_offset() * 4 + B * max_det * 6 * 4 + 4 * B if dets_out is not None else -1
+            if dets_out is None or dets_out.untyped_storage().nbytes() < need:
+                raise ValueError("counts_after needs dets_out from Engine.rows_buffer (rows followed by B int32 words)")
+        for p, e in enumerate(engines):
+            Hs, Ws = shapes[p][:2]
+            Bl = e.lane_batch(B, lanes)
+            if (Bl, Hs, Ws) not in e._tuned:
+                d, c = e.outputs(Bl, max_det)
+                e._prepare_shape(xs[p][:Bl], Bl, Hs, Ws, args[min(p, 1)], d, c, stream)
+            e.rt.tta_forward(xs[p].data_ptr(), B, Hs, Ws, args[min(p, 1)], stream)
+        Runtime.tta_nms([e.rt for e in engines], B, H, W, args[2], dets.data_ptr(), counts.data_ptr(), stream)
+        return dets, counts
+
+    def tta_candidate_counts(self, B: int):
+        """candidate_counts() of the last run_tta: merged anchors above conf, or (anchor, class) pairs."""
+        return self.rt.tta_counts(B)
 
     def input_max(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """(1,) fp32 device tensor: max over x (LoadTensor's statistic; asynchronous on the current stream)."""

@@ -75,6 +75,11 @@ def load_library(path: os.PathLike = LIB_PATH):
         "ym_read_scratch": (I, [P, I, P, C.c_size_t]),
         "ym_kpt_shape": (I, [P, C.POINTER(I), C.POINTER(I)]),
         "ym_input_max": (I, [P, P, C.c_size_t, P, P]),
+        "ym_tta_shape": (I, [I, I, I, C.POINTER(I), C.POINTER(I), C.POINTER(I), C.POINTER(I)]),
+        "ym_tta_scale": (I, [P, P, I, I, I, I, P, C.c_float, P, P]),
+        "ym_tta_forward": (I, [P, P, I, I, I, C.POINTER(InferArgs), P]),
+        "ym_tta_nms": (I, [C.POINTER(P), I, I, I, C.POINTER(InferArgs), P, P, P]),
+        "ym_tta_counts": (I, [P, C.POINTER(I), I]),
         "ym_broadcast_weights": (I, [P, P, I, P]),
         "ym_broadcast_weights_local": (I, [C.POINTER(P), I, I, P]),
         "ym_rccl_get_unique_id": (I, [C.POINTER(RcclId)]),
@@ -99,7 +104,8 @@ EXPORTED = ("ym_create", "ym_load_weights", "ym_broadcast_weights", "ym_broadcas
             "ym_rccl_comm_destroy", "ym_infer", "ym_input_max", "ym_calibrate", "ym_masks", "ym_masks_slots", "ym_letterbox",
             "ym_profile", "ym_profile_replay", "ym_tune", "ym_get_op_cfg", "ym_set_op_cfg", "ym_num_ops", "ym_op_name",
             "ym_num_buffers", "ym_buffer_info", "ym_read_buffer", "ym_sync", "ym_last_error", "ym_destroy",
-            "ym_version", "ym_num_conv_cfgs", "ym_set_debug", "ym_read_scratch", "ym_kpt_shape")
+            "ym_version", "ym_num_conv_cfgs", "ym_set_debug", "ym_read_scratch", "ym_kpt_shape",
+            "ym_tta_shape", "ym_tta_scale", "ym_tta_forward", "ym_tta_nms", "ym_tta_counts")
 
 DBG_NMS, DBG_DW_MODE, DBG_DW_TILE, DBG_CHAIN, DBG_CHAIN_LAUNCHES, DBG_STEMFUSE, DBG_ATTN_KB = 1, 2, 3, 4, 5, 6, 7
 DBG_PAIRST, DBG_CONV_CFG = 8, 9  # value + 1 (0: default)  # ym_set_debug keys (include/yolomi.h)
@@ -209,6 +215,26 @@ class Runtime:
     def infer(self, x_ptr: int, B: int, H: int, W: int, args: InferArgs, dets_ptr: int, counts_ptr: int, stream: int):
         _check(self.lib.ym_infer(self.ctx, C.c_void_p(x_ptr), B, H, W, C.byref(args), C.c_void_p(dets_ptr),
                                  C.c_void_p(counts_ptr), C.c_void_p(stream)))
+
+    def tta_scale(self, x_ptr: int, B: int, H: int, W: int, pass_: int, max_ptr: int, in_eps: float, out_ptr: int,
+                  stream: int):
+        _check(self.lib.ym_tta_scale(self.ctx, C.c_void_p(x_ptr), B, H, W, pass_, C.c_void_p(max_ptr), in_eps,
+                                     C.c_void_p(out_ptr), C.c_void_p(stream)))
+
+    def tta_forward(self, x_ptr: int, B: int, H: int, W: int, args: InferArgs, stream: int):
+        _check(self.lib.ym_tta_forward(self.ctx, C.c_void_p(x_ptr), B, H, W, C.byref(args), C.c_void_p(stream)))
+
+    @staticmethod
+    def tta_nms(runtimes, B: int, H: int, W: int, args: InferArgs, dets_ptr: int, counts_ptr: int, stream: int):
+        """ym_tta_nms over the three passes' Runtimes (pass order); the merged scratch is runtimes[0]'s."""
+        arr = (C.c_void_p * len(runtimes))(*[r.ctx.value for r in runtimes])
+        _check(runtimes[0].lib.ym_tta_nms(arr, B, H, W, C.byref(args), C.c_void_p(dets_ptr), C.c_void_p(counts_ptr),
+                                          C.c_void_p(stream)))
+
+    def tta_counts(self, B: int):
+        arr = (C.c_int * B)()
+        _check(self.lib.ym_tta_counts(self.ctx, arr, B))
+        return list(arr)
 
     def profile(self, x_ptr, B, H, W, args, dets_ptr, counts_ptr, stream):
         ms = (C.c_float * self.n_ops)()

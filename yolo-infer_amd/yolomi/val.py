@@ -208,9 +208,10 @@ class ValResults:
 
 
 def run_val(engine, data, imgsz: int = 640, batch: int = 16, conf: float = 0.001, iou: float = 0.7,
-            max_det: int = 300, collect: Optional[list] = None) -> ValResults:
+            max_det: int = 300, collect: Optional[list] = None, augment: bool = False) -> ValResults:
     """The validation loop on one Engine (a detect plan).  collect, when a list, receives per image
-    (native-pixel predictions (n, 6), native-pixel labels (m, 6)) in dataset order."""
+    (native-pixel predictions (n, 6), native-pixel labels (m, 6)) in dataset order.  augment: every batch through
+    Engine.run_tta (Ultralytics val(augment=True)) instead of Engine.run."""
     import torch
     if engine.task != "detect":
         raise NotImplementedError(f"validation is implemented for detect plans (got task {engine.task!r})")
@@ -233,7 +234,8 @@ def run_val(engine, data, imgsz: int = 640, batch: int = 16, conf: float = 0.001
         imgs = [imgs_cache[i] if i in imgs_cache else ds.image(i) for i in b["indices"]]
         x = make_batch(engine, imgs, b)
         t1 = time.perf_counter()
-        dets, counts = engine.run(x, conf=conf, iou=iou, max_det=max_det, multi_label=True)
+        run = engine.run_tta if augment else engine.run
+        dets, counts = run(x, conf=conf, iou=iou, max_det=max_det, multi_label=True)
         torch.cuda.synchronize(engine.device)
         t2 = time.perf_counter()
         n = counts[:len(imgs)].tolist()

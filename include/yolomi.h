@@ -208,6 +208,22 @@ int ym_masks(ym_ctx* ctx, const float* d_dets, int B, int max_det, const int* d_
 int ym_masks_slots(ym_ctx* ctx, const float* d_dets, int B, int max_det, const int* d_counts, int cap, int H, int W,
                    unsigned char* d_masks, int* d_flags, void* stream);
 
+/* Segment plans: native-resolution instance masks of the detections of the last ym_infer (same B, H, W, stream order),
+ * i.e. Ultralytics `ops.process_mask_native(proto, coef, boxes, (h0, w0))` per image (predict's retina_masks=True):
+ * the whole prototype-resolution mask, its letterbox window (scale_masks) resized bilinearly to the image's native
+ * (h0, w0), cropped to the box there, > 0.  d_dets: rows [x1 y1 x2 y2 conf cls coef...] with the box ALREADY in native
+ * pixels (scale_boxes), row i of image b at d_dets + (b * max_det + i) * det_stride floats (det_stride >= 6 + nm);
+ * d_offsets: B+1 device ints as for ym_masks; shapes / d_shapes: the B x 2 native (h0, w0) on the host (validated here
+ * and used to size the launch) and the same values on the device (what the kernel reads: the caller owns the upload,
+ * so the call copies nothing and stays asynchronous); d_mask_offsets: B device int64, the first mask byte of image
+ * b in d_masks; d_masks: packed bytes, image b's masks back to back, h0_b * w0_b bytes each (1 = inside the instance;
+ * no alignment is required); d_nonempty: total ints, 1 when the mask has any pixel set.  YM_ESTATE on a non-segment plan
+ * or when it does not follow ym_infer of the same (B, H, W); YM_EINVAL on a null pointer or a native size below 1 (or
+ * above 2^30 pixels).  Asynchronous on `stream`. */
+int ym_masks_native(ym_ctx* ctx, const float* d_dets, int det_stride, int B, int max_det, const int* d_offsets,
+                    int total, int H, int W, const int* shapes, const int* d_shapes, const long long* d_mask_offsets,
+                    unsigned char* d_masks, int* d_nonempty, void* stream);
+
 /* Image sources: Ultralytics `LetterBox` + predictor preprocessing of ONE HWC uint8 image already
  * in device memory (d_src, rows row_bytes apart, 3 channels; bgr = 1 for cv2.imread order).  The image is resized to
  * uh x uw with OpenCV's 8-bit INTER_LINEAR fixed-point arithmetic (skipped when the size does not change), placed at

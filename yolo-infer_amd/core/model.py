@@ -231,6 +231,9 @@ class YOLO11Model:
         bm = self.global_batch_max(im) if self.global_batch_max is not None and imsrc is None else None
         B = im.shape[0]
         names = self.model.names
+        if self.task == "segment" and bool(kwargs.get("retina_masks", False)):  # detect / pose ignore it, as upstream
+            return self._predict_retina(im, eps, imsrc, bm, (t0, t1), conf=conf, iou=iou, max_det=max_det,
+                                        classes=classes, agnostic=agnostic)
         if self.task != "segment" and imsrc is None:
             # Asynchronous call: the NMS kernel writes this call's rows AND its B detection counts (the int32 words
             # behind the rows) into a fresh buffer, so no host sync is needed here: the Results read the counts on
@@ -320,6 +323,50 @@ class YOLO11Model:
                 sel = torch.tensor([i for i, k in enumerate(kb) if k], dtype=torch.long, device=out.device)
                 bx = out[b].index_select(0, sel)[:, :6]
                 mk = mb[offs[b]:offs[b] + n[b]].index_select(0, sel)
+            if imsrc is None:
+                res.append(Results(im[b], names, bx, path=f"image{b}.jpg", speed=speed, masks=mk))
+            else:
+                res.append(Results.from_image(imsrc[0][b], imsrc[1][b], names, bx, speed=speed, masks=mk))
+        return res
+
+    def _predict_retina(self, im, eps, imsrc, bm, t01, conf, iou, max_det, classes, agnostic) -> List[Results]:
+        """predict(..., retina_masks=True) on a segment model: SegmentationPredictor.construct_result's other branch.
+        The boxes go to each image's native pixels first (scale_boxes; a tensor source is its own native image), then
+        ops.process_mask_native on the GPU (Engine.masks_native, csrc/ym_mask_native.hip): the prototype-resolution
+        mask's letterbox window resized to (h0, w0), cropped to the box there, > 0; detections whose mask is empty are
+        dropped.  `masks.data` is (n, h0, w0) bool and `masks.orig_shape` (h0, w0), per image.
+        The output size depends on the counts, so this is the two-read form (counts, then the non-empty flags); there
+        is no slot buffer and `_mask_cap` is not touched.  No memory cap either: the packed mask buffer is the sum of
+        n_b * h0_b * w0_b bytes, and torch's allocator error propagates when that does not fit."""
+        eng = self.model.engine
+        names = self.model.names
+        B, _, H, W = im.shape
+        out = torch.empty((B, max_det, 6 + eng.nm), dtype=torch.float32, device=im.device)
+        _, counts = eng.run(im, conf=conf, iou=iou, max_det=max_det, classes=classes, agnostic=agnostic, in_eps=eps,
+                            batch_max=bm, dets_out=out)
+        n = counts[:B].tolist()  # the first device→host read: the counts size the packed mask buffer
+        shapes = [(H, W)] * B if imsrc is None else [tuple(s) for s in imsrc[2]]
+        if imsrc is not None:
+            from yolomi.preprocess import scale_boxes
+            for b in range(B):
+                if n[b]:
+                    scale_boxes((H, W), out[b, : n[b], :4], shapes[b])
+        packed, nonempty, offs, boffs = eng.masks_native(out, n, H, W, shapes)
+        keep = nonempty.tolist()  # the second read
+        t2 = time.perf_counter()
+        speed = {"preprocess": (t01[1] - t01[0]) * 1e3, "inference": (t2 - t01[1]) * 1e3, "postprocess": 0.0}
+        pb = packed.view(torch.bool)  # the kernel writes 0/1 bytes: a bool view, no copy
+        res = []
+        for b in range(B):
+            mk = pb[boffs[b]:boffs[b + 1]].view(n[b], *shapes[b])
+            kb = keep[offs[b]:offs[b + 1]]
+            if all(kb) and imsrc is None:  # boxes, masks and input slice as views taken on access
+                res.append(Results.from_batch(im, b, names, out, n[b], path=f"image{b}.jpg", speed=speed, masks=mk))
+                continue
+            bx = out[b, :n[b], :6]
+            if not all(kb):
+                sel = torch.tensor([i for i, k in enumerate(kb) if k], dtype=torch.long, device=out.device)
+                bx, mk = bx.index_select(0, sel), mk.index_select(0, sel)
             if imsrc is None:
                 res.append(Results(im[b], names, bx, path=f"image{b}.jpg", speed=speed, masks=mk))
             else:

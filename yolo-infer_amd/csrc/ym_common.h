@@ -539,6 +539,16 @@ struct MaskArgs {
                                         // d % cap < counts[d / cap]; total = B * cap; nonempty[B*cap + b] = counts[b]
 };
 
+struct MaskNativeArgs {                 // ym_mask_native.hip: process_mask_native (retina_masks=True)
+  const float* proto; int MH, MW, nm;   // as MaskArgs
+  const float* dets; int max_det, stride;  // image b's row i at dets + (b * max_det + i) * stride: box in NATIVE pixels
+  const int* offsets; int B, total;     // as MaskArgs (B + 1 entries)
+  const int* shapes;                    // (B, 2) native (h0, w0) of every image
+  const long long* byte_off;            // (B) first mask byte of image b in `masks`
+  unsigned char* masks;                 // packed: image b's masks back to back, h0_b * w0_b bytes each
+  int* nonempty;                        // (total)
+};
+
 // ------------------------------------------------------------------------------------------------------------
 // Host-side launchers (defined in the .hip translation units).
 // cfg < 0: heuristic; strict: an inapplicable cfg is an error (else the heuristic runs)
@@ -584,6 +594,8 @@ int ym_conv_dwpw_num_cfgs();  // fused depthwise → 1x1 (ConvArgs::dw_w): its o
 int ym_conv_halo_num_cfgs();
 hipError_t ym_launch_masks(const MaskArgs& a, hipStream_t st);
 bool ym_masks_fused(const MaskArgs& a);  // the one-launch path (no (total, MH, MW) scratch)  // Segment: process_mask(upsample=True)
+// max_bytes: the largest h0 * w0 of the batch (sizes the grid)
+hipError_t ym_launch_masks_native(const MaskNativeArgs& a, long long max_bytes, hipStream_t st);
 // int8 (PTQ) plans: csrc/ym_conv_i8.hip
 // (f8: the fp8 e4m3 PTQ plan on the same kernels, csrc/ym_quant.h Q8<true>)
 hipError_t ym_launch_conv_i8(const ConvArgs& a, int cfg, hipStream_t st, bool strict, bool f8);

@@ -1726,6 +1726,38 @@ int ym_masks_slots(ym_ctx* c, const float* d_dets, int B, int max_det, const int
   return launch_masks(c, a, B, H, W, stream);
 }
 
+int ym_masks_native(ym_ctx* c, const float* d_dets, int det_stride, int B, int max_det, const int* d_offsets, int total,
+                    int H, int W, const int* shapes, const int* d_shapes, const long long* d_mask_offsets,
+                    unsigned char* d_masks, int* d_nonempty, void* stream) {
+  if (!c) return fail(YM_EINVAL, "null context");
+  if (B < 1 || total < 0 || max_det < 1 || !shapes || !d_dets || !d_offsets || !d_shapes || !d_mask_offsets ||
+      (total > 0 && (!d_masks || !d_nonempty)))
+    return fail(YM_EINVAL, "bad ym_masks_native arguments");
+  long long max_bytes = 0;
+  for (int b = 0; b < B; ++b) {
+    const long long h0 = shapes[2 * b], w0 = shapes[2 * b + 1];
+    if (h0 < 1 || w0 < 1 || h0 * w0 > (1ll << 30))
+      return fail(YM_EINVAL, "ym_masks_native: native size %lld x %lld of image %d (1 x 1 .. 2^30 pixels)", h0, w0, b);
+    max_bytes = std::max(max_bytes, h0 * w0);
+  }
+  if (c->task != 1 || c->proto_buf < 0) return fail(YM_ESTATE, "ym_masks_native needs a segment plan");
+  if (det_stride < 6 + c->nm) return fail(YM_EINVAL, "ym_masks_native: row stride %d below %d", det_stride, 6 + c->nm);
+  if (!c->d_arena || B > c->cB || H != c->cH || W != c->cW)
+    return fail(YM_ESTATE, "ym_masks_native must follow ym_infer of the same (B, H, W) (workspace %dx%dx%d)", c->cB,
+                c->cH, c->cW);
+  if (total == 0) return YM_OK;
+  HIPCK(hipSetDevice(c->device));
+  MaskNativeArgs a{};
+  a.proto = reinterpret_cast<const float*>(c->bptr(c->proto_buf));
+  a.MH = c->buf_H(c->proto_buf); a.MW = c->buf_Wd(c->proto_buf); a.nm = c->nm;
+  a.dets = d_dets; a.max_det = max_det; a.stride = det_stride;
+  a.offsets = d_offsets; a.B = B; a.total = total;
+  a.shapes = d_shapes; a.byte_off = d_mask_offsets; a.masks = d_masks; a.nonempty = d_nonempty;
+  const hipError_t e = ym_launch_masks_native(a, max_bytes, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail(YM_EHIP, "native mask kernel: %s", hipGetErrorString(e));
+  return YM_OK;
+}
+
 // ---------------------------------------------------------------------------------------------- RCCL (xGMI)
 // The init-time weight broadcast of the batch-sharded multi-GPU path: RCCL is resolved at run time
 // (dlopen of the process's already-loaded librccl — torch's, when the host is Python — else the ROCm one), so

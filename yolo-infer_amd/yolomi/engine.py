@@ -331,6 +331,36 @@ class Engine:
                           nonempty.data_ptr(), stream)
         return masks, nonempty, offs
 
+    def masks_native(self, dets: torch.Tensor, counts: Sequence[int], H: int, W: int, shapes: Sequence[tuple]):
+        """Segment plans: native-resolution masks (process_mask_native, retina_masks=True) of the last run()'s (B, H, W)
+        forward.  dets: any (>= B, max_det, >= 6 + nm) fp32 device rows whose boxes are already in native pixels
+        (scale_boxes) — run()'s own rows, or crafted ones; counts: rows used per image; shapes: each image's native
+        (h0, w0).  Returns the packed uint8 masks (image b's counts[b] masks back to back, h0_b * w0_b bytes each), the
+        (total,) int32 non-empty flags, the per-image row offsets (B + 1) and byte offsets (B + 1), both host lists."""
+        B = len(counts)
+        assert len(shapes) == B and dets.is_cuda and dets.dtype == torch.float32 and dets.dim() == 3
+        assert dets.shape[0] >= B and dets.shape[2] >= 6 + self.nm and dets.stride(2) == 1
+        assert dets.stride(0) == dets.shape[1] * dets.stride(1) and max(counts, default=0) <= dets.shape[1]
+        offs, boffs = [0], [0]
+        for n, (h0, w0) in zip(counts, shapes):
+            offs.append(offs[-1] + int(n))
+            boffs.append(boffs[-1] + int(n) * max(int(h0), 0) * max(int(w0), 0))
+        total = offs[-1]
+        masks = torch.empty((boffs[-1],), dtype=torch.uint8, device=self.device)
+        nonempty = torch.empty((total,), dtype=torch.int32, device=self.device)  # zeroed by ym_masks_native
+        # one upload: [row offsets (B + 1) | shapes (2B) | pad to an even count] as int32, then the B int64 byte offsets
+        n32 = (3 * B + 2) // 2 * 2
+        host = np.zeros((n32 + 2 * B,), dtype=np.int32)
+        host[: B + 1] = offs
+        host[B + 1: 3 * B + 1] = np.asarray([(int(h), int(w)) for h, w in shapes], dtype=np.int32).reshape(-1)
+        host[n32:].view(np.int64)[:] = boffs[:B]
+        par = torch.from_numpy(host).to(self.device, non_blocking=True)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        self.rt.masks_native(dets.data_ptr(), dets.stride(1), B, dets.shape[1], par.data_ptr(), total, H, W, shapes,
+                             par[B + 1:].data_ptr(), par[n32:].data_ptr(), masks.data_ptr(), nonempty.data_ptr(),
+                             stream)
+        return masks, nonempty, offs, boffs
+
     def masks_slots(self, dets: torch.Tensor, counts: torch.Tensor, cap: int, H: int, W: int):
         """Single-sync form of masks(): enqueued behind the forward, reading the DEVICE counts.  Returns the
         (B, cap, H, W) uint8 masks (slot (b, i) = detection i of image b, for i < min(count_b, cap)) and a (B*cap + B)

@@ -106,6 +106,21 @@ def scale_coords(img1_shape, coords: torch.Tensor, img0_shape) -> torch.Tensor:
     return coords
 
 
+def mask_window(mh: int, mw: int, shape) -> Tuple[int, int, int, int]:
+    """ops.scale_masks' crop of an (mh, mw) mask plane for a native image of `shape` = (h0, w0): (top, bottom, left,
+    right), the rows [top, bottom) and columns [left, right) the letterboxed image occupies, which process_mask_native
+    (retina_masks=True) resizes to (h0, w0).  csrc/ym_mask_native.hip restates the same rounding on the device.  A
+    window that rounds to nothing (an extreme aspect ratio, where upstream's interpolate raises) is widened to one
+    row / column."""
+    h0, w0 = int(shape[0]), int(shape[1])
+    gain = min(mh / h0, mw / w0)
+    pad = ((mw - w0 * gain) / 2, (mh - h0 * gain) / 2)
+    top, left = int(round(pad[1] - 0.1)), int(round(pad[0] - 0.1))
+    bottom, right = mh - int(round(pad[1] + 0.1)), mw - int(round(pad[0] + 0.1))
+    top, left = min(max(top, 0), mh - 1), min(max(left, 0), mw - 1)
+    return top, min(max(bottom, top + 1), mh), left, min(max(right, left + 1), mw)
+
+
 def scale_boxes(img1_shape, boxes: torch.Tensor, img0_shape) -> torch.Tensor:
     """ops.scale_boxes(img1_shape, boxes, img0_shape) (padding=True) + clip_boxes, in place on an (n, >=4) tensor."""
     gain = min(img1_shape[0] / img0_shape[0], img1_shape[1] / img0_shape[1])

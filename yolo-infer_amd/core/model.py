@@ -414,12 +414,16 @@ class YOLO11Model:
 
     def val(self, data=None, imgsz: int = 640, batch: int = 16, conf: float = 0.001, iou: float = 0.7,
             max_det: int = 300, augment: bool = False, **ignored):
-        """Ultralytics `model.val(data=...)` for detect plans (reference core/validator.py:141): the val loader's rect
-        batches, `Engine.run(multi_label=True)` per batch, mAP / precision / recall as upstream computes them
-        (yolomi/val.py).  data: a dataset YAML (path / val / names), a directory with images/ and labels/, or a list
-        of (HWC uint8 BGR ndarray, (m, 5) normalised labels).  Returns an object with `.box.map / .map50 / .map75 /
+        """Ultralytics `model.val(data=...)` for detect and pose plans (reference core/validator.py:141): the val
+        loader's rect batches, `Engine.run(multi_label=True)` per batch, mAP / precision / recall as upstream computes
+        them (yolomi/val.py).  data: a dataset YAML (path / val / names), a directory with images/ and labels/, or a
+        list of (HWC uint8 BGR ndarray, (m, 5) normalised labels).  Returns an object with `.box.map / .map50 / .map75 /
         .mp / .mr`, `.speed` and `.results_dict`.  augment=True: every batch goes through the test-time-augmented run
-        (Engine.run_tta).  Other Ultralytics val keywords are accepted and ignored."""
+        (Engine.run_tta).  Other Ultralytics val keywords are accepted and ignored.
+        A pose model reads pose labels (`cls cx cy w h` and K·ndim keypoint values per row; a YAML `kpt_shape` must be
+        the model's; in-memory labels are (m, 5 + K·ndim)) and also returns `.pose` — the same attributes from OKS
+        keypoint matches — with upstream PoseMetrics' `(B)` / `(P)` keys in `.results_dict`; augment=True warns and
+        validates at a single scale.  Segment models raise NotImplementedError."""
         from yolomi.val import run_val
         if data is None:
             raise ValueError("val() needs data: a dataset YAML, a directory with images/ and labels/, or a list")

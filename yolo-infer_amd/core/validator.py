@@ -5,7 +5,7 @@
 (`validator.py:209`), summarises (`:363-386`) and writes `benchmark_results.json` + `benchmark_summary.txt`
 (`:509-545`) — same schema here.  `validate` (reference `:86-156`) runs `YOLO11Model.val` (yolomi/val.py: the val
 loader's rect batches, multi-label NMS on the GPU, upstream's mAP / precision / recall) and returns the reference's
-`_process_validation_results` schema; `compare_models` / `cross_validate` stay out of scope.  `evaluate_detections` is
+`_process_validation_results` schema, plus `pose_metrics` (the OKS keypoint metrics) for a pose model; `compare_models` / `cross_validate` stay out of scope.  `evaluate_detections` is
 the offline mAP on detections the caller already holds.
 """
 from __future__ import annotations
@@ -68,10 +68,11 @@ class YOLO11Validator:
     def _process_validation_results(self, results: Any, validation_time: float) -> Dict[str, Any]:
         out: Dict[str, Any] = {"timestamp": datetime.now().isoformat(), "validation_time_seconds": validation_time,
                                "device": self.device, "model_info": self.model.get_model_info()}
-        box = getattr(results, "box", None)
-        if box is not None:
-            pairs = (("mAP50-95", "map"), ("mAP50", "map50"), ("mAP75", "map75"), ("precision", "mp"), ("recall", "mr"))
-            out["box_metrics"] = {k: float(getattr(box, a)) for k, a in pairs if hasattr(box, a)}
+        pairs = (("mAP50-95", "map"), ("mAP50", "map50"), ("mAP75", "map75"), ("precision", "mp"), ("recall", "mr"))
+        for key, attr in (("box_metrics", "box"), ("pose_metrics", "pose")):  # pose: a pose model's OKS metrics
+            met = getattr(results, attr, None)
+            if met is not None:
+                out[key] = {k: float(getattr(met, a)) for k, a in pairs if hasattr(met, a)}
         if hasattr(results, "speed"):
             out["speed_metrics"] = {k: float(v) for k, v in results.speed.items()}
         return out
@@ -84,7 +85,8 @@ class YOLO11Validator:
             f.write(f"Device: {results['device']}\n\nModel Information:\n" + "-" * 20 + "\n")
             for k, v in results["model_info"].items():
                 f.write(f"  {k}: {v}\n")
-            for title, key in (("Box Detection Metrics", "box_metrics"), ("Speed Metrics", "speed_metrics")):
+            for title, key in (("Box Detection Metrics", "box_metrics"), ("Pose Metrics", "pose_metrics"),
+                               ("Speed Metrics", "speed_metrics")):
                 if key in results:
                     f.write(f"\n{title}:\n" + "-" * (len(title) + 1) + "\n")
                     for k, v in results[key].items():

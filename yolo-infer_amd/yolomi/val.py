@@ -6,9 +6,14 @@ Restates, from the Ultralytics 8.3.x sources as remembered (the package is not a
 (non_max_suppression(multi_label=True, max_det=300) → scale_boxes with the image's own ratio and pad →
 match_predictions → ap_per_class).  The GPU work is `Engine.run(multi_label=True)` (csrc/ym_nms_ml.hip) and one
 `ym_letterbox` call per image with the geometry computed here.
+
+Pose plans restate `models/yolo/pose/val.py:PoseValidator` on top of that: labels with K·ndim keypoint
+columns (`data/utils.py:verify_image_label`), the predictions' keypoints to native pixels with the image's own ratio
+and pad (`ops.scale_coords`), and box and OKS metrics side by side (`metrics.evaluate_pose`, upstream `PoseMetrics`).
 """
 from __future__ import annotations
 
+import logging
 import math
 import os
 import time
@@ -16,8 +21,10 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .metrics import evaluate
+from .metrics import OKS_SIGMA, evaluate, evaluate_pose
 from .preprocess import IMG_SUFFIXES, load_image
+
+logger = logging.getLogger(__name__)
 
 STRIDE = 32
 PAD = 0.5
@@ -45,6 +52,36 @@ def read_labels(path: str) -> np.ndarray:
     return a
 
 
+def _pose_rows(rows, kpt_shape, what: str) -> np.ndarray:
+    """Label rows of `cls cx cy w h` and K·ndim keypoint values → (m, 5 + K·3) float32; any other row length is an
+    error.  ndim 2 gains a visibility column as verify_image_label writes it: 1, or 0 where x < 0 or y < 0."""
+    K, nd = int(kpt_shape[0]), int(kpt_shape[1])
+    if nd not in (2, 3):
+        raise ValueError(f"kpt_shape {(K, nd)}: ndim is 2 (x, y) or 3 (x, y, visibility)")
+    rows = [np.asarray(r, np.float32).reshape(-1) for r in rows]
+    for r in rows:
+        if len(r) != 5 + K * nd:
+            raise ValueError(f"{what}: pose label rows have {5 + K * nd} columns (`cls cx cy w h` and {K} x {nd} "
+                             f"keypoint values for kpt_shape {(K, nd)}), got {len(r)}")
+    if not rows:
+        return np.zeros((0, 5 + K * 3), np.float32)
+    a = np.stack(rows)
+    if nd == 3:
+        return a
+    k = a[:, 5:].reshape(len(a), K, 2)
+    v = np.where((k[..., 0] < 0) | (k[..., 1] < 0), 0.0, 1.0).astype(np.float32)
+    return np.concatenate([a[:, :5], np.concatenate([k, v[..., None]], -1).reshape(len(a), K * 3)], 1)
+
+
+def read_pose_labels(path: str, kpt_shape) -> np.ndarray:
+    """(m, 5 + K·3) [cls, cx, cy, w, h, (x, y, v) · K] normalised rows of a YOLO pose txt file (_pose_rows); a missing
+    or empty file is a background image."""
+    rows = []
+    if os.path.isfile(path):
+        rows = [[float(v) for v in ln.split()] for ln in open(path).read().splitlines() if ln.strip()]
+    return _pose_rows(rows, kpt_shape, path)
+
+
 def _image_files(root: str) -> List[str]:
     out = []
     for d, _, files in sorted(os.walk(root)):
@@ -66,9 +103,13 @@ class Dataset:
         return load_image(im) if isinstance(im, (str, os.PathLike)) else im
 
 
-def load_dataset(data) -> Dataset:
+def load_dataset(data, kpt_shape=None) -> Dataset:
     """data: a YAML file (path / val / names), a directory holding images/ and labels/, or a list of
-    (HWC uint8 BGR ndarray, (m, 5) [cls, cx, cy, w, h] normalised) pairs."""
+    (HWC uint8 BGR ndarray, (m, 5) [cls, cx, cy, w, h] normalised) pairs.
+    kpt_shape = (K, ndim), a pose model's: the labels are (m, 5 + K·3) rows (read_pose_labels); in-memory pairs carry
+    (m, 5 + K·ndim); a YAML's own `kpt_shape` entry, when present, must be the model's."""
+    if kpt_shape is not None:
+        kpt_shape = (int(kpt_shape[0]), int(kpt_shape[1]))
     if isinstance(data, (list, tuple)):
         imgs, labels = [], []
         for im, lb in data:
@@ -76,7 +117,10 @@ def load_dataset(data) -> Dataset:
             if im.ndim != 3 or im.shape[2] != 3 or im.dtype != np.uint8:
                 raise ValueError(f"in-memory images must be HWC uint8 BGR, got {im.shape} {im.dtype}")
             imgs.append(im)
-            labels.append(np.asarray(lb, np.float32).reshape(-1, 5))
+            if kpt_shape is None:
+                labels.append(np.asarray(lb, np.float32).reshape(-1, 5))
+            else:
+                labels.append(_pose_rows(lb, kpt_shape, f"in-memory image {len(imgs) - 1}"))
         return Dataset(imgs, labels)
     p = os.fspath(data)
     names = None
@@ -87,7 +131,11 @@ def load_dataset(data) -> Dataset:
         cfg = yaml.safe_load(open(p)) or {}
         if "val" not in cfg:
             raise ValueError(f"{p}: a dataset YAML needs a `val` entry")
-        root = cfg.get("path") or os.path.dirname(os.path.abspath(p))
+        if kpt_shape is not None and cfg.get("kpt_shape") is not None:
+            ks = cfg["kpt_shape"]
+            if not isinstance(ks, (list, tuple)) or tuple(int(v) for v in ks) != kpt_shape:
+                raise ValueError(f"{p}: kpt_shape {ks} is not the model's {list(kpt_shape)}")
+        root =cfg.get("path") or os.path.dirname(os.path.abspath(p))
         if not os.path.isabs(root):
             root = os.path.join(os.path.dirname(os.path.abspath(p)), root)
         n = cfg.get("names")
@@ -111,6 +159,8 @@ def load_dataset(data) -> Dataset:
         raise FileNotFoundError(f"dataset {p!r}: expected a YAML file or a directory with images/ and labels/")
     if not files:
         raise FileNotFoundError(f"dataset {p!r}: no images found")
+    if kpt_shape is not None:
+        return Dataset(files, [read_pose_labels(img2label_path(f), kpt_shape) for f in files], names)
     return Dataset(files, [read_labels(img2label_path(f)) for f in files], names)
 
 
@@ -170,6 +220,24 @@ def labels_to_native(lb: np.ndarray, shape0) -> np.ndarray:
     return out
 
 
+def kpts_to_native(kpts: np.ndarray, geo, gain: float, shape0) -> np.ndarray:
+    """ops.scale_coords(batch shape, kpts, shape0, ratio_pad=((gain, gain), (left, top))): letterboxed (n, K, ndim)
+    keypoints to the native image's pixels with to_native's gain and pad, x clipped to [0, w0] and y to [0, h0]
+    (scale_coords always clips).  A visibility column passes through.  Returns a float64 copy."""
+    k = np.array(kpts, np.float64)
+    k[..., 0] = ((k[..., 0] - geo[3]) / gain).clip(0, shape0[1])
+    k[..., 1] = ((k[..., 1] - geo[2]) / gain).clip(0, shape0[0])
+    return k
+
+
+def label_kpts_to_native(lb: np.ndarray, shape0, K: int) -> np.ndarray:
+    """(m, 5 + K·3) normalised pose labels → their (m, K, 3) keypoints [x · w0, y · h0, v] in native pixels."""
+    k = np.array(np.asarray(lb, np.float64).reshape(-1, 5 + K * 3)[:, 5:].reshape(-1, K, 3))
+    k[..., 0] *= shape0[1]
+    k[..., 1] *= shape0[0]
+    return k
+
+
 def make_batch(engine, imgs: Sequence[np.ndarray], b: Dict):
     """The (nb, 3, Hb, Wb) fp32 device batch of one build_batches entry: one ym_letterbox call per image."""
     import torch
@@ -193,15 +261,23 @@ class BoxMetrics:
 
 class ValResults:
     """What `YOLO11Model.val` returns: `.box.map / .map50 / .map75 / .mp / .mr`, `.speed` (ms per image) and
-    `.results_dict` (upstream DetMetrics keys)."""
+    `.results_dict` (upstream DetMetrics keys).  A pose run also has `.pose` (the same attributes from the OKS
+    matches) and upstream PoseMetrics' keys: the (B) keys, the (P) keys, fitness = box fitness + pose fitness."""
 
-    def __init__(self, m: Dict[str, float], speed: Dict[str, float], n_images: int, n_labels: int):
+    def __init__(self, m: Dict[str, float], speed: Dict[str, float], n_images: int, n_labels: int,
+                 pose: Optional[Dict[str, float]] = None):
         self.box = BoxMetrics(m)
         self.speed = speed
         self.n_images, self.n_labels = n_images, n_labels
         self.results_dict = {"metrics/precision(B)": self.box.mp, "metrics/recall(B)": self.box.mr,
                              "metrics/mAP50(B)": self.box.map50, "metrics/mAP50-95(B)": self.box.map,
                              "fitness": 0.1 * self.box.map50 + 0.9 * self.box.map}
+        if pose is not None:
+            self.pose = BoxMetrics(pose)
+            fitness = self.results_dict.pop("fitness")
+            self.results_dict.update({"metrics/precision(P)": self.pose.mp, "metrics/recall(P)": self.pose.mr,
+                                      "metrics/mAP50(P)": self.pose.map50, "metrics/mAP50-95(P)": self.pose.map,
+                                      "fitness": fitness + (0.1 * self.pose.map50 + 0.9 * self.pose.map)})
 
     def __repr__(self):
         return f"ValResults(images={self.n_images}, labels={self.n_labels}, {self.results_dict})"
@@ -209,13 +285,28 @@ class ValResults:
 
 def run_val(engine, data, imgsz: int = 640, batch: int = 16, conf: float = 0.001, iou: float = 0.7,
             max_det: int = 300, collect: Optional[list] = None, augment: bool = False) -> ValResults:
-    """The validation loop on one Engine (a detect plan).  collect, when a list, receives per image
+    """The validation loop on one Engine (a detect or pose plan).  collect, when a list, receives per image
     (native-pixel predictions (n, 6), native-pixel labels (m, 6)) in dataset order.  augment: every batch through
-    Engine.run_tta (Ultralytics val(augment=True)) instead of Engine.run."""
+    Engine.run_tta (Ultralytics val(augment=True)) instead of Engine.run.
+    A pose plan runs the same batches (its one class makes multi_label the single-label NMS, as upstream's
+    `multi_label &= nc > 1`), takes the rows' K·ndim keypoints to native pixels as well and returns box and OKS
+    metrics (`.box`, `.pose`); collect then receives (predictions, labels, predicted keypoints (n, K, ndim), label
+    keypoints (m, K, 3)); augment is not supported by the pose head: a warning, then single-scale, as upstream."""
     import torch
-    if engine.task != "detect":
-        raise NotImplementedError(f"validation is implemented for detect plans (got task {engine.task!r})")
-    ds = data if isinstance(data, Dataset) else load_dataset(data)
+    if engine.task == "segment":
+        raise NotImplementedError("validation is not implemented for segment plans (detect and pose plans are)")
+    if engine.task not in ("detect", "pose"):
+        raise NotImplementedError(f"validation is implemented for detect and pose plans (got task {engine.task!r})")
+    pose = engine.task == "pose"
+    if pose and augment:
+        # upstream BaseModel._predict_augment's words (only DetectionModel itself overrides it)
+        logger.warning("Model does not support 'augment=True', reverting to single-scale prediction.")
+        augment = False
+    kpt_shape = tuple(engine.kpt_shape) if pose else None
+    if isinstance(data, Dataset):
+        ds = data
+    else:
+        ds = load_dataset(data, kpt_shape) if pose else load_dataset(data)
     imgs_cache = {}
     shapes = []
     for i in range(len(ds)):
@@ -228,6 +319,9 @@ def run_val(engine, data, imgsz: int = 640, batch: int = 16, conf: float = 0.001
             shapes.append(tuple(ds.images[i].shape[:2]))
     preds: List[np.ndarray] = [None] * len(ds)
     gts: List[np.ndarray] = [None] * len(ds)
+    pkpts: List[np.ndarray] = [None] * len(ds)
+    gkpts: List[np.ndarray] = [None] * len(ds)
+    K, nk = (kpt_shape[0], engine.nk) if pose else (0, 0)
     t_pre = t_inf = t_post = 0.0
     for b in build_batches(shapes, imgsz, batch):
         t0 = time.perf_counter()
@@ -242,14 +336,26 @@ def run_val(engine, data, imgsz: int = 640, batch: int = 16, conf: float = 0.001
         rows = dets[:len(imgs)].cpu().numpy()
         for k, i in enumerate(b["indices"]):
             preds[i] = to_native(rows[k, :n[k], :6], b["geo"][k], b["gain"][k], shapes[i])
-            gts[i] = labels_to_native(ds.labels[i], shapes[i])
+            if pose:
+                pkpts[i] = kpts_to_native(rows[k, :n[k], 6:6 + nk].reshape(n[k], *kpt_shape), b["geo"][k],
+                                          b["gain"][k], shapes[i])
+                gts[i] = labels_to_native(ds.labels[i][:, :5], shapes[i])
+                gkpts[i] = label_kpts_to_native(ds.labels[i], shapes[i], K)
+            else:
+                gts[i] = labels_to_native(ds.labels[i], shapes[i])
         t3 = time.perf_counter()
         t_pre, t_inf, t_post = t_pre + t1 - t0, t_inf + t2 - t1, t_post + t3 - t2
     t3 = time.perf_counter()
-    m = evaluate(preds, gts)
+    if pose:
+        # upstream PoseValidator.init_metrics: the COCO constants for the 17-keypoint skeleton, else uniform 1 / K
+        sigma = OKS_SIGMA if kpt_shape == (17, 3) else np.ones(K) / K
+        mm = evaluate_pose(preds, gts, pkpts, gkpts, sigma)
+        m, mpose = mm["box"], mm["pose"]
+    else:
+        m, mpose = evaluate(preds, gts), None
     t_post += time.perf_counter() - t3
     if collect is not None:
-        collect.extend(zip(preds, gts))
+        collect.extend(zip(preds, gts, pkpts, gkpts) if pose else zip(preds, gts))
     k = 1e3 / max(len(ds), 1)
     speed = {"preprocess": t_pre * k, "inference": t_inf * k, "loss": 0.0, "postprocess": t_post * k}
-    return ValResults(m, speed, len(ds), int(sum(len(g) for g in gts)))
+    return ValResults(m, speed, len(ds), int(sum(len(g) for g in gts)), pose=mpose)

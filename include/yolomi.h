@@ -266,6 +266,29 @@ int ym_tta_nms(ym_ctx* const* ctxs, int B, int H, int W, const ym_infer_args* ar
  * (anchor, class) pairs before the max_nms cut after a multi-label call); synchronous. */
 int ym_tta_counts(ym_ctx* ctx, int* dst, int B);
 
+/* Feature embeddings (Ultralytics predict(source, embed=[layers]) / model.embed(source), BaseModel._predict_once's
+ * embed branch): per image, the global average pool (adaptive_avg_pool2d(x, (1, 1))) of the named layers' outputs,
+ * concatenated.  A layer's output is one or more channel views of plan buffers (yolomi.arch.GraphBuilder.layer_views:
+ * a Concat layer is its inputs' views, an Upsample layer its source's), so the caller passes a view table; view i's C
+ * means land in columns [sum of the earlier views' C, + C) of row b of d_out.
+ * The forward (d_input, B, H, W, stream as for ym_infer; of args only in_eps, d_batch_max and use_graph are read) runs
+ * up to and including the last op that stores a named buffer, then the pooling stage (csrc/ym_embed.hip) — nothing
+ * else: no later op, no decode, no NMS, no detection rows or counts; it is captured and replayed like ym_infer's.
+ * d_out: B rows of out_stride floats (out_stride >= the views' total C).  The mean is an fp32 tree sum over the pixels
+ * (fixed order: results are bit-identical from call to call, eager or replayed) divided once by H_i * W_i.
+ * YM_ESTATE before ym_load_weights.  YM_EINVAL: a null pointer; n_views outside 1..32; a view that names the input,
+ * the anchor rows or no buffer, leaves its buffer, is not made of whole 8-channel groups, or whose buffer no op of
+ * this plan stores (a conv fused into its successor); out_stride below the total C; an int8 / fp8 plan (their stored
+ * codes would need each buffer's scale and zero point).  Asynchronous on `stream`. */
+typedef struct {
+  int buf;  /* plan buffer (ym_buffer_info ids) */
+  int coff; /* first channel, a multiple of 8 */
+  int C;    /* channels, a multiple of 8 */
+  int reserved; /* 0 */
+} ym_embed_view;
+int ym_embed(ym_ctx* ctx, const float* d_input, int B, int H, int W, const ym_infer_args* args,
+             const ym_embed_view* views, int n_views, float* d_out, long long out_stride, void* stream);
+
 int ym_sync(ym_ctx* ctx);
 const char* ym_last_error(void);
 void ym_destroy(ym_ctx* ctx);

@@ -220,6 +220,8 @@ class YOLO11Model:
         classes = kwargs.get("classes", None)
         agnostic = bool(kwargs.get("agnostic_nms", False))
         augment = bool(kwargs.get("augment", False))
+        if kwargs.get("embed", None) is not None:
+            return self._predict_embed(source, kwargs)
         if augment and self.task != "detect":  # as upstream: only the Detect head is augmented
             logger.warning(f"augment=True is not supported for {self.task} models: predicting at a single scale")
             augment = False
@@ -328,6 +330,34 @@ class YOLO11Model:
             else:
                 res.append(Results.from_image(imsrc[0][b], imsrc[1][b], names, bx, speed=speed, masks=mk))
         return res
+
+    def _predict_embed(self, source, kwargs) -> List[torch.Tensor]:
+        """predict(source, embed=[layers]): Ultralytics _predict_once's embed branch.  One 1-D fp32 device tensor per
+        image (views of one fresh (B, sum C_i) buffer): the global-average-pooled outputs of the named layers,
+        concatenated in ascending layer order; the forward stops at the last of them (Engine.embed).  Preprocessing is
+        predict's own (letterboxed image sources, LoadTensor's /255 rule for tensors).  augment and retina_masks do
+        not apply (upstream returns before either is looked at).  Unlike upstream, which ignores an index no layer
+        has and returns ordinary predictions, an index outside 0..22, a non-integer or an empty list raises."""
+        from yolomi.arch import normalize_embed
+        eng = self.model.engine
+        layers = normalize_embed(kwargs["embed"])
+        eng._embed_table(layers)  # (raises for a layer the plan does not store, or a quantized plan)
+        ignored = [k for k in ("augment", "retina_masks") if kwargs.get(k, False)]
+        if ignored:
+            logger.debug(f"embed={list(layers)}: {', '.join(ignored)} ignored (the forward stops at layer {layers[-1]})")
+        im, eps, imsrc = self._as_batch(source, int(kwargs.get("imgsz", 640)))
+        bm = self.global_batch_max(im) if self.global_batch_max is not None and imsrc is None else None
+        # the captured pooling stage writes the engine's own (B, sum C) tensor (its address is part of the graph key:
+        # fresh rows per call would capture a graph per call); the caller gets a copy that later calls leave alone
+        return list(eng.embed(im, layers, in_eps=eps, batch_max=bm).clone().unbind(0))
+
+    def embed(self, source, **kwargs) -> List[torch.Tensor]:
+        """Ultralytics Model.embed: predict(source, embed=[len(model.model) - 2]) unless `embed` is given — layer 22,
+        the last neck C3k2 (256 channels for yolo11n, 512 for yolo11s)."""
+        from yolomi.arch import DEFAULT_EMBED
+        if kwargs.get("embed", None) is None:
+            kwargs["embed"] = list(DEFAULT_EMBED)
+        return self.predict(source, **kwargs)
 
     def _predict_retina(self, im, eps, imsrc, bm, t01, conf, iou, max_det, classes, agnostic) -> List[Results]:
         """predict(..., retina_masks=True) on a segment model: SegmentationPredictor.construct_result's other branch.

@@ -21,6 +21,7 @@
 #include "../../include/yolomi.h"
 #include "ym_common.h"
 #include "ym_plan.h"
+#include "ym_embed.h"
 #include "ym_tta.h"
 
 namespace {
@@ -84,6 +85,10 @@ constexpr int kMlCap = 32768;  // multi-label mode: selected keys per image (max
 struct GraphKey {
   int B, H, W;
   int skip_nms;  // 1: a ym_tta_forward capture (no NMS stage)
+  int embed_stop;  // ym_embed captures: 1 + the last op of the truncated forward (0: a whole forward) ...
+  int embed_n;     // ... the views pooled behind it (GraphEntry::embed_views) ...
+  const void* embed_out;  // ... and where their means go
+  long long embed_ld;
   const void* in;
   const void* dets;
   const void* counts;
@@ -103,6 +108,7 @@ struct GraphEntry {
   hipEvent_t done = nullptr;             // recorded behind every launch of `exec` (retire_graph waits on it)
   std::vector<hipGraphNode_t> nms_nodes;  // empty: dets is part of the key
   std::vector<NmsArgs> nms_args;
+  std::vector<ym_embed_view> embed_views;  // a ym_embed capture: the pooled views (compared with the key)
 };
 
 // The NMS kernel nodes of a captured forward and their arguments (false when none is found: the caller keys the
@@ -217,6 +223,14 @@ struct ym_ctx {
   // test-time augmentation: ym_tta_forward launches the forward without its NMS stage; the merged candidate set and the
   // NMS scratch over it (ym_tta_nms) belong to the first pass's context and are rebuilt only when the shape changes
   bool skip_nms = false;
+  // feature embeddings (ym_embed): the forward stops after op embed_stop (-1: a whole forward) and the pooling stage
+  // (csrc/ym_embed.hip) reads embed_views into embed_out; d_embed holds the chunk partials of large maps
+  int embed_stop = -1;
+  std::vector<ym_embed_view> embed_views;
+  float* embed_out = nullptr;
+  long long embed_ld = 0;
+  float* d_embed = nullptr;
+  size_t embed_floats = 0;
   struct TtaWs {
     int B = 0, H = 0, W = 0, Am = 0, kstride = 0, nc = 0;
     bool ml = false;
@@ -276,6 +290,7 @@ struct ym_ctx {
     if (d_lowres) (void)hipFree(d_lowres);
     if (d_misc) (void)hipFree(d_misc);
     if (tta.d) (void)hipFree(tta.d);
+    if (d_embed) (void)hipFree(d_embed);
     if (cap_stream) (void)hipStreamDestroy(cap_stream);
     for (int l = 0; l < kMaxLanes; ++l) {
       if (lane_streams[l]) (void)hipStreamDestroy(lane_streams[l]);
@@ -539,7 +554,8 @@ int launch_op(ym_ctx* c, const Op& op, int B, const float* d_in, const ym_infer_
       a.batch_max = args->d_batch_max;
       a.cnt = reinterpret_cast<int*>(c->d_arena + c->off_cnt);
       a.cnt_len = kMaxLanes * kSplitCounters;
-      e = ym_launch_prep(dt, a, reinterpret_cast<int*>(c->d_arena + c->off_counts), B, st);
+      // (ym_embed runs no decode: the previous forward's candidate counts stay as they are)
+      e = ym_launch_prep(dt, a, reinterpret_cast<int*>(c->d_arena + c->off_counts), c->embed_stop >= 0 ? 0 : B, st);
       break;
     }
     case OP_CONV: {
@@ -1040,6 +1056,41 @@ static int try_stem_fuse(ym_ctx* c, size_t i, int B, const float* d_in, const ym
   return 1;
 }
 
+// The pooling stage's descriptor table for B images of an H x W input: the context's validated views (ym_embed) at
+// their places in the arena (`with_ptrs`; without: the geometry only, to size the partials before the arena exists).
+static void embed_args(const ym_ctx* c, int B, int H, int W, bool with_ptrs, EmbedArgs& a) {
+  a = EmbedArgs{};
+  a.n = (int)c->embed_views.size();
+  a.B = B;
+  a.out = c->embed_out;
+  a.ld = (long)c->embed_ld;
+  a.part = c->d_embed;
+  int col = 0;
+  for (int i = 0; i < a.n; ++i) {
+    const ym_embed_view& v = c->embed_views[i];
+    const BufDesc& bd = c->bufs[v.buf];
+    EmbedDesc& d = a.d[i];
+    d.ptr = with_ptrs ? c->d_arena + c->buf_off[v.buf] : reinterpret_cast<const void*>(c);  // (any non-null)
+    d.P = (H / bd.f) * (W / bd.f);
+    d.pitch = bd.C;
+    d.coff = v.coff;
+    d.C = v.C;
+    d.mode = (bd.f32 || c->dtype == YM_DT_F32) ? YM_EMB_F32 : (c->dtype == YM_DT_X3 ? YM_EMB_X3 : YM_EMB_F16);
+    d.col = col;
+    col += v.C;
+  }
+}
+
+static int launch_embed(ym_ctx* c, int B, hipStream_t st) {
+  EmbedArgs a;
+  embed_args(c, B, c->cH, c->cW, true, a);
+  const long need = ym_embed_part_floats(a);
+  if (need < 0 || (size_t)need > c->embed_floats) return fail(YM_EINVAL, "ym_embed: bad view table");
+  const hipError_t e = ym_launch_embed(a, st);
+  if (e != hipSuccess) return fail(YM_EHIP, "embed pooling launch: %s", hipGetErrorString(e));
+  return YM_OK;
+}
+
 // Launch one forward: the input statistics over the WHOLE batch (LoadTensor's /255 rule is a batch-wide max), then
 // every other op per lane on its image slice.  With fork/join events the lanes are parallel graph branches when
 // `st` is capturing; eagerly (no capture) they run on the lane streams concurrently as well.
@@ -1050,14 +1101,20 @@ static int launch_forward(ym_ctx* c, const float* d_in, int B, const ym_infer_ar
   c->call_B = B;
   c->lane = 0;
   c->lane_img0 = 0;
+  // ym_embed: ops [0, nops) only, every op its own launch (a two-op launch could run past the stop, and the fused
+  // stem never stores model.0's output), then the pooling stage
+  const bool embed = c->embed_stop >= 0;
+  const size_t nops = embed ? (size_t)c->embed_stop + 1 : c->ops.size();
   if (L == 1 && c->nbr > 1) {  // one lane: the branch schedule (build_schedule)
     hipStream_t bs[kMaxLanes] = {st};
+    bool opened[kMaxLanes] = {};  // streams that took an op (a whole forward: all nbr; a truncated one maybe fewer)
     for (int s = 1; s < kMaxLanes; ++s) bs[s] = c->lane_streams[s];
-    for (size_t i = 0; i < c->ops.size(); ++i) {
+    for (size_t i = 0; i < nops; ++i) {
       const int s = c->br_of[i];
+      opened[s] = true;
       for (int j : c->br_wait[i]) HIPCK(hipStreamWaitEvent(bs[s], c->op_ev[j], 0));
       c->lane = s;  // split-K slab / counter region of this stream
-      if (try_stem_fuse(c, i, B, d_in, args, bs[s], rc) || try_chain(c, i, B, d_in, args, bs[s], rc)) {  // ops i, i + 1
+      if (!embed && (try_stem_fuse(c, i, B, d_in, args, bs[s], rc) || try_chain(c, i, B, d_in, args, bs[s], rc))) {  // ops i, i + 1
         c->lane = 0;
         if (rc) return rc;
         if (c->br_rec[i]) HIPCK(hipEventRecord(c->op_ev[i], bs[s]));
@@ -1069,14 +1126,15 @@ static int launch_forward(ym_ctx* c, const float* d_in, int B, const ym_infer_ar
       if (rc) return rc;
       if (c->br_rec[i]) HIPCK(hipEventRecord(c->op_ev[i], bs[s]));
     }
-    for (int s = 1; s < c->nbr; ++s) {  // every branch joins back into the caller's stream
+    for (int s = 1; s < c->nbr; ++s) {  // every branch that was opened joins back into the caller's stream
+      if (!opened[s]) continue;
       HIPCK(hipEventRecord(c->join_ev[s], bs[s]));
       HIPCK(hipStreamWaitEvent(st, c->join_ev[s], 0));
     }
-    return YM_OK;
+    return embed ? launch_embed(c, B, st) : YM_OK;  // (the pooling stage reads behind the join)
   }
   size_t o = 0;
-  for (o = 0; o < c->ops.size() && c->ops[o].kind == OP_INPUT; ++o)
+  for (o = 0; o < nops && c->ops[o].kind == OP_INPUT; ++o)
     if ((rc = launch_op(c, c->ops[o], B, d_in, args, d_dets, d_counts, st))) return rc;
   if (L > 1) HIPCK(hipEventRecord(c->fork_ev, st));
   const size_t in_img = (size_t)3 * c->cH * c->cW, det_img = (size_t)args->max_det * (6 + c->nm);
@@ -1086,8 +1144,8 @@ static int launch_forward(ym_ctx* c, const float* d_in, int B, const ym_infer_ar
     c->lane = l;
     c->lane_img0 = l * Bl;
     const int nb = B - l * Bl < Bl ? B - l * Bl : Bl;
-    for (size_t i = o; i < c->ops.size(); ++i) {
-      if (L == 1 && (try_stem_fuse(c, i, nb, d_in, args, ls, rc) || try_chain(c, i, nb, d_in, args, ls, rc))) {
+    for (size_t i = o; i < nops; ++i) {
+      if (L == 1 && !embed && (try_stem_fuse(c, i, nb, d_in, args, ls, rc) || try_chain(c, i, nb, d_in, args, ls, rc))) {
         ++i;
         if (!rc) continue;
       } else {
@@ -1105,10 +1163,10 @@ static int launch_forward(ym_ctx* c, const float* d_in, int B, const ym_infer_ar
     }
   }
   c->lane = c->lane_img0 = 0;
-  return YM_OK;
+  return embed ? launch_embed(c, B, st) : YM_OK;  // (ym_embed runs one lane: everything above is on `st`)
 }
 
-// ym_infer, and (c->skip_nms set by the caller) ym_tta_forward
+// ym_infer, (c->skip_nms set by the caller) ym_tta_forward and (c->embed_stop) ym_embed
 static int infer_impl(ym_ctx* c, const float* d_in, int B, int H, int W, const ym_infer_args* args, float* d_dets,
                       int* d_counts, void* stream) {
   int rc = check_call(c, d_in, B, H, W, args, d_dets, d_counts);
@@ -1130,10 +1188,21 @@ static int infer_impl(ym_ctx* c, const float* d_in, int B, int H, int W, const y
   memset(&key, 0, sizeof(key));
   key.B = B; key.H = H; key.W = W; key.in = d_in; key.dets = nullptr; key.counts = d_counts; key.args = *args;
   key.skip_nms = c->skip_nms ? 1 : 0;
+  const bool embed = c->embed_stop >= 0;
+  if (embed) {
+    key.embed_stop = c->embed_stop + 1;
+    key.embed_n = (int)c->embed_views.size();
+    key.embed_out = c->embed_out;
+    key.embed_ld = c->embed_ld;
+  }
+  auto same_views = [&](const GraphEntry& g) {
+    return !embed || (g.embed_views.size() == c->embed_views.size() &&
+                      memcmp(g.embed_views.data(), c->embed_views.data(), g.embed_views.size() * sizeof(ym_embed_view)) == 0);
+  };
   GraphKey key_d = key;  // the key of a graph whose NMS nodes could not be re-pointed
   key_d.dets = d_dets;
   for (auto& g : c->graphs) {
-    if (g.key == key || g.key == key_d) {
+    if ((g.key == key || g.key == key_d) && same_views(g)) {
       // re-pointable: new rows through the NMS nodes' parameters.  A launch already queued keeps the parameters it
       // was launched with (hipGraphExecKernelNodeSetParams changes later launches only:
       // tests/test_gpu_kernels.py test_repointed_graph_rows_with_no_sync_between_calls), so no wait here — an
@@ -1167,6 +1236,7 @@ static int infer_impl(ym_ctx* c, const float* d_in, int B, int H, int W, const y
     return fail(YM_EHIP, "graph instantiate: %s", hipGetErrorString(e));
   }
   ge.dets = d_dets;
+  if (embed) ge.embed_views = c->embed_views;
   static const bool no_repoint = [] { const char* v = getenv("YM_GRAPH_REPOINT"); return v && *v == '0'; }();
   ge.key = (!no_repoint && find_nms_nodes(ge)) ? key : key_d;
   c->graphs.push_back(ge);
@@ -1223,6 +1293,79 @@ int ym_tta_forward(ym_ctx* c, const float* d_in, int B, int H, int W, const ym_i
   c->skip_nms = true;
   const int rc = infer_impl(c, d_in, B, H, W, &fa, nodets, reinterpret_cast<int*>(nodets), stream);
   c->skip_nms = false;
+  return rc;
+}
+
+// ---------------------------------------------------------------------------------- feature embeddings
+int ym_embed(ym_ctx* c, const float* d_in, int B, int H, int W, const ym_infer_args* args, const ym_embed_view* views,
+             int n_views, float* d_out, long long out_stride, void* stream) {
+  if (!c) return fail(YM_EINVAL, "null context");
+  if (!c->loaded) return fail(YM_ESTATE, "ym_embed before ym_load_weights");
+  if (!d_in || !args || !views || !d_out) return fail(YM_EINVAL, "null pointer argument");
+  if (ym_dt_q8(c->dtype))
+    return fail(YM_EINVAL, "ym_embed: the quantized plans are not supported (their stored codes need each buffer's "
+                           "scale and zero point); use an x3, f16 or f32 plan");
+  if (B < 1 || H < 32 || W < 32 || H % 32 || W % 32)
+    return fail(YM_EINVAL, "input shape (%d,3,%d,%d): H and W must be positive multiples of 32", B, H, W);
+  if (n_views < 1 || n_views > kEmbedMaxViews)
+    return fail(YM_EINVAL, "ym_embed: %d views (1..%d)", n_views, kEmbedMaxViews);
+  long long cols = 0;
+  std::vector<char> want(c->bufs.size(), 0);
+  for (int i = 0; i < n_views; ++i) {
+    const ym_embed_view& v = views[i];
+    if (v.buf < 0 || v.buf >= (int)c->bufs.size() || v.buf == c->input_buf || c->bufs[v.buf].f < 1)
+      return fail(YM_EINVAL, "ym_embed: view %d names buffer %d, which is not a feature map of this plan", i, v.buf);
+    if (v.coff < 0 || v.C < 8 || v.coff % 8 || v.C % 8 || (long long)v.coff + v.C > c->bufs[v.buf].C)
+      return fail(YM_EINVAL, "ym_embed: view %d, channels [%d, %d + %d) of buffer %d (%d channels): outside the buffer "
+                             "or not in groups of 8", i, v.coff, v.coff, v.C, v.buf, c->bufs[v.buf].C);
+    want[v.buf] = 1;
+    cols += v.C;
+  }
+  if (out_stride < cols)
+    return fail(YM_EINVAL, "ym_embed: row stride %lld below the %lld pooled channels", out_stride, cols);
+  // the forward runs up to and including the last op that writes a requested buffer
+  int stop = -1;
+  for (size_t i = 0; i < c->ops.size(); ++i) {
+    const int w = op_writes(c->ops[i]);
+    if (w >= 0 && w < (int)want.size() && want[w]) {
+      want[w] = 2;
+      stop = (int)i;
+    }
+  }
+  for (size_t b = 0; b < want.size(); ++b)
+    if (want[b] == 1) return fail(YM_EINVAL, "ym_embed: no op of this plan stores buffer %zu", b);
+  HIPCK(hipSetDevice(c->device));
+  c->embed_views.assign(views, views + n_views);
+  c->embed_out = d_out;
+  c->embed_ld = out_stride;
+  EmbedArgs ea;
+  embed_args(c, B, H, W, false, ea);
+  const long need = ym_embed_part_floats(ea);
+  if (need < 0) return fail(YM_EINVAL, "ym_embed: bad view table");
+  if ((size_t)need > c->embed_floats) {  // the chunk partials grow: no captured pooling stage may keep the old ones
+    c->clear_graphs();
+    if (c->d_embed) {
+      HIPCK(hipDeviceSynchronize());
+      HIPCK(hipFree(c->d_embed));
+      c->d_embed = nullptr;
+      c->embed_floats = 0;
+    }
+    const hipError_t e = hipMalloc(&c->d_embed, (size_t)need * sizeof(float));
+    if (e != hipSuccess) {
+      c->d_embed = nullptr;
+      return fail(YM_ENOMEM, "embed partials hipMalloc(%ld floats): %s", need, hipGetErrorString(e));
+    }
+    c->embed_floats = (size_t)need;
+  }
+  // what reaches the truncated forward: the /255 rule's inputs and the launch mode; one lane; no output is written
+  ym_infer_args fa{};
+  fa.conf = 0.25f; fa.max_wh = 7680.f; fa.iou = 0.7; fa.max_det = 300; fa.max_nms = 30000;
+  fa.in_eps = args->in_eps; fa.use_graph = args->use_graph; fa.lanes = 1; fa.d_batch_max = args->d_batch_max;
+  float* nodets = reinterpret_cast<float*>(c->d_misc + 12288);
+  c->skip_nms = false;
+  c->embed_stop = stop;
+  const int rc = infer_impl(c, d_in, B, H, W, &fa, nodets, reinterpret_cast<int*>(nodets), stream);
+  c->embed_stop = -1;
   return rc;
 }
 

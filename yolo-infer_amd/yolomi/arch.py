@@ -396,6 +396,41 @@ class GraphBuilder:
         L22 = self.C3k2(22, L20, ch(1024), 2, True, 0.5, x1=L10)
         self.Detect(23, [L16, L19, L22])
         # the stem reads 3 real channels out of the 8-channel padded input: pad its weights' Cin to 8 at pack time
+        # Layer map (feature embeddings): where layer i's output lives, as views in channel order.  A record beside
+        # the plan: no op, buffer or packed byte depends on it.  Upsample (11, 14) maps to its source (a nearest 2x
+        # copy has the same mean), Concat (12, 15, 18, 21) to its inputs' views: neither is ever materialised.
+        self.layers: Dict[int, List[View]] = {
+            0: [L0], 1: [L1], 2: [L2], 3: [L3], 4: [L4], 5: [L5], 6: [L6], 7: [L7], 8: [L8], 9: [L9], 10: [L10],
+            11: [L10], 12: [L10, L6], 13: [L13], 14: [L13], 15: [L13, L4], 16: [L16], 17: [L17], 18: [L17, L13],
+            19: [L19], 20: [L20], 21: [L20, L10], 22: [L22]}
+
+    # ------------------------------------------------------------------ layer map (feature embeddings)
+    def written_buffers(self) -> set:
+        """Ids of the buffers some op of this plan writes (a fused pair never stores its first conv's output)."""
+        out = set()
+        for op in self.ops:
+            d = op.args.get("dst")
+            if d is not None:
+                out.add(d.id if isinstance(d, Buffer) else d.buf.id)
+        return out
+
+    def layer_views(self, i: int) -> List[View]:
+        """Views (buffer, channel offset, channels; the map's stride is view.buf.f) holding layer i's output, in
+        channel order.  ValueError when this plan never stores one of them."""
+        views = self.layers[i]
+        if not self.layer_stored(i):
+            raise ValueError(f"layer {i} is not stored by this plan (its conv is fused into the next one and "
+                             f"{views[0].buf.name} is never written); the f32 plan stores it")
+        return views
+
+    def layer_stored(self, i: int) -> bool:
+        wr = self.written_buffers()
+        return all(v.buf.id in wr for v in self.layers[i])
+
+    def embed_layers(self) -> List[int]:
+        """The layer indices whose outputs this plan stores."""
+        wr = self.written_buffers()
+        return [i for i, vs in sorted(self.layers.items()) if all(v.buf.id in wr for v in vs)]
 
     # ------------------------------------------------------------------ fused pairs (f16 plans)
     STREAM_KS = {1: (2, 4, 6, 8), 3: (4, 6, 10, 18)}  # csrc/ym_conv_stream.hip K steps of 32 per kind
@@ -615,6 +650,35 @@ class GraphBuilder:
         if a["anchor_level"] >= 0:
             return fin
         return fin * a["s"]
+
+
+EMBED_LAYERS = 23  # model.0 .. model.22; model.23 is the head
+DEFAULT_EMBED = (EMBED_LAYERS - 1,)  # Model.embed's default, len(model.model) - 2: the last neck C3k2
+
+
+def normalize_embed(layers) -> Tuple[int, ...]:
+    """predict(embed=...) indices as _predict_once uses them: a set, ascending.  A bare int is one layer.  Unlike
+    upstream (which silently ignores an index no layer has), an index outside 0..22, a non-integer or an empty list
+    is a ValueError."""
+    import operator
+    if isinstance(layers, (str, bytes)) or isinstance(layers, bool):
+        raise ValueError(f"embed: expected layer indices, got {layers!r}")
+    if not isinstance(layers, (list, tuple, set, frozenset)):
+        layers = [layers]
+    out = set()
+    for v in layers:
+        try:
+            if isinstance(v, bool):
+                raise TypeError
+            i = operator.index(v)
+        except TypeError:
+            raise ValueError(f"embed: layer index {v!r} is not an integer") from None
+        if not 0 <= i < EMBED_LAYERS:
+            raise ValueError(f"embed: layer index {i} is outside 0..{EMBED_LAYERS - 1}")
+        out.add(i)
+    if not out:
+        raise ValueError("embed: no layer given")
+    return tuple(sorted(out))
 
 
 def _cls_shift(scale: str) -> float:

@@ -72,6 +72,9 @@ class Engine:
         self._tta = None      # run_tta: [self, pass 1's engine, pass 2's engine]
         self._tta_in = {}     # (pass, B, H, W) -> that pass's scaled input
         self._tta_max = None  # (1,) device word: the batch max of the call
+        self._embed_tables = {}    # embed: layer tuple -> (ym_embed view table, total channels)
+        self._embed_out = {}       # (B, layer tuple) -> the engine-owned (B, sum C) result
+        self._embed_scratch = None  # rows / counts a tuning run of an embed-first shape may write
         self.tune_source: Dict[tuple, str] = {}
 
     def broadcast_weights(self, comm: int, root: int = 0):
@@ -294,6 +297,66 @@ class Engine:
             out = torch.empty((1,), dtype=torch.float32, device=self.device)
         self.rt.input_max(x.data_ptr(), x.numel(), out.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
         return out
+
+    def embed_layers(self):
+        """Layer indices (0..22) whose outputs this plan stores, i.e. the ones embed() can pool.  A plan with fused
+        conv pairs never writes the first conv's output (x3 / f16: model.1 runs inside model.2.cv1's launch)."""
+        return self.graph.embed_layers()
+
+    def _embed_table(self, layers):
+        """(view table, total channels) of a normalised layer tuple, built once."""
+        t = self._embed_tables.get(layers)
+        if t is None:
+            if self.dtype in QUANT_DTYPES:
+                raise ValueError(f"embeddings are not supported for the quantized {self.dtype!r} plans (their stored "
+                                 f"codes need each buffer's scale and zero point); use x3, f16 or f32")
+            views = [(v.buf.id, v.coff, v.C) for i in layers for v in self.graph.layer_views(i)]
+            t = self._embed_tables[layers] = (Runtime.embed_views(views), sum(v[2] for v in views))
+        return t
+
+    def embed(self, x: torch.Tensor, layers=None, out: Optional[torch.Tensor] = None, in_eps=None, use_graph=True,
+              batch_max: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Feature embeddings (Ultralytics _predict_once(embed=layers)): the (B, sum C_i) fp32 device tensor of the
+        named layers' global-average-pooled outputs, concatenated in ascending layer order (a duplicate counts once;
+        default: layer 22, Model.embed's len(model.model) - 2).  The forward stops at the last named layer (no head,
+        decode or NMS; the detection buffers of outputs() are not touched) and the pooling kernel (csrc/ym_embed.hip)
+        reads the plan's own storage.  x, in_eps, batch_max, use_graph as run().  out: the caller's (>= B, >= sum C_i)
+        fp32 rows with unit column stride (default: an engine-owned tensor per (B, layers), overwritten by the next
+        call).  Asynchronous on the current stream; in steady state nothing is allocated.
+        ValueError: an index outside 0..22, a non-integer, an empty list, a layer this plan does not store, or a
+        quantized plan."""
+        from .arch import DEFAULT_EMBED, normalize_embed
+        assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4 and x.shape[1] == 3
+        layers = normalize_embed(DEFAULT_EMBED if layers is None else layers)
+        views, width = self._embed_table(layers)
+        B, _, H, W = x.shape
+        if out is None:
+            out = self._embed_out.get((B, layers))
+            if out is None:
+                out = self._embed_out[(B, layers)] = torch.empty((B, width), dtype=torch.float32, device=self.device)
+        else:
+            assert (out.is_cuda and out.dtype == torch.float32 and out.dim() == 2 and out.shape[0] >= B
+                    and out.shape[1] >= width and out.stride(1) == 1 and out.stride(0) >= width)
+        if in_eps is None:
+            in_eps = torch.finfo(torch.float32).eps
+        bm = 0
+        if batch_max is not None:
+            assert batch_max.is_cuda and batch_max.dtype == torch.float32 and batch_max.numel() >= 1
+            bm = batch_max.data_ptr()
+        akey = ("embed", in_eps, use_graph, bm)
+        args = self._args_cache.get(akey)
+        if args is None:
+            args = self._args_cache[akey] = Runtime.make_args(in_eps=in_eps, use_graph=use_graph, lanes=1,
+                                                              batch_max_ptr=bm)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        if (B, H, W) not in self._tuned:  # the conv tile table of the shape, as run() takes it (one lane)
+            if self._embed_scratch is None or self._embed_scratch[0].shape[0] < B:
+                self._embed_scratch = (torch.zeros((B, args.max_det, 6 + self.nm), dtype=torch.float32,
+                                                   device=self.device),
+                                       torch.zeros((B,), dtype=torch.int32, device=self.device))
+            self._prepare_shape(x, B, H, W, args, self._embed_scratch[0], self._embed_scratch[1], stream)
+        self.rt.embed(x.data_ptr(), B, H, W, args, views, out.data_ptr(), out.stride(0), stream)
+        return out[:B, :width]
 
     def profile(self, x: torch.Tensor, **kw):
         B, _, H, W = x.shape

@@ -40,6 +40,11 @@ class InferArgs(C.Structure):
                 ("d_batch_max", C.c_void_p), ("multi_label", C.c_int), ("reserved", C.c_int * 3)]
 
 
+class EmbedView(C.Structure):
+    """ym_embed_view: channels [coff, coff + C) of plan buffer `buf`."""
+    _fields_ = [("buf", C.c_int), ("coff", C.c_int), ("C", C.c_int), ("reserved", C.c_int)]
+
+
 _lib = None
 
 
@@ -81,6 +86,7 @@ def load_library(path: os.PathLike = LIB_PATH):
         "ym_tta_forward": (I, [P, P, I, I, I, C.POINTER(InferArgs), P]),
         "ym_tta_nms": (I, [C.POINTER(P), I, I, I, C.POINTER(InferArgs), P, P, P]),
         "ym_tta_counts": (I, [P, C.POINTER(I), I]),
+        "ym_embed": (I, [P, P, I, I, I, C.POINTER(InferArgs), C.POINTER(EmbedView), I, P, C.c_longlong, P]),
         "ym_broadcast_weights": (I, [P, P, I, P]),
         "ym_broadcast_weights_local": (I, [C.POINTER(P), I, I, P]),
         "ym_rccl_get_unique_id": (I, [C.POINTER(RcclId)]),
@@ -106,7 +112,7 @@ EXPORTED = ("ym_create", "ym_load_weights", "ym_broadcast_weights", "ym_broadcas
             "ym_letterbox", "ym_profile", "ym_profile_replay", "ym_tune", "ym_get_op_cfg", "ym_set_op_cfg", "ym_num_ops", "ym_op_name",
             "ym_num_buffers", "ym_buffer_info", "ym_read_buffer", "ym_sync", "ym_last_error", "ym_destroy",
             "ym_version", "ym_num_conv_cfgs", "ym_set_debug", "ym_read_scratch", "ym_kpt_shape",
-            "ym_tta_shape", "ym_tta_scale", "ym_tta_forward", "ym_tta_nms", "ym_tta_counts")
+            "ym_tta_shape", "ym_tta_scale", "ym_tta_forward", "ym_tta_nms", "ym_tta_counts", "ym_embed")
 
 DBG_NMS, DBG_DW_MODE, DBG_DW_TILE, DBG_CHAIN, DBG_CHAIN_LAUNCHES, DBG_STEMFUSE, DBG_ATTN_KB = 1, 2, 3, 4, 5, 6, 7
 DBG_PAIRST, DBG_CONV_CFG = 8, 9  # value + 1 (0: default)  # ym_set_debug keys (include/yolomi.h)
@@ -236,6 +242,20 @@ class Runtime:
         arr = (C.c_int * B)()
         _check(self.lib.ym_tta_counts(self.ctx, arr, B))
         return list(arr)
+
+    @staticmethod
+    def embed_views(views):
+        """A ym_embed view table from (buffer id, channel offset, channels) triples."""
+        arr = (EmbedView * len(views))()
+        for a, (buf, coff, ch) in zip(arr, views):
+            a.buf, a.coff, a.C = int(buf), int(coff), int(ch)
+        return arr
+
+    def embed(self, x_ptr: int, B: int, H: int, W: int, args: InferArgs, views, out_ptr: int, out_stride: int,
+              stream: int):
+        """ym_embed: the forward up to the last named buffer, then the pooled means into (B, out_stride) floats."""
+        _check(self.lib.ym_embed(self.ctx, C.c_void_p(x_ptr), B, H, W, C.byref(args), views, len(views),
+                                 C.c_void_p(out_ptr), out_stride, C.c_void_p(stream)))
 
     def profile(self, x_ptr, B, H, W, args, dets_ptr, counts_ptr, stream):
         ms = (C.c_float * self.n_ops)()

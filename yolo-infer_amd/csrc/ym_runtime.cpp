@@ -16,11 +16,13 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/yolomi.h"
 #include "ym_common.h"
 #include "ym_plan.h"
+#include "ym_nms_ws.h"
 #include "ym_embed.h"
 #include "ym_tta.h"
 
@@ -79,8 +81,24 @@ constexpr int kChainCtl = 4096;        // ready counters (+ done, give-up words)
 constexpr float kPresortConf = 0.1f;  // NMS keys presorted over several workgroups below this conf (ym_misc.hip)
 constexpr int kMaxLanes = 4;           // concurrent batch slices in one forward graph (<= GPU_MAX_HW_QUEUES)
 constexpr size_t kMaxGraphs = 16;      // captured forwards cached per context (the oldest is retired first)
-constexpr size_t kMiscBytes = 16384;  // ym_ctx::d_misc
-constexpr int kMlCap = 32768;  // multi-label mode: selected keys per image (max_nms up to this; csrc/ym_nms_ml.hip)
+// ym_ctx::d_misc and its sub-regions: ym_input_max's statistics (slots, ticket, partials), the control words of
+// ym_broadcast_weights, and the words that stand in for the outputs of a forward that writes none (never written)
+constexpr size_t kMiscBytes = 16384;
+constexpr size_t kMiscStats = 0, kMiscBcast = 8192, kMiscNoDets = 12288;
+static_assert(kMiscStats + YM_CTL_BYTES <= kMiscBcast && kMiscBcast + 2 * sizeof(unsigned long long) <= kMiscNoDets &&
+                  kMiscNoDets < kMiscBytes, "the d_misc sub-regions fit in kMiscBytes and do not overlap");
+static_assert(sizeof(MlState) == kMlStateBytes, "ym_nms_ws.h sizes the multi-label state rows");
+
+// What one launch_forward / launch_op call works on.  A value built per call (and per lane or branch stream inside
+// launch_forward), never context state: nothing is left to reset on an early return.
+struct Launch {
+  int lane = 0;           // split-K slab / counter region of the stream the ops go to
+  int img0 = 0;           // first image of the ops being launched (a lane's slice of the batch)
+  int B = 0;              // images of the whole call (all lanes)
+  bool skip_nms = false;  // ym_tta_forward: the passes' candidates are merged first (ym_tta_nms)
+  int stop = -1;          // ym_embed: the last op of the truncated forward (-1: a whole forward)
+  float* const* calib_raw = nullptr;  // ym_calibrate: per-op pre-activation output buffers (f32 plans)
+};
 
 struct GraphKey {
   int B, H, W;
@@ -204,39 +222,33 @@ struct ym_ctx {
   char* d_arena = nullptr;
   size_t arena_bytes = 0;
   std::vector<size_t> buf_off;
-  size_t off_boxes = 0, off_scores = 0, off_cls = 0, off_keys = 0, off_keys2 = 0, off_counts = 0, off_ctl = 0, off_sboxes = 0,
-         off_sareas = 0, off_sup = 0, off_slab = 0, off_cnt = 0, off_chain = 0, off_kpts = 0, slab_bytes = 0;
-  int A = 0, kstride = 0;
-  // multi-label mode (ym_infer_args.multi_label): its scratch joins the arena at the first workspace (re)build after a
-  // multi-label call was seen (check_call sets ml_want), so a context that never validates pays nothing
-  bool ml_want = false, ml_have = false;
-  size_t off_ml_sel = 0, off_ml_sel2 = 0, off_ml_hist = 0, off_ml_state = 0, off_ml_seln = 0;
+  size_t off_ctl = 0, off_slab = 0, off_cnt = 0, off_chain = 0, off_kpts = 0, slab_bytes = 0;
+  int A = 0;
+  // the NMS stage's scratch in the arena.  Multi-label mode (ym_infer_args.multi_label): its regions join at the first
+  // workspace (re)build after a multi-label call was seen (check_call sets ml_want; nms.ml: they are there), so a
+  // context that never validates pays nothing
+  NmsScratch nms;
+  bool ml_want = false;
   int lvl_W[4] = {0}, lvl_off[4] = {0};
   hipStream_t cap_stream = nullptr;
   // lanes: the batch is cut into image slices whose op chains are captured as parallel branches of one graph, so
   // the fixed per-launch latency of one slice's small kernels overlaps the other slices' work
   hipStream_t lane_streams[kMaxLanes] = {};
   hipEvent_t fork_ev = nullptr, join_ev[kMaxLanes] = {};
-  int lane = 0, lane_img0 = 0;  // lane / first image of the ops being launched
-  int call_B = 0;               // images of the forward being launched (all lanes)
   std::vector<GraphEntry> graphs;
-  // test-time augmentation: ym_tta_forward launches the forward without its NMS stage; the merged candidate set and the
-  // NMS scratch over it (ym_tta_nms) belong to the first pass's context and are rebuilt only when the shape changes
-  bool skip_nms = false;
-  // feature embeddings (ym_embed): the forward stops after op embed_stop (-1: a whole forward) and the pooling stage
-  // (csrc/ym_embed.hip) reads embed_views into embed_out; d_embed holds the chunk partials of large maps
-  int embed_stop = -1;
+  // feature embeddings (ym_embed): the forward stops early (Launch::stop) and the pooling stage (csrc/ym_embed.hip)
+  // reads embed_views into embed_out; d_embed holds the chunk partials of large maps
   std::vector<ym_embed_view> embed_views;
   float* embed_out = nullptr;
   long long embed_ld = 0;
   float* d_embed = nullptr;
   size_t embed_floats = 0;
+  // test-time augmentation: ym_tta_forward launches the forward without its NMS stage; the merged candidate set and the
+  // NMS scratch over it (ym_tta_nms) belong to the first pass's context and are rebuilt only when the shape changes
   struct TtaWs {
-    int B = 0, H = 0, W = 0, Am = 0, kstride = 0, nc = 0;
-    bool ml = false;
+    int B = 0, H = 0, W = 0, nc = 0;
     char* d = nullptr;
-    size_t off_boxes = 0, off_scores = 0, off_cls = 0, off_keys = 0, off_keys2 = 0, off_counts = 0, off_sboxes = 0,
-           off_sareas = 0, off_sup = 0, off_rows = 0, off_sel = 0, off_sel2 = 0, off_hist = 0, off_state = 0, off_seln = 0;
+    NmsScratch ws;  // over ws.A merged anchors; multi-label regions and class rows on demand (ws.ml)
   } tta;
   // the previous forward: every forward of a context uses the same arena, NMS scratch, split-K slabs /
   // counters and input_stats ticket, so a forward launched on another stream than the previous one first waits for
@@ -250,12 +262,25 @@ struct ym_ctx {
     }
     return YM_OK;
   }
+  int record_last(hipEvent_t ev, hipStream_t st) {
+    HIPCK(hipEventRecord(ev, st));
+    last_ev = ev;
+    last_st = st;
+    return YM_OK;
+  }
+  int mark_last(hipStream_t st) {  // behind an eager forward (or any other use of the shared scratch) on `st`
+    if (!fwd_ev) HIPCK(hipEventCreateWithFlags(&fwd_ev, hipEventDisableTiming));
+    return record_last(fwd_ev, st);
+  }
+  int launch_graph(GraphEntry& g, hipStream_t st) {
+    HIPCK(hipGraphLaunch(g.exec, st));
+    return record_last(g.done, st);
+  }
   void retire(GraphEntry& g) {  // retire_graph, forgetting last_ev when it is that graph's event (now complete)
     if (g.done && g.done == last_ev) last_ev = nullptr;
     retire_graph(g);
   }
   std::vector<hipEvent_t> prof_events;
-  float* const* calib_raw = nullptr;  // ym_calibrate: per-op pre-activation output buffers (f32 plans)
   // per-shape, per-op conv tile configuration (-1 = heuristic); set by ym_tune / ym_set_op_cfg
   struct ShapeCfg {
     int B, H, W;
@@ -315,22 +340,42 @@ struct ym_ctx {
   template <typename T> const T* wptr(int32_t off) const {  // a record's *_off slot: unsigned bytes into the weights
     return reinterpret_cast<const T*>(d_weights + (size_t)(uint32_t)off);
   }
-  float* raw_of(const Op& op) const { return calib_raw ? calib_raw[&op - ops.data()] : nullptr; }
-  // buffer b of the current lane: its image slice of the whole-batch buffer (all buffers are image-major)
-  void* bptr(int b) const {
-    return d_arena + buf_off[b] + (size_t)lane_img0 * buf_P(b) * bufs[b].C * elem(b);
-  }
-  template <typename T> T* scratch(size_t off, size_t per_image_bytes) const {
-    return reinterpret_cast<T*>(d_arena + off + (size_t)lane_img0 * per_image_bytes);
-  }
+  float* raw_of(const Launch& L, const Op& op) const { return L.calib_raw ? L.calib_raw[&op - ops.data()] : nullptr; }
+  // buffer b from image img0 on: that slice of the whole-batch buffer (all buffers are image-major)
+  void* bptr(int b, int img0) const { return d_arena + buf_off[b] + (size_t)img0 * buf_P(b) * bufs[b].C * elem(b); }
 };
 
 namespace {
 
 size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// Typed pointers into an NmsScratch at `base`, from image img0 on (absent regions: null)
+struct NmsView {
+  float4 *boxes, *sboxes;
+  float *scores, *sareas, *rows;
+  int *cls, *counts, *seln;
+  unsigned long long *keys, *keys2, *sel, *sel2;
+  unsigned char* sup;
+  unsigned int* hist;
+  MlState* state;
+  int A, kstride;
+};
+NmsView nms_view(char* base, const NmsScratch& s, int img0) {
+  NmsView v{};
+  auto set = [&](auto*& p, const NmsRegion& r) {
+    p = r.stride ? reinterpret_cast<std::remove_reference_t<decltype(p)>>(base + r.at(img0)) : nullptr;
+  };
+  set(v.boxes, s.boxes); set(v.scores, s.scores); set(v.cls, s.cls);
+  set(v.keys, s.keys); set(v.keys2, s.keys2); set(v.counts, s.counts);
+  set(v.sboxes, s.sboxes); set(v.sareas, s.sareas); set(v.sup, s.sup);
+  set(v.rows, s.rows);
+  set(v.sel, s.sel); set(v.sel2, s.sel2); set(v.hist, s.hist); set(v.state, s.state); set(v.seln, s.seln);
+  v.A = s.A; v.kstride = s.kstride;
+  return v;
+}
+
 int ensure_workspace(ym_ctx* c, int B, int H, int W) {
-  if (c->d_arena && B <= c->cB && H == c->cH && W == c->cW && (!c->ml_want || c->ml_have)) return YM_OK;
+  if (c->d_arena && B <= c->cB && H == c->cH && W == c->cW && (!c->ml_want || c->nms.ml)) return YM_OK;
   const int nB = (H == c->cH && W == c->cW && B < c->cB) ? c->cB : B;
   c->clear_graphs();
   if (c->d_arena) {
@@ -347,8 +392,6 @@ int ensure_workspace(ym_ctx* c, int B, int H, int W) {
     c->lvl_W[l] = W / c->strides[l];
     c->A += (H / c->strides[l]) * (W / c->strides[l]);
   }
-  c->kstride = 1;
-  while (c->kstride < c->A) c->kstride <<= 1;
   size_t off = 0;
   c->buf_off.assign(c->bufs.size(), 0);
   for (size_t b = 0; b < c->bufs.size(); ++b) {
@@ -356,32 +399,15 @@ int ensure_workspace(ym_ctx* c, int B, int H, int W) {
     if ((int)b == c->input_buf) continue;  // the stem conv reads the caller's NCHW fp32 batch directly
     off = align_up(off + (size_t)nB * c->buf_P((int)b) * c->bufs[b].C * c->elem((int)b), 256);
   }
-  const size_t BA = (size_t)nB * c->A;
-  c->off_boxes = off;  off = align_up(off + BA * 16, 256);
-  c->off_scores = off; off = align_up(off + BA * 4, 256);
-  c->off_cls = off;    off = align_up(off + BA * 4, 256);
-  c->off_keys = off;   off = align_up(off + (size_t)nB * c->kstride * 8, 256);
-  c->off_keys2 = off;  off = align_up(off + (size_t)nB * c->kstride * 8, 256);  // NMS presort chunks
-  c->off_counts = off; off = align_up(off + (size_t)nB * 4, 256);
+  off = nms_scratch_append(c->nms, off, nB, c->A, c->ml_want, 0);
   c->off_ctl = off;    off = align_up(off + YM_CTL_BYTES, 256);
-  c->off_sboxes = off; off = align_up(off + BA * 16, 256);
-  c->off_sareas = off; off = align_up(off + BA * 4, 256);
-  c->off_sup = off;    off = align_up(off + BA, 256);
   // split-K workspace of the LDS-DMA conv kernels: fp32 partial tiles + per-tile arrival counters
   c->slab_bytes = std::min<size_t>(std::max<size_t>(32u << 20, (size_t)nB << 22), 1u << 30);
   c->off_slab = off;   off = align_up(off + kMaxLanes * c->slab_bytes, 256);  // one slab region per lane
   c->off_cnt = off;    off = align_up(off + (size_t)kMaxLanes * kSplitCounters * 4, 256);
   c->off_chain = off;  off = align_up(off + (size_t)kChainCtl * 4, 256);  // persistent chain kernel's counters
   c->off_kpts = off;  // pose plans: decoded keypoints (B, A, nm) fp32, the rows NMS takes its extras from
-  if (c->task == kTaskPose) off = align_up(off + BA * c->nm * 4, 256);
-  c->ml_have = c->ml_want;
-  if (c->ml_have) {  // B * max_nms-scaled: two key rows, the select histogram and state per image
-    c->off_ml_sel = off;   off = align_up(off + (size_t)nB * kMlCap * 8, 256);
-    c->off_ml_sel2 = off;  off = align_up(off + (size_t)nB * kMlCap * 8, 256);
-    c->off_ml_hist = off;  off = align_up(off + (size_t)nB * 1024 * 4, 256);
-    c->off_ml_state = off; off = align_up(off + (size_t)nB * sizeof(MlState), 256);
-    c->off_ml_seln = off;  off = align_up(off + (size_t)nB * 4, 256);
-  }
+  if (c->task == kTaskPose) off = align_up(off + (size_t)nB * c->A * c->nm * 4, 256);
   c->arena_bytes = off;
   hipError_t e = hipMalloc(&c->d_arena, off);
   if (e != hipSuccess) {
@@ -394,7 +420,8 @@ int ensure_workspace(ym_ctx* c, int B, int H, int W) {
 }
 
 // Kernel arguments of a conv op for batch B at the current workspace shape.
-int conv_args(ym_ctx* c, const Op& op, int B, const float* d_in, float in_eps, ConvArgs& a, int& out_f32) {
+int conv_args(ym_ctx* c, const Launch& L, const Op& op, int B, const float* d_in, float in_eps, ConvArgs& a,
+              int& out_f32) {
   a = ConvArgs{};
   a.wsc = a.wsc2 = 1.0f;
   const int pst = ym_debug_get(YM_DBG_PAIRST);  // (value + 1; 0: the default family mask 21)
@@ -402,7 +429,7 @@ int conv_args(ym_ctx* c, const Op& op, int B, const float* d_in, float in_eps, C
   const int k = op.k, s = op.s, cin = op.cin, cout = op.n;
   const int b0 = op.src0, b1 = op.src1, bd = op.dst, br = op.res;
   const int up0 = op.up0;
-  a.src0 = c->bptr(b0); a.s0_ctot = c->bufs[b0].C; a.s0_coff = op.src0_coff; a.C0 = op.c0;
+  a.src0 = c->bptr(b0, L.img0); a.s0_ctot = c->bufs[b0].C; a.s0_coff = op.src0_coff; a.C0 = op.c0;
   if (b0 == c->input_buf) {  // stem: NCHW fp32 source, LoadTensor /255 decided on device from ctl[0]
     a.src0 = nullptr;
     a.nchw = d_in;
@@ -414,7 +441,8 @@ int conv_args(ym_ctx* c, const Op& op, int B, const float* d_in, float in_eps, C
   a.Hin = c->buf_H(b0) * (up0 ? 2 : 1);
   a.Win = c->buf_Wd(b0) * (up0 ? 2 : 1);
   if (b1 >= 0) {
-    a.src1 = c->bptr(b1); a.s1_ctot = c->bufs[b1].C; a.s1_coff = op.src1_coff; a.C1 = op.c1; a.s1_P = c->buf_P(b1);
+    a.src1 = c->bptr(b1, L.img0); a.s1_ctot = c->bufs[b1].C; a.s1_coff = op.src1_coff; a.C1 = op.c1;
+    a.s1_P = c->buf_P(b1);
     if (c->buf_H(b1) != a.Hin || c->buf_Wd(b1) != a.Win)
       return fail(YM_EBLOB, "op %s: concat sources disagree in shape", op.name);
   }
@@ -473,7 +501,7 @@ int conv_args(ym_ctx* c, const Op& op, int B, const float* d_in, float in_eps, C
   }
   a.shuffle = op.shuffle;
   a.npr = a.shuffle ? cout / 4 : cout;
-  a.dst = c->bptr(bd); a.d_ctot = c->bufs[bd].C; a.d_coff = op.dst_coff; a.d_P = c->buf_P(bd);
+  a.dst = c->bptr(bd, L.img0); a.d_ctot = c->bufs[bd].C; a.d_coff = op.dst_coff; a.d_P = c->buf_P(bd);
   const int lvl = op.level;
   if (lvl >= 0) {
     a.d_pixoff = c->lvl_off[lvl];
@@ -487,19 +515,19 @@ int conv_args(ym_ctx* c, const Op& op, int B, const float* d_in, float in_eps, C
       return fail(YM_EBLOB, "op %s: output %dx%d does not match dst buffer %dx%d", op.name, a.Ho, a.Wo,
                   c->buf_H(bd), c->buf_Wd(bd));
   }
-  if (br >= 0) { a.res = c->bptr(br); a.r_ctot = c->bufs[br].C; a.r_coff = op.res_coff; a.r_P = c->buf_P(br); }
+  if (br >= 0) { a.res = c->bptr(br, L.img0); a.r_ctot = c->bufs[br].C; a.r_coff = op.res_coff; a.r_P = c->buf_P(br); }
   a.M = B * a.Ho * a.Wo;
   a.fd_hw = ym_fdiv(a.Ho * a.Wo);
   a.fd_w = ym_fdiv(a.Wo);
   out_f32 = c->bufs[bd].f32 && c->dtype != YM_DT_F32;  // (x3: fp32 head rows, pair-layout activations)
-  a.raw = c->raw_of(op);
+  a.raw = c->raw_of(L, op);
   // operand extents in storage elements (the LDS-DMA buffer descriptors): fp16 halves of the x3 pairs
   const long xs = a.x3 ? 2 : 1;
   a.s0_elems = (b0 == c->input_buf) ? 0 : xs * c->cB * c->buf_P(b0) * c->bufs[b0].C;
   a.s1_elems = b1 >= 0 ? xs * c->cB * c->buf_P(b1) * c->bufs[b1].C : 0;
-  a.slab = reinterpret_cast<float*>(c->d_arena + c->off_slab + (size_t)c->lane * c->slab_bytes);
+  a.slab = reinterpret_cast<float*>(c->d_arena + c->off_slab + (size_t)L.lane * c->slab_bytes);
   a.slab_cap = (long)c->slab_bytes;
-  a.cnt = reinterpret_cast<int*>(c->d_arena + c->off_cnt) + (size_t)c->lane * kSplitCounters;
+  a.cnt = reinterpret_cast<int*>(c->d_arena + c->off_cnt) + (size_t)L.lane * kSplitCounters;
   a.cnt_cap = kSplitCounters;
   static const int pf_max = [] { const char* e = getenv("YM_DMA_PF"); return e ? atoi(e) : 0; }();
   a.pf = a.M <= pf_max;
@@ -509,15 +537,15 @@ int conv_args(ym_ctx* c, const Op& op, int B, const float* d_in, float in_eps, C
 // A fused pair (ConvArgs::w2) run as its two convs: A writes the intermediate buffer (the record's `mid`), B reads it.
 // The tuner picks this when the two tuned single launches beat every fused variant (op cfg kSplitTag + ...).
 constexpr int kSplitTag = 1 << 20;  // op cfg = kSplitTag + 256 * cfg(A) + cfg(B)
-void split_args(ym_ctx* c, const Op& op, const ConvArgs& a, ConvArgs& A, ConvArgs& Bc) {
+void split_args(ym_ctx* c, const Launch& L, const Op& op, const ConvArgs& a, ConvArgs& A, ConvArgs& Bc) {
   const int mid = op.mid;
   A = a;
   A.w2 = nullptr; A.bias2 = nullptr; A.res = nullptr;
-  A.dst = c->bptr(mid); A.d_ctot = c->bufs[mid].C; A.d_coff = 0; A.d_P = c->buf_P(mid); A.d_pixoff = 0;
+  A.dst = c->bptr(mid, L.img0); A.d_ctot = c->bufs[mid].C; A.d_coff = 0; A.d_P = c->buf_P(mid); A.d_pixoff = 0;
   A.d_W = c->buf_Wd(mid);
   Bc = a;
   Bc.w2 = nullptr; Bc.bias2 = nullptr;
-  Bc.src0 = c->bptr(mid); Bc.s0_ctot = c->bufs[mid].C; Bc.s0_coff = 0; Bc.C0 = a.N; Bc.s0_W = c->buf_Wd(mid);
+  Bc.src0 = c->bptr(mid, L.img0); Bc.s0_ctot = c->bufs[mid].C; Bc.s0_coff = 0; Bc.C0 = a.N; Bc.s0_W = c->buf_Wd(mid);
   Bc.s0_P = c->buf_P(mid); Bc.up0 = 0;
   Bc.src1 = nullptr; Bc.C1 = 0; Bc.s1_elems = 0;
   Bc.Hin = a.Ho; Bc.Win = a.Wo; Bc.k = a.k2; Bc.s = 1; Bc.pad = a.k2 / 2;
@@ -527,27 +555,73 @@ void split_args(ym_ctx* c, const Op& op, const ConvArgs& a, ConvArgs& A, ConvArg
   Bc.s0_elems = (long)xs * c->cB * c->buf_P(mid) * c->bufs[mid].C;
 }
 
-hipError_t launch_fused(ym_ctx* c, const Op& op, const ConvArgs& a, int out_f32, int cfg, hipStream_t st) {
+hipError_t launch_fused(ym_ctx* c, const Launch& L, const Op& op, const ConvArgs& a, int out_f32, int cfg,
+                        hipStream_t st) {
   if (cfg < kSplitTag) {
     const hipError_t e = ym_launch_conv(c->dtype, out_f32, a, cfg, st);
     if (e != hipErrorInvalidValue) return e;
     cfg = kSplitTag + 256 * 255 + 255;  // no fused kernel takes this shape (e.g. a map width the Bottleneck kernel
   }                                     // does not tile): the two convs with their heuristic tiles
   ConvArgs A, Bc;
-  split_args(c, op, a, A, Bc);
+  split_args(c, L, op, a, A, Bc);
   const hipError_t e = ym_launch_conv(c->dtype, 0, A, ((cfg - kSplitTag) >> 8) & 255, st);
   return e != hipSuccess ? e : ym_launch_conv(c->dtype, out_f32, Bc, (cfg - kSplitTag) & 255, st);
 }
 
-int launch_op(ym_ctx* c, const Op& op, int B, const float* d_in, const ym_infer_args* args, float* d_dets,
-              int* d_counts, hipStream_t st) {
+// Where an NMS stage reads per-candidate rows: the nm extras the NMS kernel copies behind each kept box, and the
+// class scores the multi-label candidate stage thresholds (both (B, A, *_ld) fp32; null: none)
+struct NmsSource {
+  const float* extras; int extras_ld, mask_off;
+  const float* cls; int cls_ld, cls_off;
+};
+
+// The NMS stage over B images of the candidates in `v` (decode_anchors' or the TTA merge's): single-label, with the
+// keys presorted at low conf, or multi-label.  The forward's OP_NMS and ym_tta_nms both end here.
+hipError_t launch_nms_stage(const NmsView& v, const NmsSource& src, const ym_infer_args* args, int B, int nc, int nm,
+                            int H, int W, float* dets, int* out_counts, int* counts2, hipStream_t st) {
+  NmsArgs a{};
+  a.anchors = src.extras; a.no_tot = src.extras_ld; a.mask_off = src.mask_off;
+  a.boxes = v.boxes; a.scores = v.scores; a.cls = v.cls; a.keys = v.keys; a.counts = v.counts;
+  a.sboxes = v.sboxes; a.sareas = v.sareas; a.sup = v.sup;
+  a.dets = dets; a.out_counts = out_counts; a.counts2 = counts2;
+  a.A = v.A; a.kstride = v.kstride; a.nm = nm; a.max_det = args->max_det; a.max_nms = args->max_nms;
+  a.agnostic = args->agnostic; a.B = B; a.nc = nc;
+  a.max_wh = args->max_wh; a.img_h = (float)H; a.img_w = (float)W;
+  a.iou = args->iou;
+  if (args->multi_label && nc > 1) {
+    // every (anchor, class) pair above conf: candidates, the max_nms best, their sort and the NMS in
+    // csrc/ym_nms_ml.hip (the boxes are written; the single-label keys go unused)
+    MlArgs m{};
+    m.anchors = src.cls; m.no_tot = src.cls_ld; m.cls_off = src.cls_off;
+    m.A = v.A; m.nc = nc; m.B = B;
+    m.conf = args->conf; m.has_classes = args->has_classes;
+    for (int i = 0; i < 4; ++i) m.classes[i] = args->classes[i];
+    m.max_nms = args->max_nms; m.cap = kMlCap;
+    m.counts = v.counts; m.hist = v.hist; m.state = v.state; m.sel = v.sel; m.sel2 = v.sel2; m.seln = v.seln;
+    a.keys = m.sel; a.kstride = kMlCap; a.counts = m.seln;
+    a.scores = nullptr; a.cls = nullptr;
+    return ym_launch_nms_ml(m, a, st);
+  }
+  // low conf (the validator's 0.001): thousands of candidates per image; sort their keys over several
+  // workgroups per image first (conf is part of the graph key: the predict default 0.25 never launches these)
+  if (args->conf < kPresortConf && v.kstride >= 16384) {
+    a.keys2 = v.keys2;
+    a.presorted = 1;
+    const hipError_t e = ym_launch_nms_presort(a, st);
+    if (e != hipSuccess) return e;
+  }
+  return ym_launch_nms(a, st);
+}
+
+int launch_op(ym_ctx* c, const Launch& L, const Op& op, int B, const float* d_in, const ym_infer_args* args,
+              float* d_dets, int* d_counts, hipStream_t st) {
   const int dt = c->dtype;
   hipError_t e = hipSuccess;
   switch (op.kind) {
     case OP_INPUT: {
       PrepArgs a{};
       a.in = d_in;
-      a.out = c->bptr(c->input_buf);
+      a.out = c->bptr(c->input_buf, L.img0);
       a.ctl = reinterpret_cast<float*>(c->d_arena + c->off_ctl);
       a.B = B; a.C = 3; a.H = c->cH; a.W = c->cW;
       a.eps = args->in_eps;
@@ -555,24 +629,24 @@ int launch_op(ym_ctx* c, const Op& op, int B, const float* d_in, const ym_infer_
       a.cnt = reinterpret_cast<int*>(c->d_arena + c->off_cnt);
       a.cnt_len = kMaxLanes * kSplitCounters;
       // (ym_embed runs no decode: the previous forward's candidate counts stay as they are)
-      e = ym_launch_prep(dt, a, reinterpret_cast<int*>(c->d_arena + c->off_counts), c->embed_stop >= 0 ? 0 : B, st);
+      e = ym_launch_prep(dt, a, nms_view(c->d_arena, c->nms, 0).counts, L.stop >= 0 ? 0 : B, st);
       break;
     }
     case OP_CONV: {
       ConvArgs a{};
       int out_f32 = 0;
-      const int rc = conv_args(c, op, B, d_in, args->in_eps, a, out_f32);
+      const int rc = conv_args(c, L, op, B, d_in, args->in_eps, a, out_f32);
       if (rc) return rc;
       const int cfg = c->op_cfg(&op - c->ops.data(), B);
       e = a.nchw ? ym_launch_stem(dt, a, st)
-                 : (a.w2 ? launch_fused(c, op, a, out_f32, cfg, st) : ym_launch_conv(dt, out_f32, a, cfg, st));
+                 : (a.w2 ? launch_fused(c, L, op, a, out_f32, cfg, st) : ym_launch_conv(dt, out_f32, a, cfg, st));
       break;
     }
     case OP_DW: {
       DwArgs a{};
       const int bs = op.src0, bd = op.dst;
-      a.src = c->bptr(bs); a.s_ctot = c->bufs[bs].C; a.s_coff = op.src0_coff; a.s_P = c->buf_P(bs);
-      a.dst = c->bptr(bd); a.d_ctot = c->bufs[bd].C; a.d_coff = op.dst_coff; a.d_P = c->buf_P(bd);
+      a.src = c->bptr(bs, L.img0); a.s_ctot = c->bufs[bs].C; a.s_coff = op.src0_coff; a.s_P = c->buf_P(bs);
+      a.dst = c->bptr(bd, L.img0); a.d_ctot = c->bufs[bd].C; a.d_coff = op.dst_coff; a.d_P = c->buf_P(bd);
       a.w = c->wptr<float>(op.w_off);
       a.bias = c->wptr<float>(op.b_off);
       a.C = op.cin; a.act = op.act; a.H = c->buf_H(bs); a.W = c->buf_Wd(bs); a.B = B;
@@ -582,14 +656,14 @@ int launch_op(ym_ctx* c, const Op& op, int B, const float* d_in, const ym_infer_
         a.q = c->wptr<QRec>(op.q_off);
         a.sasw = c->wptr<float>(op.sasw_off);
       }
-      a.raw = c->raw_of(op);
+      a.raw = c->raw_of(L, op);
       e = ym_launch_dwconv(dt, a, st);
       break;
     }
     case OP_SPPF: {
       PoolArgs a{};
       const int bb = op.sppf_buf();
-      a.buf = c->bptr(bb); a.ctot = c->bufs[bb].C; a.coff = op.sppf_coff(); a.P = c->buf_P(bb);
+      a.buf = c->bptr(bb, L.img0); a.ctot = c->bufs[bb].C; a.coff = op.sppf_coff(); a.P = c->buf_P(bb);
       a.C = op.cin; a.H = c->buf_H(bb); a.W = c->buf_Wd(bb); a.B = B;
       e = ym_launch_sppf(dt, a, st);
       break;
@@ -597,8 +671,8 @@ int launch_op(ym_ctx* c, const Op& op, int B, const float* d_in, const ym_infer_
     case OP_ATTN: {
       AttnArgs a{};
       const int bq = op.src0, bd = op.dst;
-      a.qkv = c->bptr(bq); a.q_ctot = c->bufs[bq].C; a.q_coff = op.src0_coff; a.q_P = c->buf_P(bq);
-      a.dst = c->bptr(bd); a.d_ctot = c->bufs[bd].C; a.d_coff = op.dst_coff; a.d_P = c->buf_P(bd);
+      a.qkv = c->bptr(bq, L.img0); a.q_ctot = c->bufs[bq].C; a.q_coff = op.src0_coff; a.q_P = c->buf_P(bq);
+      a.dst = c->bptr(bd, L.img0); a.d_ctot = c->bufs[bd].C; a.d_coff = op.dst_coff; a.d_P = c->buf_P(bd);
       a.pe_w = c->wptr<float>(op.w_off);
       a.pe_b = c->wptr<float>(op.b_off);
       a.C = op.cin; a.nh = op.attn_nh(); a.kd = op.attn_kd(); a.hd = op.attn_hd();
@@ -610,7 +684,7 @@ int launch_op(ym_ctx* c, const Op& op, int B, const float* d_in, const ym_infer_
         a.q = c->wptr<QRec>(op.q_off);
         a.pe_sasw = c->wptr<float>(op.sasw_off);
       }
-      a.raw = c->raw_of(op);
+      a.raw = c->raw_of(L, op);
       e = ym_launch_attn(dt, a, st);
       break;
     }
@@ -618,10 +692,10 @@ int launch_op(ym_ctx* c, const Op& op, int B, const float* d_in, const ym_infer_
       if (!ym_dt_q8(dt)) return fail(YM_EBLOB, "op %s: requant in a non-quantized plan", op.name);
       ReqArgs a{};
       const int bs = op.src0, bd = op.dst;
-      a.src = static_cast<const i8*>(c->bptr(bs)); a.s_ctot = c->bufs[bs].C; a.s_coff = op.src0_coff; a.s_P = c->buf_P(bs);
-      a.s_W = c->buf_Wd(bs); a.up = op.req_up();
-      a.dst = static_cast<i8*>(c->bptr(bd)); a.d_ctot = c->bufs[bd].C; a.d_coff = op.dst_coff; a.d_P = c->buf_P(bd);
-      a.d_W = c->buf_Wd(bd);
+      a.src = static_cast<const i8*>(c->bptr(bs, L.img0)); a.s_ctot = c->bufs[bs].C; a.s_coff = op.src0_coff;
+      a.s_P = c->buf_P(bs); a.s_W = c->buf_Wd(bs); a.up = op.req_up();
+      a.dst = static_cast<i8*>(c->bptr(bd, L.img0)); a.d_ctot = c->bufs[bd].C; a.d_coff = op.dst_coff;
+      a.d_P = c->buf_P(bd); a.d_W = c->buf_Wd(bd);
       a.C = op.cin; a.H = c->buf_H(bd); a.W = c->buf_Wd(bd); a.B = B;
       if (c->buf_H(bs) * (a.up ? 2 : 1) != a.H || a.s_W * (a.up ? 2 : 1) != a.W)
         return fail(YM_EBLOB, "op %s: requant source/destination shapes disagree", op.name);
@@ -630,15 +704,12 @@ int launch_op(ym_ctx* c, const Op& op, int B, const float* d_in, const ym_infer_
       break;
     }
     case OP_DECODE: {
+      const NmsView v = nms_view(c->d_arena, c->nms, L.img0);
       DecodeArgs a{};
-      a.anchors = reinterpret_cast<const float*>(c->bptr(c->anchor_buf));
+      a.anchors = reinterpret_cast<const float*>(c->bptr(c->anchor_buf, L.img0));
       a.no_tot = c->bufs[c->anchor_buf].C;
-      a.boxes = c->scratch<float4>(c->off_boxes, (size_t)c->A * 16);
-      a.scores = c->scratch<float>(c->off_scores, (size_t)c->A * 4);
-      a.cls = c->scratch<int>(c->off_cls, (size_t)c->A * 4);
-      a.keys = c->scratch<unsigned long long>(c->off_keys, (size_t)c->kstride * 8);
-      a.counts = c->scratch<int>(c->off_counts, 4);
-      a.A = c->A; a.kstride = c->kstride; a.nc = c->nc; a.reg_max = c->reg_max; a.B = B; a.nl = c->nl;
+      a.boxes = v.boxes; a.scores = v.scores; a.cls = v.cls; a.keys = v.keys; a.counts = v.counts;
+      a.A = v.A; a.kstride = v.kstride; a.nc = c->nc; a.reg_max = c->reg_max; a.B = B; a.nl = c->nl;
       for (int l = 0; l < c->nl; ++l) {
         a.lvl_W[l] = c->lvl_W[l]; a.lvl_off[l] = c->lvl_off[l]; a.lvl_stride[l] = (float)c->strides[l];
       }
@@ -649,75 +720,31 @@ int launch_op(ym_ctx* c, const Op& op, int B, const float* d_in, const ym_infer_
       break;
     }
     case OP_NMS: {
-      if (c->skip_nms) break;  // ym_tta_forward: the passes' candidates are merged first (ym_tta_nms)
-      NmsArgs a{};
-      a.anchors = reinterpret_cast<const float*>(c->bptr(c->anchor_buf));
-      a.no_tot = c->bufs[c->anchor_buf].C;
-      a.mask_off = c->no;
-      a.boxes = c->scratch<const float4>(c->off_boxes, (size_t)c->A * 16);
-      a.scores = c->scratch<const float>(c->off_scores, (size_t)c->A * 4);
-      a.cls = c->scratch<const int>(c->off_cls, (size_t)c->A * 4);
-      a.keys = c->scratch<unsigned long long>(c->off_keys, (size_t)c->kstride * 8);
-      a.counts = c->scratch<const int>(c->off_counts, 4);
-      a.sboxes = c->scratch<float4>(c->off_sboxes, (size_t)c->A * 16);
-      a.sareas = c->scratch<float>(c->off_sareas, (size_t)c->A * 4);
-      a.sup = c->scratch<unsigned char>(c->off_sup, (size_t)c->A);
-      a.dets = d_dets;
-      a.out_counts = d_counts;
-      // counts_after_dets: this lane's images' words behind the WHOLE batch's rows (lane_img0: d_dets is the lane's)
-      a.counts2 = args->counts_after_dets
-                      ? reinterpret_cast<int*>(d_dets + (size_t)(c->call_B - c->lane_img0) * args->max_det * (6 + c->nm)) +
-                            c->lane_img0
-                      : nullptr;
-      a.A = c->A; a.kstride = c->kstride; a.nm = c->nm; a.max_det = args->max_det; a.max_nms = args->max_nms;
-      a.agnostic = args->agnostic; a.B = B; a.nc = c->nc;
-      a.max_wh = args->max_wh; a.img_h = (float)c->cH; a.img_w = (float)c->cW;
-      a.iou = args->iou;
+      if (L.skip_nms) break;
+      const NmsView v = nms_view(c->d_arena, c->nms, L.img0);
+      const float* rows = reinterpret_cast<const float*>(c->bptr(c->anchor_buf, L.img0));
+      const int no_tot = c->bufs[c->anchor_buf].C;
+      NmsSource src{rows, no_tot, c->no, rows, no_tot, 4 * c->reg_max};
       if (c->task == kTaskPose) {
         // Pose: decode the candidates' keypoints (behind decode_anchors, before any NMS kernel) into their own
         // (B, A, nm) rows and let NMS carry its nm extras from there; the raw head rows stay as the convs wrote them
         KptArgs k{};
-        k.anchors = a.anchors; k.no_tot = a.no_tot; k.kpt_off = c->kpt_off;
-        k.keys = a.keys; k.counts = a.counts;
-        k.out = c->scratch<float>(c->off_kpts, (size_t)c->A * c->nm * 4);
-        k.nk_pad = c->nm; k.A = c->A; k.kstride = c->kstride; k.K = c->kpt_K; k.ndim = c->kpt_ndim; k.B = B;
+        k.anchors = rows; k.no_tot = no_tot; k.kpt_off = c->kpt_off;
+        k.keys = v.keys; k.counts = v.counts;
+        k.out = reinterpret_cast<float*>(c->d_arena + c->off_kpts) + (size_t)L.img0 * c->A * c->nm;
+        k.nk_pad = c->nm; k.A = v.A; k.kstride = v.kstride; k.K = c->kpt_K; k.ndim = c->kpt_ndim; k.B = B;
         k.nl = c->nl;
         for (int l = 0; l < c->nl; ++l) {
           k.lvl_W[l] = c->lvl_W[l]; k.lvl_off[l] = c->lvl_off[l]; k.lvl_stride[l] = (float)c->strides[l];
         }
         e = ym_launch_kpts(k, st);
         if (e != hipSuccess) break;
-        a.anchors = k.out; a.no_tot = c->nm; a.mask_off = 0;
+        src.extras = k.out; src.extras_ld = c->nm; src.mask_off = 0;
       }
-      if (args->multi_label && c->nc > 1) {
-        // every (anchor, class) pair above conf: candidates, the max_nms best, their sort and the NMS in
-        // csrc/ym_nms_ml.hip (decode_anchors has written the boxes; its own keys go unused)
-        MlArgs m{};
-        m.anchors = a.anchors; m.no_tot = a.no_tot; m.cls_off = 4 * c->reg_max;
-        m.A = c->A; m.nc = c->nc; m.B = B;
-        m.conf = args->conf; m.has_classes = args->has_classes;
-        for (int i = 0; i < 4; ++i) m.classes[i] = args->classes[i];
-        m.max_nms = args->max_nms; m.cap = kMlCap;
-        m.counts = c->scratch<int>(c->off_counts, 4);
-        m.hist = c->scratch<unsigned int>(c->off_ml_hist, 1024 * 4);
-        m.state = c->scratch<MlState>(c->off_ml_state, sizeof(MlState));
-        m.sel = c->scratch<unsigned long long>(c->off_ml_sel, (size_t)kMlCap * 8);
-        m.sel2 = c->scratch<unsigned long long>(c->off_ml_sel2, (size_t)kMlCap * 8);
-        m.seln = c->scratch<int>(c->off_ml_seln, 4);
-        a.keys = m.sel; a.kstride = kMlCap; a.counts = m.seln;
-        a.scores = nullptr; a.cls = nullptr;
-        e = ym_launch_nms_ml(m, a, st);
-        break;
-      }
-      // low conf (the validator's 0.001): thousands of candidates per image; sort their keys over several
-      // workgroups per image first (conf is part of the graph key: the predict default 0.25 never launches these)
-      if (args->conf < kPresortConf && c->kstride >= 16384) {
-        a.keys2 = c->scratch<unsigned long long>(c->off_keys2, (size_t)c->kstride * 8);
-        a.presorted = 1;
-        e = ym_launch_nms_presort(a, st);
-        if (e != hipSuccess) break;
-      }
-      e = ym_launch_nms(a, st);
+      // counts_after_dets: this lane's images' words behind the WHOLE batch's rows (d_dets is the lane's)
+      const size_t rows_left = (size_t)(L.B - L.img0) * args->max_det * (6 + c->nm);
+      int* counts2 = args->counts_after_dets ? reinterpret_cast<int*>(d_dets + rows_left) + L.img0 : nullptr;
+      e = launch_nms_stage(v, src, args, B, c->nc, c->nm, c->cH, c->cW, d_dets, d_counts, counts2, st);
       break;
     }
     default:
@@ -727,27 +754,71 @@ int launch_op(ym_ctx* c, const Op& op, int B, const float* d_in, const ym_infer_
   return YM_OK;
 }
 
+// B images of H x W; `who`: the message's prefix ("" or "entry point: ")
+int check_shape(int B, int H, int W, const char* who) {
+  if (B < 1 || H < 32 || W < 32 || H % 32 || W % 32)
+    return fail(YM_EINVAL, "%sinput shape (%d,3,%d,%d): H and W must be positive multiples of 32", who, B, H, W);
+  return YM_OK;
+}
+
+int check_nms_args(const ym_infer_args* args, int nc, int task) {
+  if (args->max_det < 1 || args->max_nms < 1) return fail(YM_EINVAL, "max_det/max_nms must be >= 1");
+  if (args->max_det > 1024) return fail(YM_EINVAL, "max_det %d > 1024 is not supported", args->max_det);
+  if (args->counts_after_dets != 0 && args->counts_after_dets != 1) return fail(YM_EINVAL, "counts_after_dets is 0 or 1");
+  if (args->multi_label != 0 && args->multi_label != 1) return fail(YM_EINVAL, "multi_label is 0 or 1");
+  if (args->multi_label && nc > 1) {  // (nc == 1: the single-label path, as upstream's multi_label &= nc > 1)
+    if (task != 0)
+      return fail(YM_EINVAL, "multi_label: %s plans are not supported (validation mode is for detect plans)",
+                  ym_task_name(task));
+    if (nc > 128) return fail(YM_EINVAL, "multi_label: nc %d > 128 is not supported", nc);
+    if (args->max_nms > kMlCap) return fail(YM_EINVAL, "multi_label: max_nms %d > %d is not supported", args->max_nms, kMlCap);
+  }
+  return YM_OK;
+}
+
 int check_call(ym_ctx* c, const float* d_in, int B, int H, int W, const ym_infer_args* args, float* d_dets,
                int* d_counts) {
   if (!c) return fail(YM_EINVAL, "null context");
   if (!c->loaded) return fail(YM_ESTATE, "ym_infer before ym_load_weights");
   if (!d_in || !d_dets || !d_counts || !args) return fail(YM_EINVAL, "null pointer argument");
-  if (B < 1 || H < 32 || W < 32 || H % 32 || W % 32)
-    return fail(YM_EINVAL, "input shape (%d,3,%d,%d): H and W must be positive multiples of 32", B, H, W);
-  if (args->max_det < 1 || args->max_nms < 1) return fail(YM_EINVAL, "max_det/max_nms must be >= 1");
-  if (args->max_det > 1024) return fail(YM_EINVAL, "max_det %d > 1024 is not supported", args->max_det);
-  if (args->counts_after_dets != 0 && args->counts_after_dets != 1) return fail(YM_EINVAL, "counts_after_dets is 0 or 1");
-  if (args->multi_label != 0 && args->multi_label != 1) return fail(YM_EINVAL, "multi_label is 0 or 1");
-  if (args->multi_label && c->nc > 1) {  // (nc == 1: the single-label path, as upstream's multi_label &= nc > 1)
-    if (c->task != 0)
-      return fail(YM_EINVAL, "multi_label: %s plans are not supported (validation mode is for detect plans)",
-                  ym_task_name(c->task));
-    if (c->nc > 128) return fail(YM_EINVAL, "multi_label: nc %d > 128 is not supported", c->nc);
-    if (args->max_nms > kMlCap) return fail(YM_EINVAL, "multi_label: max_nms %d > %d is not supported", args->max_nms, kMlCap);
-    c->ml_want = true;
-  }
-  c->call_B = B;  // (launch_forward sets it again; eager per-op paths launch the NMS op directly)
+  if (int rc = check_shape(B, H, W, "")) return rc;
+  if (int rc = check_nms_args(args, c->nc, c->task)) return rc;
+  if (args->multi_label && c->nc > 1) c->ml_want = true;
   return YM_OK;
+}
+
+// `reps` calls of launch(stream) captured on the private stream as one graph, replayed on `st`: once warm, then
+// `timed` times between two events (device-bound even for tiny kernels).  Returns a HIP failure as YM_EHIP; else
+// launch_rc is the first non-zero result of `launch` (nothing was replayed) or 0 with the timed replays' total in ms.
+// Graph, exec and events are destroyed on every path.
+template <typename F>
+int time_captured(ym_ctx* c, hipStream_t st, int reps, int timed, F&& launch, int& launch_rc, float& ms) {
+  hipGraph_t g = nullptr;
+  hipGraphExec_t ge = nullptr;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  launch_rc = 0;
+  hipError_t e = hipStreamBeginCapture(c->cap_stream, hipStreamCaptureModeRelaxed);
+  if (e == hipSuccess) {
+    for (int r = 0; r < reps && launch_rc == 0; ++r) launch_rc = launch(c->cap_stream);
+    e = hipStreamEndCapture(c->cap_stream, &g);  // (always: the capture must not stay open)
+  }
+  if (e == hipSuccess && launch_rc == 0) {
+    e = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
+    if (e == hipSuccess) e = hipEventCreate(&e0);
+    if (e == hipSuccess) e = hipEventCreate(&e1);
+    if (e == hipSuccess) e = hipGraphLaunch(ge, st);  // warm
+    if (e == hipSuccess) e = hipEventRecord(e0, st);
+    for (int r = 0; r < timed && e == hipSuccess; ++r) e = hipGraphLaunch(ge, st);
+    if (e == hipSuccess) e = hipEventRecord(e1, st);
+    if (e == hipSuccess) e = hipEventSynchronize(e1);
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+  }
+  if (e1) (void)hipEventDestroy(e1);
+  if (e0) (void)hipEventDestroy(e0);
+  if (ge) (void)hipGraphExecDestroy(ge);
+  if (g) (void)hipGraphDestroy(g);
+  if (launch_rc != 0) return YM_OK;  // (the caller skips or reports it)
+  return e == hipSuccess ? YM_OK : fail(YM_EHIP, "timed graph replay: %s", hipGetErrorString(e));
 }
 
 }  // namespace
@@ -779,7 +850,6 @@ int ym_create(int device, const ym_model_desc* desc, ym_ctx** out) {
   hipError_t e = hipStreamCreateWithFlags(&c->cap_stream, hipStreamNonBlocking);
   for (int l = 1; l < kMaxLanes && e == hipSuccess; ++l) e = hipStreamCreateWithFlags(&c->lane_streams[l], hipStreamNonBlocking);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&c->fork_ev, hipEventDisableTiming);
-  // ym_input_max's ctl region (slots, ticket, partials: YM_CTL_BYTES) at 0, broadcast control words at 8 KB
   if (e == hipSuccess) e = hipMalloc(&c->d_misc, kMiscBytes);
   if (e == hipSuccess) e = hipMemset(c->d_misc, 0, kMiscBytes);
   for (int l = 1; l < kMaxLanes && e == hipSuccess; ++l) e = hipEventCreateWithFlags(&c->join_ev[l], hipEventDisableTiming);
@@ -790,7 +860,6 @@ int ym_create(int device, const ym_model_desc* desc, ym_ctx** out) {
   *out = c;
   return YM_OK;
 }
-
 
 // Static branch schedule (one-lane forwards): op i depends on every earlier op that writes a buffer it reads
 // (buffer granularity; the planner never rewrites a buffer region within a forward, so RAW is the only hazard).
@@ -1005,10 +1074,10 @@ static void lane_split(const ym_infer_args* args, int B, int& L, int& Bl) {
 // YM_DBG_CHAIN = 1 (ym_set_debug, or YM_CHAIN=1 in the environment; verdict r5 item 1): op i and op i+1 as ONE persistent launch (csrc/ym_conv_dma.hip
 // conv_dma_chain) where both are x3 3x3 convs on the same LDS-DMA configuration, op i+1 reads op i's output and waits
 // for nothing else, and both run on the main stream (one chain kernel in flight at a time).  Returns 1 when launched.
-static int try_chain(ym_ctx* c, size_t i, int B, const float* d_in, const ym_infer_args* args, hipStream_t st,
-                     int& rc) {
+static int try_chain(ym_ctx* c, const Launch& L, size_t i, int B, const float* d_in, const ym_infer_args* args,
+                     hipStream_t st, int& rc) {
   rc = YM_OK;
-  if (ym_debug_get(YM_DBG_CHAIN) != 1 || c->dtype != YM_DT_X3 || i + 1 >= c->ops.size() || c->lane != 0) return 0;
+  if (ym_debug_get(YM_DBG_CHAIN) != 1 || c->dtype != YM_DT_X3 || i + 1 >= c->ops.size() || L.lane != 0) return 0;
   const Op &o0 = c->ops[i], &o1 = c->ops[i + 1];
   if (o0.kind != OP_CONV || o1.kind != OP_CONV || o0.k2 || o1.k2) return 0;
   if (c->nbr > 1 && (c->br_of[i] != 0 || c->br_of[i + 1] != 0 || !c->br_wait[i + 1].empty())) return 0;
@@ -1017,8 +1086,8 @@ static int try_chain(ym_ctx* c, size_t i, int B, const float* d_in, const ym_inf
   if (cf0 != cf1 || (dma != 8 && dma != 13 && dma != 26)) return 0;
   ConvArgs a0{}, a1{};
   int f0 = 0, f1 = 0;
-  if ((rc = conv_args(c, o0, B, d_in, args->in_eps, a0, f0)) || (rc = conv_args(c, o1, B, d_in, args->in_eps, a1, f1)))
-    return 1;
+  const float eps = args->in_eps;
+  if ((rc = conv_args(c, L, o0, B, d_in, eps, a0, f0)) || (rc = conv_args(c, L, o1, B, d_in, eps, a1, f1))) return 1;
   if (f0 || f1 || a0.nchw) return 0;
   const hipError_t e = ym_launch_conv_dma_chain(a0, a1, dma, reinterpret_cast<int*>(c->d_arena + c->off_chain),
                                                 kChainCtl, st);
@@ -1032,8 +1101,8 @@ static int try_chain(ym_ctx* c, size_t i, int B, const float* d_in, const ym_inf
 // reads its output (op i + 1: model.1 -> model.2.cv1) as ONE launch (csrc/ym_stem_fused.hip): the stem's output is
 // never stored.  Only where nothing else reads that output and op i + 1 waits for nothing else.  Returns 1 when
 // launched.
-static int try_stem_fuse(ym_ctx* c, size_t i, int B, const float* d_in, const ym_infer_args* args, hipStream_t st,
-                         int& rc) {
+static int try_stem_fuse(ym_ctx* c, const Launch& L, size_t i, int B, const float* d_in, const ym_infer_args* args,
+                         hipStream_t st, int& rc) {
   rc = YM_OK;
   if (ym_debug_get(YM_DBG_STEMFUSE) != 1 || c->dtype != YM_DT_X3 || i + 1 >= c->ops.size()) return 0;
   const Op &o0 = c->ops[i], &o1 = c->ops[i + 1];
@@ -1047,8 +1116,8 @@ static int try_stem_fuse(ym_ctx* c, size_t i, int B, const float* d_in, const ym
   }
   ConvArgs a0{}, a1{};
   int f0 = 0, f1 = 0;
-  if ((rc = conv_args(c, o0, B, d_in, args->in_eps, a0, f0)) || (rc = conv_args(c, o1, B, d_in, args->in_eps, a1, f1)))
-    return 1;
+  const float eps = args->in_eps;
+  if ((rc = conv_args(c, L, o0, B, d_in, eps, a0, f0)) || (rc = conv_args(c, L, o1, B, d_in, eps, a1, f1))) return 1;
   if (f0 || f1) return 0;
   const hipError_t e = ym_launch_stem_down_x3(a0, a1, st);
   if (e == hipErrorInvalidValue) return 0;
@@ -1091,40 +1160,41 @@ static int launch_embed(ym_ctx* c, int B, hipStream_t st) {
   return YM_OK;
 }
 
-// Launch one forward: the input statistics over the WHOLE batch (LoadTensor's /255 rule is a batch-wide max), then
-// every other op per lane on its image slice.  With fork/join events the lanes are parallel graph branches when
-// `st` is capturing; eagerly (no capture) they run on the lane streams concurrently as well.
-static int launch_forward(ym_ctx* c, const float* d_in, int B, const ym_infer_args* args, float* d_dets,
+// One step of a forward's op loop: op i alone, or (`pair_ok`) ops i and i + 1 as one launch where the fused stem or the
+// chain kernel takes them.  Returns the ops consumed (1 or 2); rc: the step's status.
+static int launch_step(ym_ctx* c, const Launch& L, size_t i, bool pair_ok, int B, const float* d_in,
+                       const ym_infer_args* args, float* d_dets, int* d_counts, hipStream_t st, int& rc) {
+  if (pair_ok && (try_stem_fuse(c, L, i, B, d_in, args, st, rc) || try_chain(c, L, i, B, d_in, args, st, rc))) return 2;
+  rc = launch_op(c, L, c->ops[i], B, d_in, args, d_dets, d_counts, st);
+  return 1;
+}
+
+// Launch one forward of call.B images: the input statistics over the WHOLE batch (LoadTensor's /255 rule is a
+// batch-wide max), then every other op per lane on its image slice.  With fork/join events the lanes are parallel
+// graph branches when `st` is capturing; eagerly (no capture) they run on the lane streams concurrently as well.
+static int launch_forward(ym_ctx* c, const Launch& call, const float* d_in, const ym_infer_args* args, float* d_dets,
                           int* d_counts, hipStream_t st) {
-  int L, Bl, rc;
+  const int B = call.B;
+  int L, Bl, rc = YM_OK;
   lane_split(args, B, L, Bl);
-  c->call_B = B;
-  c->lane = 0;
-  c->lane_img0 = 0;
   // ym_embed: ops [0, nops) only, every op its own launch (a two-op launch could run past the stop, and the fused
   // stem never stores model.0's output), then the pooling stage
-  const bool embed = c->embed_stop >= 0;
-  const size_t nops = embed ? (size_t)c->embed_stop + 1 : c->ops.size();
+  const bool embed = call.stop >= 0;
+  const size_t nops = embed ? (size_t)call.stop + 1 : c->ops.size();
   if (L == 1 && c->nbr > 1) {  // one lane: the branch schedule (build_schedule)
     hipStream_t bs[kMaxLanes] = {st};
     bool opened[kMaxLanes] = {};  // streams that took an op (a whole forward: all nbr; a truncated one maybe fewer)
     for (int s = 1; s < kMaxLanes; ++s) bs[s] = c->lane_streams[s];
-    for (size_t i = 0; i < nops; ++i) {
+    for (size_t i = 0; i < nops;) {
       const int s = c->br_of[i];
       opened[s] = true;
       for (int j : c->br_wait[i]) HIPCK(hipStreamWaitEvent(bs[s], c->op_ev[j], 0));
-      c->lane = s;  // split-K slab / counter region of this stream
-      if (!embed && (try_stem_fuse(c, i, B, d_in, args, bs[s], rc) || try_chain(c, i, B, d_in, args, bs[s], rc))) {  // ops i, i + 1
-        c->lane = 0;
-        if (rc) return rc;
-        if (c->br_rec[i]) HIPCK(hipEventRecord(c->op_ev[i], bs[s]));
-        ++i;
-      } else {
-        rc = launch_op(c, c->ops[i], B, d_in, args, d_dets, d_counts, bs[s]);
-        c->lane = 0;
-      }
+      Launch l = call;
+      l.lane = s;  // split-K slab / counter region of this stream
+      const int n = launch_step(c, l, i, !embed, B, d_in, args, d_dets, d_counts, bs[s], rc);
       if (rc) return rc;
-      if (c->br_rec[i]) HIPCK(hipEventRecord(c->op_ev[i], bs[s]));
+      for (const size_t end = i + n; i < end; ++i)  // (both ops of a two-op launch)
+        if (c->br_rec[i]) HIPCK(hipEventRecord(c->op_ev[i], bs[s]));
     }
     for (int s = 1; s < c->nbr; ++s) {  // every branch that was opened joins back into the caller's stream
       if (!opened[s]) continue;
@@ -1135,62 +1205,58 @@ static int launch_forward(ym_ctx* c, const float* d_in, int B, const ym_infer_ar
   }
   size_t o = 0;
   for (o = 0; o < nops && c->ops[o].kind == OP_INPUT; ++o)
-    if ((rc = launch_op(c, c->ops[o], B, d_in, args, d_dets, d_counts, st))) return rc;
+    if ((rc = launch_op(c, call, c->ops[o], B, d_in, args, d_dets, d_counts, st))) return rc;
   if (L > 1) HIPCK(hipEventRecord(c->fork_ev, st));
   const size_t in_img = (size_t)3 * c->cH * c->cW, det_img = (size_t)args->max_det * (6 + c->nm);
-  for (int l = 0; l < L; ++l) {
-    hipStream_t ls = l == 0 ? st : c->lane_streams[l];
-    if (l > 0) HIPCK(hipStreamWaitEvent(ls, c->fork_ev, 0));
-    c->lane = l;
-    c->lane_img0 = l * Bl;
-    const int nb = B - l * Bl < Bl ? B - l * Bl : Bl;
-    for (size_t i = o; i < nops; ++i) {
-      if (L == 1 && !embed && (try_stem_fuse(c, i, nb, d_in, args, ls, rc) || try_chain(c, i, nb, d_in, args, ls, rc))) {
-        ++i;
-        if (!rc) continue;
-      } else {
-        rc = launch_op(c, c->ops[i], nb, d_in + c->lane_img0 * in_img, args, d_dets + c->lane_img0 * det_img,
-                       d_counts + c->lane_img0, ls);
-      }
-      if (rc) {
-        c->lane = c->lane_img0 = 0;
-        return rc;
-      }
+  for (int ln = 0; ln < L; ++ln) {
+    hipStream_t ls = ln == 0 ? st : c->lane_streams[ln];
+    if (ln > 0) HIPCK(hipStreamWaitEvent(ls, c->fork_ev, 0));
+    Launch l = call;
+    l.lane = ln;
+    l.img0 = ln * Bl;
+    const int nb = B - l.img0 < Bl ? B - l.img0 : Bl;
+    for (size_t i = o; i < nops;) {
+      i += launch_step(c, l, i, L == 1 && !embed, nb, d_in + l.img0 * in_img, args, d_dets + l.img0 * det_img,
+                       d_counts + l.img0, ls, rc);
+      if (rc) return rc;
     }
-    if (l > 0) {
-      HIPCK(hipEventRecord(c->join_ev[l], ls));
-      HIPCK(hipStreamWaitEvent(st, c->join_ev[l], 0));
+    if (ln > 0) {
+      HIPCK(hipEventRecord(c->join_ev[ln], ls));
+      HIPCK(hipStreamWaitEvent(st, c->join_ev[ln], 0));
     }
   }
-  c->lane = c->lane_img0 = 0;
   return embed ? launch_embed(c, B, st) : YM_OK;  // (ym_embed runs one lane: everything above is on `st`)
 }
 
-// ym_infer, (c->skip_nms set by the caller) ym_tta_forward and (c->embed_stop) ym_embed
+// Behind check_call, for every entry point that launches ops: device, workspace, stream order; L: one whole-batch launch
+static int begin_launch(ym_ctx* c, int B, int H, int W, hipStream_t st, Launch& L) {
+  HIPCK(hipSetDevice(c->device));
+  if (int rc = ensure_workspace(c, B, H, W)) return rc;
+  L = Launch{};
+  L.B = B;
+  return c->order_after_last(st);
+}
+
+// ym_infer, (skip_nms) ym_tta_forward and (stop >= 0) ym_embed
 static int infer_impl(ym_ctx* c, const float* d_in, int B, int H, int W, const ym_infer_args* args, float* d_dets,
-                      int* d_counts, void* stream) {
+                      int* d_counts, void* stream, bool skip_nms, int stop) {
   int rc = check_call(c, d_in, B, H, W, args, d_dets, d_counts);
   if (rc) return rc;
-  HIPCK(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  rc = ensure_workspace(c, B, H, W);
-  if (rc) return rc;
-  if ((rc = c->order_after_last(st))) return rc;
+  Launch L;
+  if ((rc = begin_launch(c, B, H, W, st, L))) return rc;
+  L.skip_nms = skip_nms; L.stop = stop;
   if (!args->use_graph) {
-    if (!c->fwd_ev) HIPCK(hipEventCreateWithFlags(&c->fwd_ev, hipEventDisableTiming));
-    if ((rc = launch_forward(c, d_in, B, args, d_dets, d_counts, st))) return rc;
-    HIPCK(hipEventRecord(c->fwd_ev, st));
-    c->last_ev = c->fwd_ev;
-    c->last_st = st;
-    return YM_OK;
+    if ((rc = launch_forward(c, L, d_in, args, d_dets, d_counts, st))) return rc;
+    return c->mark_last(st);
   }
   GraphKey key;
   memset(&key, 0, sizeof(key));
   key.B = B; key.H = H; key.W = W; key.in = d_in; key.dets = nullptr; key.counts = d_counts; key.args = *args;
-  key.skip_nms = c->skip_nms ? 1 : 0;
-  const bool embed = c->embed_stop >= 0;
+  key.skip_nms = L.skip_nms ? 1 : 0;
+  const bool embed = L.stop >= 0;
   if (embed) {
-    key.embed_stop = c->embed_stop + 1;
+    key.embed_stop = L.stop + 1;
     key.embed_n = (int)c->embed_views.size();
     key.embed_out = c->embed_out;
     key.embed_ld = c->embed_ld;
@@ -1208,11 +1274,7 @@ static int infer_impl(ym_ctx* c, const float* d_in, int B, int H, int W, const y
       // tests/test_gpu_kernels.py test_repointed_graph_rows_with_no_sync_between_calls), so no wait here — an
       // asynchronous predict() loop enqueues the next forward while the previous one runs
       if (g.key == key && g.dets != d_dets && (rc = repoint_dets(g, d_dets))) return rc;
-      HIPCK(hipGraphLaunch(g.exec, st));
-      HIPCK(hipEventRecord(g.done, st));
-      c->last_ev = g.done;
-      c->last_st = st;
-      return YM_OK;
+      return c->launch_graph(g, st);
     }
   }
   if (c->graphs.size() >= kMaxGraphs) {  // evict the oldest capture once its last replay has drained
@@ -1221,7 +1283,7 @@ static int infer_impl(ym_ctx* c, const float* d_in, int B, int H, int W, const y
   }
   // capture on the private stream (lane streams join through the fork event), replay on the caller's stream
   HIPCK(hipStreamBeginCapture(c->cap_stream, hipStreamCaptureModeRelaxed));
-  if ((rc = launch_forward(c, d_in, B, args, d_dets, d_counts, c->cap_stream))) {
+  if ((rc = launch_forward(c, L, d_in, args, d_dets, d_counts, c->cap_stream))) {
     hipGraph_t g = nullptr;
     (void)hipStreamEndCapture(c->cap_stream, &g);
     if (g) (void)hipGraphDestroy(g);
@@ -1240,23 +1302,18 @@ static int infer_impl(ym_ctx* c, const float* d_in, int B, int H, int W, const y
   static const bool no_repoint = [] { const char* v = getenv("YM_GRAPH_REPOINT"); return v && *v == '0'; }();
   ge.key = (!no_repoint && find_nms_nodes(ge)) ? key : key_d;
   c->graphs.push_back(ge);
-  HIPCK(hipGraphLaunch(ge.exec, st));
-  HIPCK(hipEventRecord(ge.done, st));
-  c->last_ev = ge.done;
-  c->last_st = st;
-  return YM_OK;
+  return c->launch_graph(c->graphs.back(), st);
 }
 
 int ym_infer(ym_ctx* c, const float* d_in, int B, int H, int W, const ym_infer_args* args, float* d_dets,
              int* d_counts, void* stream) {
-  if (c) c->skip_nms = false;
-  return infer_impl(c, d_in, B, H, W, args, d_dets, d_counts, stream);
+  return infer_impl(c, d_in, B, H, W, args, d_dets, d_counts, stream, false, -1);
 }
 
 // ---------------------------------------------------------------------------------- test-time augmentation
 int ym_tta_shape(int H, int W, int pass, int* Hs, int* Ws, int* hc, int* wc) {
-  if (H < 32 || W < 32 || H % 32 || W % 32 || pass < 0 || pass >= kTtaPasses)
-    return fail(YM_EINVAL, "ym_tta_shape: H and W are positive multiples of 32, pass is 0..%d", kTtaPasses - 1);
+  if (int rc = check_shape(1, H, W, "ym_tta_shape: ")) return rc;
+  if (pass < 0 || pass >= kTtaPasses) return fail(YM_EINVAL, "ym_tta_shape: pass is 0..%d", kTtaPasses - 1);
   int v[4];
   ym_tta_pass_shape(H, W, pass, v[0], v[1], v[2], v[3]);
   if (Hs) *Hs = v[0];
@@ -1269,8 +1326,8 @@ int ym_tta_shape(int H, int W, int pass, int* Hs, int* Ws, int* hc, int* wc) {
 int ym_tta_scale(ym_ctx* c, const float* d_in, int B, int H, int W, int pass, const float* d_max, float in_eps,
                  float* d_out, void* stream) {
   if (!c || !d_in || !d_max || !d_out) return fail(YM_EINVAL, "null argument");
-  if (B < 1 || H < 32 || W < 32 || H % 32 || W % 32 || pass < 1 || pass >= kTtaPasses)
-    return fail(YM_EINVAL, "ym_tta_scale: input (%d,3,%d,%d), pass %d (H, W multiples of 32; pass 1 or 2)", B, H, W, pass);
+  if (int rc = check_shape(B, H, W, "ym_tta_scale: ")) return rc;
+  if (pass < 1 || pass >= kTtaPasses) return fail(YM_EINVAL, "ym_tta_scale: pass %d (1 or 2)", pass);
   HIPCK(hipSetDevice(c->device));
   TtaScaleArgs a{};
   a.in = d_in; a.B = B; a.H = H; a.W = W; a.out = d_out;
@@ -1289,11 +1346,8 @@ int ym_tta_forward(ym_ctx* c, const float* d_in, int B, int H, int W, const ym_i
   fa.multi_label = 0;
   fa.counts_after_dets = 0;
   // (the NMS stage is the only reader of the outputs: any device words do, they are never written)
-  float* nodets = reinterpret_cast<float*>(c->d_misc + 12288);
-  c->skip_nms = true;
-  const int rc = infer_impl(c, d_in, B, H, W, &fa, nodets, reinterpret_cast<int*>(nodets), stream);
-  c->skip_nms = false;
-  return rc;
+  float* nodets = reinterpret_cast<float*>(c->d_misc + kMiscNoDets);
+  return infer_impl(c, d_in, B, H, W, &fa, nodets, reinterpret_cast<int*>(nodets), stream, true, -1);
 }
 
 // ---------------------------------------------------------------------------------- feature embeddings
@@ -1305,8 +1359,7 @@ int ym_embed(ym_ctx* c, const float* d_in, int B, int H, int W, const ym_infer_a
   if (ym_dt_q8(c->dtype))
     return fail(YM_EINVAL, "ym_embed: the quantized plans are not supported (their stored codes need each buffer's "
                            "scale and zero point); use an x3, f16 or f32 plan");
-  if (B < 1 || H < 32 || W < 32 || H % 32 || W % 32)
-    return fail(YM_EINVAL, "input shape (%d,3,%d,%d): H and W must be positive multiples of 32", B, H, W);
+  if (int rc = check_shape(B, H, W, "")) return rc;
   if (n_views < 1 || n_views > kEmbedMaxViews)
     return fail(YM_EINVAL, "ym_embed: %d views (1..%d)", n_views, kEmbedMaxViews);
   long long cols = 0;
@@ -1361,54 +1414,30 @@ int ym_embed(ym_ctx* c, const float* d_in, int B, int H, int W, const ym_infer_a
   ym_infer_args fa{};
   fa.conf = 0.25f; fa.max_wh = 7680.f; fa.iou = 0.7; fa.max_det = 300; fa.max_nms = 30000;
   fa.in_eps = args->in_eps; fa.use_graph = args->use_graph; fa.lanes = 1; fa.d_batch_max = args->d_batch_max;
-  float* nodets = reinterpret_cast<float*>(c->d_misc + 12288);
-  c->skip_nms = false;
-  c->embed_stop = stop;
-  const int rc = infer_impl(c, d_in, B, H, W, &fa, nodets, reinterpret_cast<int*>(nodets), stream);
-  c->embed_stop = -1;
-  return rc;
+  float* nodets = reinterpret_cast<float*>(c->d_misc + kMiscNoDets);
+  return infer_impl(c, d_in, B, H, W, &fa, nodets, reinterpret_cast<int*>(nodets), stream, false, stop);
 }
 
 // the merged scratch of ctxs[0] for B images of an H x W frame: Am merged anchors, multi-label regions on demand
 static int ensure_tta(ym_ctx* c, int B, int H, int W, int Am, bool ml) {
   ym_ctx::TtaWs& t = c->tta;
-  if (t.d && B <= t.B && H == t.H && W == t.W && Am == t.Am && c->nc == t.nc && (!ml || t.ml)) return YM_OK;
+  if (t.d && B <= t.B && H == t.H && W == t.W && Am == t.ws.A && c->nc == t.nc && (!ml || t.ws.ml)) return YM_OK;
   if (t.d) {
     HIPCK(hipDeviceSynchronize());  // an earlier merge / NMS on any stream may still use the old scratch
     HIPCK(hipFree(t.d));
     t.d = nullptr;
   }
-  const int nB = (H == t.H && W == t.W && Am == t.Am && B < t.B) ? t.B : B;
-  t.ml = ml || (t.ml && H == t.H && W == t.W);
+  const int nB = (H == t.H && W == t.W && Am == t.ws.A && B < t.B) ? t.B : B;
+  ml = ml || (t.ws.ml && H == t.H && W == t.W);
   t.B = 0;
-  t.H = H; t.W = W; t.Am = Am; t.nc = c->nc;
-  t.kstride = 1;
-  while (t.kstride < Am) t.kstride <<= 1;
-  const size_t BA = (size_t)nB * Am;
-  size_t off = 0;
-  t.off_boxes = off;  off = align_up(off + BA * 16, 256);
-  t.off_scores = off; off = align_up(off + BA * 4, 256);
-  t.off_cls = off;    off = align_up(off + BA * 4, 256);
-  t.off_keys = off;   off = align_up(off + (size_t)nB * t.kstride * 8, 256);
-  t.off_keys2 = off;  off = align_up(off + (size_t)nB * t.kstride * 8, 256);
-  t.off_counts = off; off = align_up(off + (size_t)nB * 4, 256);
-  t.off_sboxes = off; off = align_up(off + BA * 16, 256);
-  t.off_sareas = off; off = align_up(off + BA * 4, 256);
-  t.off_sup = off;    off = align_up(off + BA, 256);
-  if (t.ml) {
-    t.off_rows = off;  off = align_up(off + BA * c->nc * 4, 256);
-    t.off_sel = off;   off = align_up(off + (size_t)nB * kMlCap * 8, 256);
-    t.off_sel2 = off;  off = align_up(off + (size_t)nB * kMlCap * 8, 256);
-    t.off_hist = off;  off = align_up(off + (size_t)nB * 1024 * 4, 256);
-    t.off_state = off; off = align_up(off + (size_t)nB * sizeof(MlState), 256);
-    t.off_seln = off;  off = align_up(off + (size_t)nB * 4, 256);
-  }
-  const hipError_t e = hipMalloc(&t.d, off);
+  t.H = H; t.W = W; t.nc = c->nc;
+  const size_t bytes = nms_scratch_append(t.ws, 0, nB, Am, ml, ml ? c->nc : 0);
+  const hipError_t e = hipMalloc(&t.d, bytes);
   if (e != hipSuccess) {
     t.d = nullptr;
-    return fail(YM_ENOMEM, "tta scratch hipMalloc(%zu) failed: %s", off, hipGetErrorString(e));
+    return fail(YM_ENOMEM, "tta scratch hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
   }
-  HIPCK(hipMemset(t.d, 0, off));
+  HIPCK(hipMemset(t.d, 0, bytes));
   t.B = nB;
   return YM_OK;
 }
@@ -1416,8 +1445,7 @@ static int ensure_tta(ym_ctx* c, int B, int H, int W, int Am, bool ml) {
 int ym_tta_nms(ym_ctx* const* ctxs, int B, int H, int W, const ym_infer_args* args, float* d_dets, int* d_counts,
                void* stream) {
   if (!ctxs || !args || !d_dets || !d_counts) return fail(YM_EINVAL, "null pointer argument");
-  if (B < 1 || H < 32 || W < 32 || H % 32 || W % 32)
-    return fail(YM_EINVAL, "input shape (%d,3,%d,%d): H and W must be positive multiples of 32", B, H, W);
+  if (int rc = check_shape(B, H, W, "")) return rc;
   ym_ctx* c = ctxs[0];
   for (int p = 0; p < kTtaPasses; ++p) {
     ym_ctx* q = ctxs[p];
@@ -1437,13 +1465,8 @@ int ym_tta_nms(ym_ctx* const* ctxs, int B, int H, int W, const ym_infer_args* ar
       return fail(YM_ESTATE, "pass %d: ym_tta_nms must follow ym_tta_forward of (%d,3,%d,%d) (workspace %dx%dx%d)", p, B, Hs,
                   Ws, q->cB, q->cH, q->cW);
   }
-  if (args->max_det < 1 || args->max_nms < 1) return fail(YM_EINVAL, "max_det/max_nms must be >= 1");
-  if (args->max_det > 1024) return fail(YM_EINVAL, "max_det %d > 1024 is not supported", args->max_det);
-  if (args->counts_after_dets != 0 && args->counts_after_dets != 1) return fail(YM_EINVAL, "counts_after_dets is 0 or 1");
-  if (args->multi_label != 0 && args->multi_label != 1) return fail(YM_EINVAL, "multi_label is 0 or 1");
+  if (int rc = check_nms_args(args, c->nc, c->task)) return rc;
   const bool ml = args->multi_label && c->nc > 1;
-  if (ml && c->nc > 128) return fail(YM_EINVAL, "multi_label: nc %d > 128 is not supported", c->nc);
-  if (ml && args->max_nms > kMlCap) return fail(YM_EINVAL, "multi_label: max_nms %d > %d is not supported", args->max_nms, kMlCap);
   HIPCK(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
   // _clip_augmented (g = 21 = 1 + 4 + 16 grid points per stride-32 cell): pass 0 without its last A / 21 anchors,
@@ -1459,75 +1482,34 @@ int ym_tta_nms(ym_ctx* const* ctxs, int B, int H, int W, const ym_infer_args* ar
     P.base = Am;
     Am += P.keep;
     P.anchors = reinterpret_cast<const float*>(q->d_arena + q->buf_off[q->anchor_buf]);
-    P.boxes = reinterpret_cast<const float4*>(q->d_arena + q->off_boxes);
-    P.scores = reinterpret_cast<const float*>(q->d_arena + q->off_scores);
-    P.cls = reinterpret_cast<const int*>(q->d_arena + q->off_cls);
+    const NmsView qv = nms_view(q->d_arena, q->nms, 0);
+    P.boxes = qv.boxes; P.scores = qv.scores; P.cls = qv.cls;
     for (int l = 0; l < q->nl; ++l) { P.lvl_W[l] = q->lvl_W[l]; P.lvl_off[l] = q->lvl_off[l]; }
     P.s = (float)kTtaRatio[p];
     P.flip = kTtaFlip[p];
   }
   if (int rc = ensure_tta(c, B, H, W, Am, ml)) return rc;
-  const ym_ctx::TtaWs& t = c->tta;
+  const NmsView v = nms_view(c->tta.d, c->tta.ws, 0);
   if (int rc = c->order_after_last(st)) return rc;  // (the scratch's previous user: ctxs[0]'s last call)
   m.no_tot = c->bufs[c->anchor_buf].C; m.nc = c->nc; m.reg_max = c->reg_max; m.nl = c->nl;
   for (int l = 0; l < c->nl; ++l) m.lvl_stride[l] = (float)c->strides[l];
-  m.boxes = reinterpret_cast<float4*>(t.d + t.off_boxes);
-  m.scores = reinterpret_cast<float*>(t.d + t.off_scores);
-  m.cls = reinterpret_cast<int*>(t.d + t.off_cls);
-  m.keys = reinterpret_cast<unsigned long long*>(t.d + t.off_keys);
-  m.counts = reinterpret_cast<int*>(t.d + t.off_counts);
-  m.rows = ml ? reinterpret_cast<float*>(t.d + t.off_rows) : nullptr;
-  m.Am = Am; m.kstride = t.kstride; m.B = B;
+  m.boxes = v.boxes; m.scores = v.scores; m.cls = v.cls; m.keys = v.keys; m.counts = v.counts;
+  m.rows = ml ? v.rows : nullptr;
+  m.Am = Am; m.kstride = v.kstride; m.B = B;
   m.conf = args->conf; m.has_classes = args->has_classes;
   for (int i = 0; i < 4; ++i) m.classes[i] = args->classes[i];
   m.img_w = (float)W;
   if (!ml) HIPCK(hipMemsetAsync(m.counts, 0, (size_t)B * 4, st));
   hipError_t e = ym_launch_tta_merge(m, st);
   if (e != hipSuccess) return fail(YM_EHIP, "tta merge launch: %s", hipGetErrorString(e));
-  NmsArgs a{};
-  a.boxes = m.boxes; a.scores = m.scores; a.cls = m.cls; a.keys = m.keys; a.counts = m.counts;
-  a.sboxes = reinterpret_cast<float4*>(t.d + t.off_sboxes);
-  a.sareas = reinterpret_cast<float*>(t.d + t.off_sareas);
-  a.sup = reinterpret_cast<unsigned char*>(t.d + t.off_sup);
-  a.dets = d_dets; a.out_counts = d_counts;
-  a.counts2 = args->counts_after_dets ? reinterpret_cast<int*>(d_dets + (size_t)B * args->max_det * 6) : nullptr;
-  a.A = Am; a.kstride = t.kstride; a.nm = 0; a.max_det = args->max_det; a.max_nms = args->max_nms;
-  a.agnostic = args->agnostic; a.B = B; a.nc = c->nc;
-  a.max_wh = args->max_wh; a.img_h = (float)H; a.img_w = (float)W;
-  a.iou = args->iou;
-  if (ml) {
-    MlArgs k{};
-    k.anchors = m.rows; k.no_tot = c->nc; k.cls_off = 0;
-    k.A = Am; k.nc = c->nc; k.B = B;
-    k.conf = args->conf; k.has_classes = args->has_classes;
-    for (int i = 0; i < 4; ++i) k.classes[i] = args->classes[i];
-    k.max_nms = args->max_nms; k.cap = kMlCap;
-    k.counts = m.counts;
-    k.hist = reinterpret_cast<unsigned int*>(t.d + t.off_hist);
-    k.state = reinterpret_cast<MlState*>(t.d + t.off_state);
-    k.sel = reinterpret_cast<unsigned long long*>(t.d + t.off_sel);
-    k.sel2 = reinterpret_cast<unsigned long long*>(t.d + t.off_sel2);
-    k.seln = reinterpret_cast<int*>(t.d + t.off_seln);
-    a.keys = k.sel; a.kstride = kMlCap; a.counts = k.seln;
-    a.scores = nullptr; a.cls = nullptr;
-    e = ym_launch_nms_ml(k, a, st);
-  } else {
-    if (args->conf < kPresortConf && t.kstride >= 16384) {  // as the plain path: low conf, thousands of candidates
-      a.keys2 = reinterpret_cast<unsigned long long*>(t.d + t.off_keys2);
-      a.presorted = 1;
-      e = ym_launch_nms_presort(a, st);
-    }
-    if (e == hipSuccess) e = ym_launch_nms(a, st);
-  }
+  // no extras (detect plans: nm = 0); multi-label thresholds the merged class rows
+  const NmsSource src{nullptr, 0, 0, m.rows, c->nc, 0};
+  int* counts2 = args->counts_after_dets ? reinterpret_cast<int*>(d_dets + (size_t)B * args->max_det * 6) : nullptr;
+  e = launch_nms_stage(v, src, args, B, c->nc, 0, H, W, d_dets, d_counts, counts2, st);
   if (e != hipSuccess) return fail(YM_EHIP, "tta NMS launch: %s", hipGetErrorString(e));
   // the merge read every pass's arena: a later forward of any of them on another stream waits for this call
-  for (int p = 0; p < kTtaPasses; ++p) {
-    ym_ctx* q = ctxs[p];
-    if (!q->fwd_ev) HIPCK(hipEventCreateWithFlags(&q->fwd_ev, hipEventDisableTiming));
-    HIPCK(hipEventRecord(q->fwd_ev, st));
-    q->last_ev = q->fwd_ev;
-    q->last_st = st;
-  }
+  for (int p = 0; p < kTtaPasses; ++p)
+    if (int rc = ctxs[p]->mark_last(st)) return rc;
   return YM_OK;
 }
 
@@ -1536,14 +1518,14 @@ int ym_tta_counts(ym_ctx* c, int* dst, int B) {
   if (!c->tta.d || B > c->tta.B) return fail(YM_ESTATE, "no merged scratch for %d images yet (run ym_tta_nms first)", B);
   HIPCK(hipSetDevice(c->device));
   HIPCK(hipDeviceSynchronize());
-  HIPCK(hipMemcpy(dst, c->tta.d + c->tta.off_counts, (size_t)B * 4, hipMemcpyDefault));
+  HIPCK(hipMemcpy(dst, c->tta.d + c->tta.ws.counts.off, (size_t)B * 4, hipMemcpyDefault));
   return YM_OK;
 }
 
 int ym_input_max(ym_ctx* c, const float* d_in, size_t n, float* d_max, void* stream) {
   if (!c || !d_in || !d_max || n == 0) return fail(YM_EINVAL, "bad ym_input_max arguments");
   HIPCK(hipSetDevice(c->device));
-  const hipError_t e = ym_launch_input_max(d_in, (long)n, reinterpret_cast<float*>(c->d_misc), d_max,
+  const hipError_t e = ym_launch_input_max(d_in, (long)n, reinterpret_cast<float*>(c->d_misc + kMiscStats), d_max,
                                            static_cast<hipStream_t>(stream));
   if (e != hipSuccess) return fail(YM_EHIP, "input max: %s", hipGetErrorString(e));
   return YM_OK;
@@ -1555,15 +1537,14 @@ int ym_calibrate(ym_ctx* c, const float* d_in, int B, int H, int W, const ym_inf
   if (rc) return rc;
   if (c->dtype != YM_DT_F32) return fail(YM_ESTATE, "ym_calibrate needs an f32 (parity) plan");
   if (!d_raw || n_ops != (int)c->ops.size()) return fail(YM_EINVAL, "d_raw must hold %zu entries", c->ops.size());
-  HIPCK(hipSetDevice(c->device));
-  if ((rc = ensure_workspace(c, B, H, W))) return rc;
-  if ((rc = c->order_after_last(static_cast<hipStream_t>(stream)))) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  Launch L;
+  if ((rc = begin_launch(c, B, H, W, st, L))) return rc;
   ym_infer_args one = *args;
   one.lanes = 1;
-  c->calib_raw = d_raw;
-  rc = launch_forward(c, d_in, B, &one, d_dets, d_counts, static_cast<hipStream_t>(stream));
-  c->calib_raw = nullptr;
-  return rc;
+  L.calib_raw = d_raw;
+  if ((rc = launch_forward(c, L, d_in, &one, d_dets, d_counts, st))) return rc;
+  return c->mark_last(st);  // (a later forward on another stream waits for this one on the shared arena)
 }
 
 int ym_profile(ym_ctx* c, const float* d_in, int B, int H, int W, const ym_infer_args* args, float* d_dets,
@@ -1571,10 +1552,9 @@ int ym_profile(ym_ctx* c, const float* d_in, int B, int H, int W, const ym_infer
   int rc = check_call(c, d_in, B, H, W, args, d_dets, d_counts);
   if (rc) return rc;
   if (!op_ms || n_ops < (int)c->ops.size()) return fail(YM_EINVAL, "op_ms must hold %zu entries", c->ops.size());
-  HIPCK(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if ((rc = ensure_workspace(c, B, H, W))) return rc;
-  if ((rc = c->order_after_last(st))) return rc;
+  Launch L;
+  if ((rc = begin_launch(c, B, H, W, st, L))) return rc;
   const size_t ne = c->ops.size() + 1;
   while (c->prof_events.size() < ne) {
     hipEvent_t e;
@@ -1586,7 +1566,7 @@ int ym_profile(ym_ctx* c, const float* d_in, int B, int H, int W, const ym_infer
   HIPCK(ym_launch_spin(20 * (int)c->ops.size() + 2000, st));
   HIPCK(hipEventRecord(c->prof_events[0], st));
   for (size_t i = 0; i < c->ops.size(); ++i) {
-    if ((rc = launch_op(c, c->ops[i], B, d_in, args, d_dets, d_counts, st))) return rc;
+    if ((rc = launch_op(c, L, c->ops[i], B, d_in, args, d_dets, d_counts, st))) return rc;
     HIPCK(hipEventRecord(c->prof_events[i + 1], st));
   }
   HIPCK(hipEventSynchronize(c->prof_events[ne - 1]));
@@ -1601,46 +1581,25 @@ int ym_profile_replay(ym_ctx* c, const float* d_in, int B, int H, int W, const y
   if (rc) return rc;
   if (!op_ms || n_ops < (int)c->ops.size()) return fail(YM_EINVAL, "op_ms must hold %zu entries", c->ops.size());
   if (reps < 1) reps = 20;
-  HIPCK(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if ((rc = ensure_workspace(c, B, H, W))) return rc;
-  if ((rc = c->order_after_last(st))) return rc;
+  Launch L;
+  if ((rc = begin_launch(c, B, H, W, st, L))) return rc;
   // one real forward so every buffer holds this input's activations (and the /255 flag is set)
   for (const Op& op : c->ops)
-    if ((rc = launch_op(c, op, B, d_in, args, d_dets, d_counts, st))) return rc;
-  hipEvent_t e0, e1;
-  HIPCK(hipEventCreate(&e0));
-  HIPCK(hipEventCreate(&e1));
+    if ((rc = launch_op(c, L, op, B, d_in, args, d_dets, d_counts, st))) return rc;
   for (size_t i = 0; i < c->ops.size(); ++i) {
     const Op& op = c->ops[i];
     const int k = op.kind;
     op_ms[i] = -1.f;
     // input (resets counters), decode (appends candidates) and NMS (consumes them) are not idempotent: skipped
     if (k != OP_CONV && k != OP_DW && k != OP_SPPF && k != OP_ATTN) continue;
-    hipGraph_t g = nullptr;
-    hipGraphExec_t ge = nullptr;
-    HIPCK(hipStreamBeginCapture(c->cap_stream, hipStreamCaptureModeRelaxed));
     int lrc = YM_OK;
-    for (int r = 0; r < reps && lrc == YM_OK; ++r) lrc = launch_op(c, op, B, d_in, args, d_dets, d_counts, c->cap_stream);
-    HIPCK(hipStreamEndCapture(c->cap_stream, &g));
-    if (lrc != YM_OK) {
-      (void)hipGraphDestroy(g);
-      return lrc;
-    }
-    HIPCK(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
-    HIPCK(hipGraphLaunch(ge, st));  // warm
-    HIPCK(hipEventRecord(e0, st));
-    HIPCK(hipGraphLaunch(ge, st));
-    HIPCK(hipEventRecord(e1, st));
-    HIPCK(hipEventSynchronize(e1));
     float ms = 0.f;
-    HIPCK(hipEventElapsedTime(&ms, e0, e1));
+    auto launch = [&](hipStream_t s) { return launch_op(c, L, op, B, d_in, args, d_dets, d_counts, s); };
+    if ((rc = time_captured(c, st, reps, 1, launch, lrc, ms))) return rc;
+    if (lrc != YM_OK) return lrc;
     op_ms[i] = ms / reps;
-    (void)hipGraphExecDestroy(ge);
-    (void)hipGraphDestroy(g);
   }
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
   return YM_OK;
 }
 
@@ -1648,20 +1607,16 @@ int ym_tune(ym_ctx* c, const float* d_in, int B, int H, int W, const ym_infer_ar
             int* d_counts, void* stream, int reps) {
   int rc = check_call(c, d_in, B, H, W, args, d_dets, d_counts);
   if (rc) return rc;
-  HIPCK(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if ((rc = ensure_workspace(c, B, H, W))) return rc;
-  if ((rc = c->order_after_last(st))) return rc;
+  Launch L;
+  if ((rc = begin_launch(c, B, H, W, st, L))) return rc;
   if (reps < 1) reps = 8;
   // one real forward first so every buffer a candidate reads holds this model's activations
   c->drop_cfg(B, H, W);
   for (const Op& op : c->ops)
-    if ((rc = launch_op(c, op, B, d_in, args, d_dets, d_counts, st))) return rc;
+    if ((rc = launch_op(c, L, op, B, d_in, args, d_dets, d_counts, st))) return rc;
   HIPCK(hipStreamSynchronize(st));
   std::vector<int> best(c->ops.size(), -1);
-  hipEvent_t e0, e1;
-  HIPCK(hipEventCreate(&e0));
-  HIPCK(hipEventCreate(&e1));
   const int ncfg = ym_conv_num_cfgs_dt(c->dtype);
   const char* tl = getenv("YM_TUNE_LOG");  // per-candidate timings to stderr (tools/)
   const bool tune_log = tl && *tl && *tl != '0';
@@ -1670,53 +1625,37 @@ int ym_tune(ym_ctx* c, const float* d_in, int B, int H, int W, const ym_infer_ar
     if (op.kind != OP_CONV) continue;
     ConvArgs a;
     int out_f32 = 0;
-    if ((rc = conv_args(c, op, B, d_in, args->in_eps, a, out_f32))) return rc;
+    if ((rc = conv_args(c, L, op, B, d_in, args->in_eps, a, out_f32))) return rc;
     if (a.nchw) continue;  // the stem has its own kernel (csrc/ym_stem.hip)
-    // best config of one conv launch: time `reps` back-to-back launches of each candidate as one graph
-    // (device-bound even for tiny kernels)
-    auto tune_one = [&](const ConvArgs& ca, int of32, int& bcf) -> float {
-      float bt = 1e30f;
+    // best config of one conv launch (bcf, its time bt; -1: none launched): `reps` back-to-back launches of each
+    // candidate, replayed twice between the events
+    auto tune_one = [&](const ConvArgs& ca, int of32, int& bcf, float& bt) -> int {
+      bt = 1e30f;
       bcf = -1;
       for (int cf = 0; cf < ncfg; ++cf) {
-        hipGraph_t g = nullptr;
-        hipGraphExec_t ge = nullptr;
-        HIPCK(hipStreamBeginCapture(c->cap_stream, hipStreamCaptureModeRelaxed));
-        hipError_t le = hipSuccess;
-        for (int r = 0; r < reps && le == hipSuccess; ++r) le = ym_launch_conv(c->dtype, of32, ca, cf, c->cap_stream, true);
-        HIPCK(hipStreamEndCapture(c->cap_stream, &g));
-        if (le != hipSuccess) {
-          (void)hipGraphDestroy(g);
-          continue;
-        }
-        HIPCK(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
-        HIPCK(hipGraphLaunch(ge, st));
-        HIPCK(hipEventRecord(e0, st));
-        HIPCK(hipGraphLaunch(ge, st));
-        HIPCK(hipGraphLaunch(ge, st));
-        HIPCK(hipEventRecord(e1, st));
-        HIPCK(hipEventSynchronize(e1));
+        int lrc = 0;
         float ms = 0.f;
-        HIPCK(hipEventElapsedTime(&ms, e0, e1));
-        (void)hipGraphExecDestroy(ge);
-        (void)hipGraphDestroy(g);
-        if (tune_log) fprintf(stderr, "[ym_tune] %s%s cfg %d: %.2f us\n", op.name, of32 < 0 ? "" : "", cf, ms * 1e3f / (2 * reps));
+        auto launch = [&](hipStream_t s) { return (int)ym_launch_conv(c->dtype, of32, ca, cf, s, true); };
+        if (int trc = time_captured(c, st, reps, 2, launch, lrc, ms)) return trc;
+        if (lrc != 0) continue;  // this configuration does not take the shape
+        if (tune_log) fprintf(stderr, "[ym_tune] %s cfg %d: %.2f us\n", op.name, cf, ms * 1e3f / (2 * reps));
         if (ms < bt) { bt = ms; bcf = cf; }
       }
-      return bt;
+      return YM_OK;
     };
     int cf = -1;
-    const float tf = tune_one(a, out_f32, cf);
+    float tf = 0.f;
+    if ((rc = tune_one(a, out_f32, cf, tf))) return rc;
     best[i] = cf;
     if (a.w2) {  // fused pair: also the two convs as separate tuned launches
       ConvArgs A, Bc;
-      split_args(c, op, a, A, Bc);
+      split_args(c, L, op, a, A, Bc);
       int ca = -1, cb = -1;
-      const float ta = tune_one(A, 0, ca), tb = tune_one(Bc, out_f32, cb);
+      float ta = 0.f, tb = 0.f;
+      if ((rc = tune_one(A, 0, ca, ta)) || (rc = tune_one(Bc, out_f32, cb, tb))) return rc;
       if (ca >= 0 && cb >= 0 && ta + tb < tf) best[i] = kSplitTag + 256 * ca + cb;
     }
   }
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
   c->clear_graphs();
   c->put_cfg(B, H, W, best);
   return YM_OK;
@@ -1755,7 +1694,7 @@ int ym_num_buffers(ym_ctx* c) { return c ? (int)c->bufs.size() : fail(YM_EINVAL,
 int ym_buffer_info(ym_ctx* c, int b, void** ptr, int* C, int* H, int* W, int* elem_bytes) {
   if (!c || b < 0 || b >= (int)c->bufs.size()) return fail(YM_EINVAL, "bad buffer id");
   if (!c->d_arena) return fail(YM_ESTATE, "no workspace yet (run ym_infer first)");
-  if (ptr) *ptr = c->bptr(b);
+  if (ptr) *ptr = c->bptr(b, 0);
   if (C) *C = c->bufs[b].C;
   if (H) *H = c->buf_H(b);
   if (W) *W = c->buf_Wd(b);
@@ -1770,7 +1709,7 @@ int ym_read_buffer(ym_ctx* c, int b, void* dst, size_t bytes) {
   if (bytes > cap) return fail(YM_EINVAL, "read of %zu bytes exceeds buffer size %zu", bytes, cap);
   HIPCK(hipSetDevice(c->device));
   HIPCK(hipDeviceSynchronize());
-  HIPCK(hipMemcpy(dst, c->bptr(b), bytes, hipMemcpyDefault));
+  HIPCK(hipMemcpy(dst, c->bptr(b, 0), bytes, hipMemcpyDefault));
   return YM_OK;
 }
 
@@ -1787,8 +1726,8 @@ int ym_read_scratch(ym_ctx* c, int which, void* dst, size_t bytes) {
   if (!c->d_arena) return fail(YM_ESTATE, "no workspace yet (run ym_infer first)");
   size_t off = 0, cap = 0;
   switch (which) {
-    case YM_SCRATCH_KEYS: off = c->off_keys; cap = (size_t)c->cB * c->kstride * 8; break;
-    case YM_SCRATCH_COUNTS: off = c->off_counts; cap = (size_t)c->cB * 4; break;
+    case YM_SCRATCH_KEYS: off = c->nms.keys.off; cap = c->cB * c->nms.keys.stride; break;
+    case YM_SCRATCH_COUNTS: off = c->nms.counts.off; cap = c->cB * c->nms.counts.stride; break;
     case YM_SCRATCH_KPTS:
       if (c->task != kTaskPose) return fail(YM_ESTATE, "YM_SCRATCH_KPTS needs a pose plan");
       off = c->off_kpts; cap = (size_t)c->cB * c->A * c->nm * 4;
@@ -1829,7 +1768,7 @@ static int launch_masks(ym_ctx* c, MaskArgs& a, int B, int H, int W, void* strea
     return fail(YM_ESTATE, "ym_masks must follow ym_infer of the same (B, H, W) (workspace %dx%dx%d)", c->cB, c->cH,
                 c->cW);
   HIPCK(hipSetDevice(c->device));
-  a.proto = reinterpret_cast<const float*>(c->bptr(c->proto_buf));
+  a.proto = reinterpret_cast<const float*>(c->bptr(c->proto_buf, 0));
   a.MH = c->buf_H(c->proto_buf); a.MW = c->buf_Wd(c->proto_buf); a.nm = c->nm;
   a.no = 6 + c->nm; a.B = B; a.H = H; a.W = W;
   if (a.total == 0) return YM_OK;
@@ -1891,7 +1830,7 @@ int ym_masks_native(ym_ctx* c, const float* d_dets, int det_stride, int B, int m
   if (total == 0) return YM_OK;
   HIPCK(hipSetDevice(c->device));
   MaskNativeArgs a{};
-  a.proto = reinterpret_cast<const float*>(c->bptr(c->proto_buf));
+  a.proto = reinterpret_cast<const float*>(c->bptr(c->proto_buf, 0));
   a.MH = c->buf_H(c->proto_buf); a.MW = c->buf_Wd(c->proto_buf); a.nm = c->nm;
   a.dets = d_dets; a.max_det = max_det; a.stride = det_stride;
   a.offsets = d_offsets; a.B = B; a.total = total;
@@ -2061,8 +2000,8 @@ int ym_broadcast_weights(ym_ctx* c, void* comm, int root, void* stream) {
   BcastRank me;
   me.c = c;
   me.rank = rank;
-  // control words: the context's 4 KB scratch (allocated by ym_create, so nothing can fail before step 1)
-  unsigned long long* dctl = reinterpret_cast<unsigned long long*>(c->d_misc + 8192);
+  // control words in the context's scratch (allocated by ym_create, so nothing can fail before step 1)
+  unsigned long long* dctl = reinterpret_cast<unsigned long long*>(c->d_misc + kMiscBcast);
   auto allreduce_sum = [&](unsigned long long* h, int cnt) -> int {
     me.hip_ok = me.hip_ok && hipMemcpyAsync(dctl, h, 8 * cnt, hipMemcpyHostToDevice, st) == hipSuccess;
     const int r = R->allreduce(dctl, dctl, cnt, kNcclUint64, kNcclSum, comm, st);

@@ -289,6 +289,49 @@ typedef struct {
 int ym_embed(ym_ctx* ctx, const float* d_input, int B, int H, int W, const ym_infer_args* args,
              const ym_embed_view* views, int n_views, float* d_out, long long out_stride, void* stream);
 
+/* Object tracking (Ultralytics model.track(..., tracker="bytetrack.yaml"), trackers/byte_tracker.py BYTETracker.update):
+ * a tracker holds the ByteTrack state of `streams` independent video streams in device memory; one ym_track_update
+ * call advances stream b by the detections of image b of a batch, as ONE kernel launch behind the NMS
+ * (csrc/ym_track.hip: fp64 XYAH Kalman filter, fp32 IoU, an optimal (not greedy) assignment), with no
+ * host synchronisation.  Track ids count from 1 per stream.
+ * ym_track_cfg: bytetrack.yaml's parameters; max_time_lost = track_buffer frames (frame rate 30).  capacity: track
+ * slots per stream (tracked + lost + unconfirmed), 0 = YM_TRACK_CAPACITY; when every slot is taken, further
+ * detections start no track and the stream's drop counter goes up.
+ * ym_track_create: YM_EINVAL for a null pointer, streams outside 1..YM_TRACK_MAX_STREAMS, a threshold outside [0, 1],
+ * track_buffer < 0 or capacity outside 0..YM_TRACK_CAPACITY.  The tracker lives on ctx's device and starts reset.
+ * ym_track_reset: every stream back to frame 0, no tracks, next id 1, drops 0 (asynchronous on `stream`).
+ * ym_track_update: d_dets = B x max_det rows of det_stride floats [x1,y1,x2,y2,conf,cls,extras] with d_counts[b] valid
+ * rows per image (what ym_infer wrote; det_stride = 6 + nm).  d_tracks: B x max_det rows of det_stride + 1 floats
+ * [x1,y1,x2,y2 (the filter's box), id, conf, cls, extras of the detection that fed the track]; d_idx: B x max_det
+ * int32, that detection's row; d_track_counts: B int32 rows written per image.  Rows are in ascending id order; only
+ * activated tracks matched in this frame appear.  An image whose count is 0 leaves its stream untouched (no frame is
+ * counted) and writes count 0.  YM_EINVAL: a null pointer, B != streams, max_det outside 1..YM_TRACK_MAX_DET,
+ * det_stride outside 6..YM_TRACK_MAX_STRIDE.  Asynchronous on `stream`; calls of one tracker must be stream-ordered.
+ * ym_track_read_state: per stream YM_TRACK_STATE_WORDS ints [frame_id, next id, activated tracked tracks, lost
+ * tracks, unconfirmed tracks, drops] after the last update, n_streams <= streams of them; synchronous. */
+#define YM_TRACK_CAPACITY 512
+#define YM_TRACK_MAX_DET 300
+#define YM_TRACK_MAX_STRIDE 64
+#define YM_TRACK_MAX_STREAMS 1024
+#define YM_TRACK_STATE_WORDS 6
+typedef struct ym_tracker ym_tracker;
+typedef struct {
+  double track_high_thresh; /* 0.25 */
+  double track_low_thresh;  /* 0.1 */
+  double new_track_thresh;  /* 0.25 */
+  double match_thresh;      /* 0.8 */
+  int track_buffer;         /* 30 */
+  int fuse_score;           /* 1 */
+  int capacity;             /* 0 = YM_TRACK_CAPACITY */
+  int reserved;             /* 0 */
+} ym_track_cfg;
+int ym_track_create(ym_ctx* ctx, int streams, const ym_track_cfg* cfg, ym_tracker** out);
+void ym_track_destroy(ym_tracker* trk);
+int ym_track_reset(ym_tracker* trk, void* stream);
+int ym_track_update(ym_tracker* trk, const float* d_dets, int det_stride, int B, int max_det, const int* d_counts,
+                    float* d_tracks, int* d_idx, int* d_track_counts, void* stream);
+int ym_track_read_state(ym_tracker* trk, int* state, int n_streams);
+
 int ym_sync(ym_ctx* ctx);
 const char* ym_last_error(void);
 void ym_destroy(ym_ctx* ctx);

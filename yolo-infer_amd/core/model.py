@@ -331,6 +331,58 @@ class YOLO11Model:
                 res.append(Results.from_image(imsrc[0][b], imsrc[1][b], names, bx, speed=speed, masks=mk))
         return res
 
+    def track(self, source, persist: bool = False, tracker="bytetrack.yaml", **kwargs) -> List[Results]:
+        """Ultralytics `model.track(source, persist=..., tracker="bytetrack.yaml")`: predict(), then ByteTrack on the GPU
+        right behind the NMS (Engine.track, csrc/ym_track.hip).  Image b of the batch is video stream b:
+        call it once per frame (or per batch of B cameras' frames) with persist=True to carry ids across calls;
+        persist=False (the default, as upstream) starts over.  `Results.boxes` is (n, 7) [x1, y1, x2, y2, id, conf, cls]
+        — the filter's box of every activated track matched in this frame, ascending ids, which count from 1 per
+        stream — `boxes.id` / `boxes.is_track` are set, and a pose model's keypoints are those of the detection behind
+        each track.  conf defaults to 0.1 (ByteTrack's second association wants the low scores); the other predict
+        keywords pass through, max_det <= 300; augment and retina_masks are ignored.  For tensor sources the call is
+        asynchronous like predict().  tracker: "bytetrack.yaml", a YAML file with its keys, or a dict
+        (yolomi.track.tracker_config); "botsort.yaml" and segment models raise NotImplementedError; a batch size other
+        than the live tracker's under persist=True raises ValueError."""
+        from yolomi.track import tracker_config
+        cfg = tracker_config(tracker)
+        if self.task == "segment":
+            raise NotImplementedError("track() is offered for detect and pose models: a segment model's masks would "
+                                      "have to be re-gathered by the tracks' detection rows")
+        ignored = [k for k in ("augment", "retina_masks") if kwargs.get(k, False)]
+        if ignored:
+            logger.debug(f"track: {', '.join(ignored)} ignored")
+        t0 = time.perf_counter()
+        im, eps, imsrc = self._as_batch(source, int(kwargs.get("imgsz", 640)))
+        t1 = time.perf_counter()
+        eng = self.model.engine
+        bm = self.global_batch_max(im) if self.global_batch_max is not None and imsrc is None else None
+        B = im.shape[0]
+        names = self.model.names
+        out, cnt, idx = eng.track(im, cfg, persist=bool(persist), conf=float(kwargs.get("conf", 0.1)),
+                                  iou=float(kwargs.get("iou", 0.7)), max_det=int(kwargs.get("max_det", 300)),
+                                  classes=kwargs.get("classes", None), agnostic=bool(kwargs.get("agnostic_nms", False)),
+                                  in_eps=eps, batch_max=bm)
+        if imsrc is None:  # asynchronous, as predict(): the counts are read on first access
+            lazy = LazyCounts(cnt, torch.cuda.current_stream(im.device))
+            if kwargs.get("sync", False):
+                lazy[0]
+            speed = {"preprocess": (t1 - t0) * 1e3, "inference": (time.perf_counter() - t1) * 1e3, "postprocess": 0.0}
+            return [Results.from_batch(im, b, names, out, lazy, path=f"image{b}.jpg", speed=speed,
+                                       kpt_shape=eng.kpt_shape, tracked=True, det_idx=idx) for b in range(B)]
+        n = cnt.tolist()  # the device->host sync of an image-source call
+        from yolomi.preprocess import scale_boxes, scale_coords
+        for b in range(B):  # ops.scale_boxes / scale_coords after tracking, on the track rows
+            if n[b]:
+                scale_boxes(im.shape[2:], out[b, : n[b], :4], imsrc[2][b])
+                if self.task == "pose":
+                    K, nd = eng.kpt_shape
+                    scale_coords(im.shape[2:], out[b, : n[b], 7:7 + eng.nk].view(n[b], K, nd), imsrc[2][b])
+        speed = {"preprocess": (t1 - t0) * 1e3, "inference": (time.perf_counter() - t1) * 1e3, "postprocess": 0.0}
+        return [Results.from_image(imsrc[0][b], imsrc[1][b], names, out[b, : n[b], :7], speed=speed,
+                                   keypoints=(out[b, : n[b], 7:7 + eng.nk].reshape(n[b], *eng.kpt_shape)
+                                              if self.task == "pose" else None))
+                for b in range(B)]
+
     def _predict_embed(self, source, kwargs) -> List[torch.Tensor]:
         """predict(source, embed=[layers]): Ultralytics _predict_once's embed branch.  One 1-D fp32 device tensor per
         image (views of one fresh (B, sum C_i) buffer): the global-average-pooled outputs of the named layers,

@@ -49,7 +49,8 @@ class _TensorView:
 
 
 class Boxes(_TensorView):
-    """(n, 6) [x1, y1, x2, y2, conf, cls] detections of one image (upstream `ultralytics.engine.results.Boxes`)."""
+    """(n, 6) [x1, y1, x2, y2, conf, cls] detections of one image, or with tracking (n, 7) [x1, y1, x2, y2, id, conf,
+    cls] (upstream `ultralytics.engine.results.Boxes`)."""
 
     def __init__(self, boxes, orig_shape):
         if boxes.ndim == 1:
@@ -66,19 +67,19 @@ class Boxes(_TensorView):
 
     @property
     def conf(self):
-        return self.data[:, 4]
+        return self.data[:, -2]
 
     @property
     def cls(self):
-        return self.data[:, 5]
+        return self.data[:, -1]
 
     @property
     def id(self):
-        return None
+        return self.data[:, -3] if self.is_track else None
 
     @property
     def is_track(self):
-        return False
+        return self.data.shape[-1] == 7
 
     @property
     def xywh(self):
@@ -191,13 +192,18 @@ class Results:
     @classmethod
     def from_batch(cls, batch: torch.Tensor, b: int, names: Dict[int, str], dets: torch.Tensor, n,
                    path: str = "image0.jpg", speed=None, masks: Optional[torch.Tensor] = None,
-                   moff: int = 0, kpt_shape: Optional[tuple] = None) -> "Results":
+                   moff: int = 0, kpt_shape: Optional[tuple] = None, tracked: bool = False,
+                   det_idx: Optional[torch.Tensor] = None) -> "Results":
         """Image b of a predict() batch: boxes = dets[b, :n, :6], the input slice batch[b] and (Segment) the masks
         masks[moff : moff + n], all taken (as tensor views) on first access, so building the B Results of a call
         costs no tensor operations.  n: the count, or the call's LazyCounts (read from the device on first access).
         kpt_shape (Pose): (K, ndim); the keypoints are dets[b, :n, 6 : 6 + K·ndim], copied, clipped to the image
-        (scale_coords with equal shapes) and masked by visibility on first access."""
+        (scale_coords with equal shapes) and masked by visibility on first access.
+        tracked: dets holds track() rows, [x1, y1, x2, y2, id, conf, cls, extras]: the boxes take 7 columns and the
+        keypoints start at column 7; det_idx: the call's (B, max_det) detection row behind each track row."""
         r = cls.__new__(cls)
+        r._ncol = 7 if tracked else 6
+        r._didx = det_idx
         r._batch, r._b, r._dets, r._n = batch, b, dets, n
         r._orig_tensor_v = None
         r._orig_img = None
@@ -247,7 +253,7 @@ class Results:
     @property
     def boxes(self) -> "Boxes":
         if self._boxes is None:
-            self._boxes = Boxes(self._dets[self._b, : self._count, :6], self.orig_shape)
+            self._boxes = Boxes(self._dets[self._b, : self._count, :self._ncol], self.orig_shape)
         return self._boxes
 
     @boxes.setter
@@ -271,7 +277,7 @@ class Results:
         if self._kpts is None and getattr(self, "_ksrc", None) is not None:
             K, nd = self._ksrc
             n = self._count
-            k = self._dets[self._b, :n, 6:6 + K * nd].reshape(n, K, nd).clone()
+            k = self._dets[self._b, :n, self._ncol:self._ncol + K * nd].reshape(n, K, nd).clone()
             k[..., 0].clamp_(0, self.orig_shape[1])  # ops.scale_coords(shape, kpts, shape): gain 1, pad 0, clip
             k[..., 1].clamp_(0, self.orig_shape[0])
             self._kpts = Keypoints(k, self.orig_shape)
@@ -281,6 +287,13 @@ class Results:
     def keypoints(self, k):
         self._kpts = k
         self._ksrc = None
+
+    @property
+    def det_idx(self) -> Optional[torch.Tensor]:
+        """track() results of a tensor source: per box, the row of this frame's detection (in predict()'s order for
+        the same call) that fed the track; None otherwise."""
+        d = getattr(self, "_didx", None)
+        return d[self._b, : self._count] if d is not None else None
 
     @property
     def orig_img(self) -> np.ndarray:
@@ -320,11 +333,14 @@ class Results:
 
     def summary(self, normalize=False, decimals=5):
         out = []
+        is_track = self.boxes.is_track
         for row in self.boxes.data.tolist():
-            x1, y1, x2, y2, conf, c = row[:6]
+            (x1, y1, x2, y2), conf, c = row[:4], row[-2], row[-1]
             out.append({"name": self.names[int(c)], "class": int(c), "confidence": round(conf, decimals),
                         "box": {"x1": round(x1, decimals), "y1": round(y1, decimals), "x2": round(x2, decimals),
                                 "y2": round(y2, decimals)}})
+            if is_track:
+                out[-1]["track_id"] = int(row[-3])
         return out
 
     def __repr__(self):

@@ -75,6 +75,8 @@ class Engine:
         self._embed_tables = {}    # embed: layer tuple -> (ym_embed view table, total channels)
         self._embed_out = {}       # (B, layer tuple) -> the engine-owned (B, sum C) result
         self._embed_scratch = None  # rows / counts a tuning run of an embed-first shape may write
+        self._trackers = {}        # track: (B, cfg items, capacity) -> yolomi.lib.Tracker
+        self._live_tracker = None  # the key of the tracker the last track() call advanced
         self.tune_source: Dict[tuple, str] = {}
 
     def broadcast_weights(self, comm: int, root: int = 0):
@@ -203,6 +205,53 @@ class Engine:
             self._prepare_shape(x[:Bl], Bl, H, W, args, dets, counts, stream)
         self.rt.infer(x.data_ptr(), B, H, W, args, dets.data_ptr(), counts.data_ptr(), stream)
         return dets, counts
+
+    def track(self, x: torch.Tensor, cfg: Optional[Dict] = None, persist: bool = True, capacity: int = 0, **kw):
+        """run() followed by the tracker launch (csrc/ym_track.hip) on the same stream, with no host sync in between:
+        image b of the batch is video stream b of a ByteTrack state that lives in device memory.  cfg: the ByteTrack
+        parameters (yolomi.track.tracker_config; default bytetrack.yaml's); the engine owns one tracker per (B, cfg,
+        capacity).  persist=False resets the tracker first; persist=True continues the live one, and raises ValueError
+        when its batch size is not this call's.  A call whose cfg or capacity differs from the live tracker's at the
+        same batch size switches to that key's tracker and starts it over, persist=True or not: state is never carried
+        from one parameter set to another.  kw: run()'s thresholds (conf, iou, max_det <= 300, classes, agnostic,
+        in_eps, batch_max).  Returns (tracks, counts, idx): fresh tensors of this call — tracks (B, max_det, 7 + nm) fp32
+        rows [x1, y1, x2, y2, id, conf, cls, extras] in ascending id order, counts the (B,) int32 words behind them
+        (rows_buffer's layout, so LazyCounts reads them), idx (B, max_det) int32, the detection row behind each track
+        row.  Segment plans raise NotImplementedError (their masks would have to be re-gathered by idx)."""
+        from .lib import TRACK_DEFAULTS, TRACK_MAX_DET
+        if self.task == "segment":
+            raise NotImplementedError("tracking is offered for detect and pose plans; segment masks are not re-gathered")
+        full = dict(TRACK_DEFAULTS, **(cfg or {}))
+        max_det = int(kw.get("max_det", 300))
+        if not 1 <= max_det <= TRACK_MAX_DET:
+            raise ValueError(f"track: max_det {max_det} outside 1..{TRACK_MAX_DET}")
+        B = x.shape[0]
+        key = (B, tuple(sorted(full.items())), int(capacity))
+        live = self._live_tracker
+        if persist and live is not None and live[0] != B:
+            raise ValueError(f"track(persist=True): the live tracker follows {live[0]} streams, this batch has {B} "
+                             f"(image b of a batch is stream b); pass persist=False to start over")
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        trk = self._trackers.get(key)
+        if trk is None:
+            trk = self._trackers[key] = self.rt.track_create(B, full, capacity)
+        elif not persist or live != key:
+            trk.reset(stream)
+        self._live_tracker = key
+        dets, cnt = self.rows_buffer(B, max_det)
+        self.run(x, dets_out=dets, counts_after=True, **kw)
+        no = 7 + self.nm
+        flat = torch.empty((B * max_det * no + B,), dtype=torch.float32, device=self.device)
+        tracks, tcnt = flat[: B * max_det * no].view(B, max_det, no), flat[B * max_det * no:].view(torch.int32)
+        idx = torch.empty((B, max_det), dtype=torch.int32, device=self.device)
+        trk.update(dets.data_ptr(), 6 + self.nm, B, max_det, cnt.data_ptr(), tracks.data_ptr(), idx.data_ptr(),
+                   tcnt.data_ptr(), stream)
+        return tracks, tcnt, idx
+
+    def tracker_state(self):
+        """The live tracker's per-stream (frame_id, next id, activated tracked, lost, unconfirmed, drops), or None;
+        synchronous (tests, debugging)."""
+        return self._trackers[self._live_tracker].read_state() if self._live_tracker is not None else None
 
     def _tta_engines(self):
         """The three passes' engines (this one, then two more contexts holding the same packed model: a context has

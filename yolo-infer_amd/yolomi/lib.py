@@ -45,6 +45,15 @@ class EmbedView(C.Structure):
     _fields_ = [("buf", C.c_int), ("coff", C.c_int), ("C", C.c_int), ("reserved", C.c_int)]
 
 
+class TrackCfg(C.Structure):
+    """ym_track_cfg: bytetrack.yaml's parameters and the per-stream slot capacity (0: the library's default)."""
+    _fields_ = [("track_high_thresh", C.c_double), ("track_low_thresh", C.c_double), ("new_track_thresh", C.c_double),
+                ("match_thresh", C.c_double), ("track_buffer", C.c_int), ("fuse_score", C.c_int), ("capacity", C.c_int),
+                ("reserved", C.c_int)]
+
+
+TRACK_CAPACITY, TRACK_MAX_DET, TRACK_STATE_WORDS = 512, 300, 6  # include/yolomi.h YM_TRACK_*
+
 _lib = None
 
 
@@ -87,6 +96,11 @@ def load_library(path: os.PathLike = LIB_PATH):
         "ym_tta_nms": (I, [C.POINTER(P), I, I, I, C.POINTER(InferArgs), P, P, P]),
         "ym_tta_counts": (I, [P, C.POINTER(I), I]),
         "ym_embed": (I, [P, P, I, I, I, C.POINTER(InferArgs), C.POINTER(EmbedView), I, P, C.c_longlong, P]),
+        "ym_track_create": (I, [P, I, C.POINTER(TrackCfg), C.POINTER(P)]),
+        "ym_track_destroy": (None, [P]),
+        "ym_track_reset": (I, [P, P]),
+        "ym_track_update": (I, [P, P, I, I, I, P, P, P, P, P]),
+        "ym_track_read_state": (I, [P, C.POINTER(I), I]),
         "ym_broadcast_weights": (I, [P, P, I, P]),
         "ym_broadcast_weights_local": (I, [C.POINTER(P), I, I, P]),
         "ym_rccl_get_unique_id": (I, [C.POINTER(RcclId)]),
@@ -112,7 +126,8 @@ EXPORTED = ("ym_create", "ym_load_weights", "ym_broadcast_weights", "ym_broadcas
             "ym_letterbox", "ym_profile", "ym_profile_replay", "ym_tune", "ym_get_op_cfg", "ym_set_op_cfg", "ym_num_ops", "ym_op_name",
             "ym_num_buffers", "ym_buffer_info", "ym_read_buffer", "ym_sync", "ym_last_error", "ym_destroy",
             "ym_version", "ym_num_conv_cfgs", "ym_set_debug", "ym_read_scratch", "ym_kpt_shape",
-            "ym_tta_shape", "ym_tta_scale", "ym_tta_forward", "ym_tta_nms", "ym_tta_counts", "ym_embed")
+            "ym_tta_shape", "ym_tta_scale", "ym_tta_forward", "ym_tta_nms", "ym_tta_counts", "ym_embed",
+            "ym_track_create", "ym_track_destroy", "ym_track_reset", "ym_track_update", "ym_track_read_state")
 
 DBG_NMS, DBG_DW_MODE, DBG_DW_TILE, DBG_CHAIN, DBG_CHAIN_LAUNCHES, DBG_STEMFUSE, DBG_ATTN_KB = 1, 2, 3, 4, 5, 6, 7
 DBG_PAIRST, DBG_CONV_CFG = 8, 9  # value + 1 (0: default)  # ym_set_debug keys (include/yolomi.h)
@@ -257,6 +272,10 @@ class Runtime:
         _check(self.lib.ym_embed(self.ctx, C.c_void_p(x_ptr), B, H, W, C.byref(args), views, len(views),
                                  C.c_void_p(out_ptr), out_stride, C.c_void_p(stream)))
 
+    def track_create(self, streams: int, cfg: dict = None, capacity: int = 0) -> "Tracker":
+        """ym_track_create: the ByteTrack state of `streams` video streams on this context's device."""
+        return Tracker(self, streams, cfg, capacity)
+
     def profile(self, x_ptr, B, H, W, args, dets_ptr, counts_ptr, stream):
         ms = (C.c_float * self.n_ops)()
         _check(self.lib.ym_profile(self.ctx, C.c_void_p(x_ptr), B, H, W, C.byref(args), C.c_void_p(dets_ptr),
@@ -336,6 +355,54 @@ class Runtime:
         if self.ctx:
             self.lib.ym_destroy(self.ctx)
             self.ctx = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+TRACK_DEFAULTS = {"track_high_thresh": 0.25, "track_low_thresh": 0.1, "new_track_thresh": 0.25, "track_buffer": 30,
+                  "match_thresh": 0.8, "fuse_score": True}  # Ultralytics trackers/cfg/bytetrack.yaml
+
+
+class Tracker:
+    """One ym_tracker: `streams` independent ByteTrack states in device memory (include/yolomi.h ym_track_*)."""
+
+    def __init__(self, rt: Runtime, streams: int, cfg: Optional[dict] = None, capacity: int = 0):
+        self.lib = rt.lib
+        self.trk = C.c_void_p()
+        self.streams = int(streams)
+        full = dict(TRACK_DEFAULTS, **(cfg or {}))
+        c = TrackCfg()
+        c.track_high_thresh, c.track_low_thresh = float(full["track_high_thresh"]), float(full["track_low_thresh"])
+        c.new_track_thresh, c.match_thresh = float(full["new_track_thresh"]), float(full["match_thresh"])
+        c.track_buffer, c.fuse_score, c.capacity = int(full["track_buffer"]), int(bool(full["fuse_score"])), int(capacity)
+        _check(self.lib.ym_track_create(rt.ctx, self.streams, C.byref(c), C.byref(self.trk)))
+
+    def reset(self, stream: int):
+        _check(self.lib.ym_track_reset(self.trk, C.c_void_p(stream)))
+
+    def update(self, dets_ptr: int, det_stride: int, B: int, max_det: int, counts_ptr: int, tracks_ptr: int,
+               idx_ptr: int, track_counts_ptr: int, stream: int):
+        """ym_track_update: (B, max_det, det_stride) NMS rows + counts -> (B, max_det, det_stride + 1) track rows, the
+        (B, max_det) detection row of each, and the B track counts; asynchronous on `stream`."""
+        _check(self.lib.ym_track_update(self.trk, C.c_void_p(dets_ptr), det_stride, B, max_det, C.c_void_p(counts_ptr),
+                                        C.c_void_p(tracks_ptr), C.c_void_p(idx_ptr), C.c_void_p(track_counts_ptr),
+                                        C.c_void_p(stream)))
+
+    def read_state(self):
+        """Per stream (frame_id, next id, activated tracked, lost, unconfirmed, drops); synchronous."""
+        arr = (C.c_int * (TRACK_STATE_WORDS * self.streams))()
+        _check(self.lib.ym_track_read_state(self.trk, arr, self.streams))
+        v = list(arr)
+        return [tuple(v[i * TRACK_STATE_WORDS:(i + 1) * TRACK_STATE_WORDS]) for i in range(self.streams)]
+
+    def close(self):
+        if self.trk:
+            self.lib.ym_track_destroy(self.trk)
+            self.trk = C.c_void_p()
 
     def __del__(self):
         try:

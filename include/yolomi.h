@@ -332,6 +332,53 @@ int ym_track_update(ym_tracker* trk, const float* d_dets, int det_stride, int B,
                     float* d_tracks, int* d_idx, int* d_track_counts, void* stream);
 int ym_track_read_state(ym_tracker* trk, int* state, int n_streams);
 
+/* Annotated frames (Ultralytics Results.plot(): boxes, labels, masks, keypoints, skeletons, track ids), composited per
+ * pixel on the device by two launches (csrc/ym_annot.hip; the drawing rules are this project's own, exact and integer:
+ * DESIGN.md §17, csrc/ym_annot.h).  Works on any context, loaded or not: it reads rows, not activations.
+ * d_frames: the B canvases, B x 3 x H x W fp32 (frames_are_f32_chw = 1: converted as trunc(clamp(x * 255, 0, 255)), no
+ * channel flip) or B x H x W x 3 bytes; d_dets: B x max_det rows of args->det_stride floats, [x1 y1 x2 y2 conf cls
+ * extras] or with args->tracked [x1 y1 x2 y2 id conf cls extras], the first d_counts[b] of image b valid (device counts:
+ * no host value is needed); with args->K > 0 the first K * ndim extras are keypoints (x, y[, visibility]).
+ * d_masks (may be null): packed mask planes of mask_h x mask_w bytes (non-zero = inside), instance i of image b at
+ * d_masks + d_mask_offsets[b] + i * mask_h * mask_w for i < args->mask_cap (0: max_det); d_mask_geo (may be null: the
+ * identity (H, W, 0, 0)): B x (uh, uw, top, left) int32, the window of the mask plane the canvas maps to.
+ * d_names: args->nc x 24 bytes, class names (0-terminated when shorter); args->d_font: 95 glyphs x 11 row bytes
+ * (yolomi/font6x11.py), column gx of a row in bit 5 - gx.  d_out: B x H x W x 3 bytes.
+ * YM_EINVAL: a null pointer (frames, rows, counts, args, font, output; names with nc > 0; offsets with masks), B outside
+ * 1..65535, a side outside 1..YM_ANNOT_MAX_SIDE, line_width outside 1..255, kpt_radius outside 0..255, K outside 0..32,
+ * ndim not 2 | 3, det_stride below 6 + tracked + K * ndim, an unknown color_mode or switch bit.  Asynchronous on
+ * `stream`.  The records of a call live in ONE scratch buffer per context: calls on the same context must be
+ * stream-ordered (one stream, or the caller's own events between streams) — two calls in flight on different streams
+ * would overwrite each other's records; contexts are independent, so concurrent streams take a context each.  The
+ * scratch grows when B * max_det does, with hipDeviceSynchronize + hipFree + hipMalloc: a call that grows it must not
+ * be made while a stream is capturing (make one call of the largest B * max_det first; later calls allocate nothing). */
+#define YM_ANNOT_MAX_SIDE 8192
+#define YM_ANNOT_BOXES 1     /* flags: off hides outline and label */
+#define YM_ANNOT_LABELS 2    /* off hides the label */
+#define YM_ANNOT_CONF 4      /* off drops the confidence from the label text */
+#define YM_ANNOT_MASKS 8     /* off skips the mask blend */
+#define YM_ANNOT_KPT_LINE 16 /* off hides the limbs */
+#define YM_ANNOT_CLIP_KPTS 32 /* on: keypoints are clipped to [0, W] x [0, H] first, as predict()'s Results hold them */
+#define YM_ANNOT_COLOR_CLASS 0
+#define YM_ANNOT_COLOR_INSTANCE 1 /* by track id when tracked, else by row index */
+typedef struct {
+  int line_width; /* >= 1 (the caller applies upstream's default rule) */
+  int kpt_radius; /* 5 */
+  int flags;      /* YM_ANNOT_* switches */
+  int color_mode; /* YM_ANNOT_COLOR_* */
+  int tracked;    /* rows carry the id column */
+  int det_stride; /* floats per row */
+  int K, ndim;    /* keypoints per row (0: none), values per keypoint */
+  int nc;         /* rows of d_names */
+  int mask_cap;   /* mask planes per image (0: max_det) */
+  const void* d_font;
+  int reserved[2]; /* 0 */
+} ym_annotate_args;
+int ym_annotate(ym_ctx* ctx, const void* d_frames, int frames_are_f32_chw, int B, int H, int W, const float* d_dets,
+                int max_det, const int* d_counts, const unsigned char* d_masks, const long long* d_mask_offsets,
+                int mask_h, int mask_w, const int* d_mask_geo, const unsigned char* d_names, const ym_annotate_args* args,
+                unsigned char* d_out, void* stream);
+
 int ym_sync(ym_ctx* ctx);
 const char* ym_last_error(void);
 void ym_destroy(ym_ctx* ctx);

@@ -182,6 +182,7 @@ class YOLO11Model:
         except Exception as e:
             logger.error(f"Failed to load model: {e}")
             raise
+        engine.set_names(names)  # the labels of Results.plot() / Engine.annotate
         return _ModelHandle(sd, engine, names)
 
     # ------------------------------------------------------------------ hot path
@@ -191,11 +192,13 @@ class YOLO11Model:
         if isinstance(source, (list, tuple)) and source and all(isinstance(s, torch.Tensor) for s in source):
             source = torch.stack(list(source))
         if not isinstance(source, torch.Tensor):
-            from yolomi.preprocess import expand_sources, letterbox_batch
+            from yolomi.preprocess import batch_geometry, expand_sources, letterbox_batch
             imgs, paths = expand_sources(source)
             stream = torch.cuda.current_stream(self._dev).cuda_stream
-            im, shapes = letterbox_batch(self.model.engine.rt, imgs, self._dev, imgsz=imgsz, stream=stream)
-            return im, torch.finfo(torch.float32).eps, (imgs, paths, shapes)
+            geo = batch_geometry(imgs, imgsz)  # once: the letterbox kernel and the masks' window use the same values
+            im, shapes = letterbox_batch(self.model.engine.rt, imgs, self._dev, imgsz=imgsz, stream=stream, geo=geo)
+            return im, torch.finfo(torch.float32).eps, (imgs, paths, shapes,
+                                                        [(g[0], g[1], g[2], g[4]) for g in geo])  # (uh, uw, top, left)
         im = source
         if im.dim() != 4:
             if im.dim() != 3:
@@ -250,7 +253,7 @@ class YOLO11Model:
             speed = {"preprocess": (t1 - t0) * 1e3, "inference": (time.perf_counter() - t1) * 1e3,
                      "postprocess": 0.0}  # host time of the calls (the forward itself runs asynchronously)
             return [Results.from_batch(im, b, names, out, lazy, path=f"image{b}.jpg", speed=speed,
-                                       kpt_shape=eng.kpt_shape) for b in range(B)]
+                                       kpt_shape=eng.kpt_shape, annotator=eng) for b in range(B)]
         # the NMS kernel writes this call's rows straight into a fresh tensor (the Results keep views into it)
         out = torch.empty((B, max_det, 6 + eng.nm), dtype=torch.float32, device=im.device)
         dets, counts = run(im, conf=conf, iou=iou, max_det=max_det, classes=classes, agnostic=agnostic,
@@ -305,11 +308,11 @@ class YOLO11Model:
         speed = {"preprocess": (t1 - t0) * 1e3, "inference": (t2 - t1) * 1e3, "postprocess": 0.0}
         if masks is None:
             if imsrc is None:
-                return [Results.from_batch(im, b, names, out, n[b], path=f"image{b}.jpg", speed=speed)
+                return [Results.from_batch(im, b, names, out, n[b], path=f"image{b}.jpg", speed=speed, annotator=eng)
                         for b in range(B)]
             return [Results.from_image(imsrc[0][b], imsrc[1][b], names, out[b, : n[b], :6], speed=speed,
                                        keypoints=(out[b, : n[b], 6:6 + eng.nk].reshape(n[b], *eng.kpt_shape)
-                                                  if self.task == "pose" else None))
+                                                  if self.task == "pose" else None), annotator=eng)
                     for b in range(B)]
         res = []  # Segment: the predictor keeps only non-empty masks
         mb = masks.view(torch.bool).reshape(-1, H, W)  # the kernel writes 0/1 bytes: a bool view, no copy
@@ -317,7 +320,7 @@ class YOLO11Model:
             kb = keep[offs[b]:offs[b] + n[b]]
             if all(kb) and imsrc is None:  # the common case: boxes, masks and input slice as views taken on access
                 res.append(Results.from_batch(im, b, names, out, n[b], path=f"image{b}.jpg", speed=speed, masks=mb,
-                                              moff=offs[b]))
+                                              moff=offs[b], annotator=eng))
                 continue
             if all(kb):  # every kept detection has a mask pixel — views, no gathers
                 bx, mk = out[b, :n[b], :6], mb[offs[b]:offs[b] + n[b]]
@@ -326,9 +329,10 @@ class YOLO11Model:
                 bx = out[b].index_select(0, sel)[:, :6]
                 mk = mb[offs[b]:offs[b] + n[b]].index_select(0, sel)
             if imsrc is None:
-                res.append(Results(im[b], names, bx, path=f"image{b}.jpg", speed=speed, masks=mk))
-            else:
-                res.append(Results.from_image(imsrc[0][b], imsrc[1][b], names, bx, speed=speed, masks=mk))
+                res.append(Results(im[b], names, bx, path=f"image{b}.jpg", speed=speed, masks=mk, annotator=eng))
+            else:  # the masks are in letterboxed coordinates: plot() maps the image into its window of the plane
+                res.append(Results.from_image(imsrc[0][b], imsrc[1][b], names, bx, speed=speed, masks=mk,
+                                              annotator=eng, mask_geo=imsrc[3][b]))
         return res
 
     def track(self, source, persist: bool = False, tracker="bytetrack.yaml", **kwargs) -> List[Results]:
@@ -368,7 +372,8 @@ class YOLO11Model:
                 lazy[0]
             speed = {"preprocess": (t1 - t0) * 1e3, "inference": (time.perf_counter() - t1) * 1e3, "postprocess": 0.0}
             return [Results.from_batch(im, b, names, out, lazy, path=f"image{b}.jpg", speed=speed,
-                                       kpt_shape=eng.kpt_shape, tracked=True, det_idx=idx) for b in range(B)]
+                                       kpt_shape=eng.kpt_shape, tracked=True, det_idx=idx, annotator=eng)
+                    for b in range(B)]
         n = cnt.tolist()  # the device->host sync of an image-source call
         from yolomi.preprocess import scale_boxes, scale_coords
         for b in range(B):  # ops.scale_boxes / scale_coords after tracking, on the track rows
@@ -380,7 +385,7 @@ class YOLO11Model:
         speed = {"preprocess": (t1 - t0) * 1e3, "inference": (time.perf_counter() - t1) * 1e3, "postprocess": 0.0}
         return [Results.from_image(imsrc[0][b], imsrc[1][b], names, out[b, : n[b], :7], speed=speed,
                                    keypoints=(out[b, : n[b], 7:7 + eng.nk].reshape(n[b], *eng.kpt_shape)
-                                              if self.task == "pose" else None))
+                                              if self.task == "pose" else None), annotator=eng)
                 for b in range(B)]
 
     def _predict_embed(self, source, kwargs) -> List[torch.Tensor]:
@@ -443,16 +448,18 @@ class YOLO11Model:
             mk = pb[boffs[b]:boffs[b + 1]].view(n[b], *shapes[b])
             kb = keep[offs[b]:offs[b + 1]]
             if all(kb) and imsrc is None:  # boxes, masks and input slice as views taken on access
-                res.append(Results.from_batch(im, b, names, out, n[b], path=f"image{b}.jpg", speed=speed, masks=mk))
+                res.append(Results.from_batch(im, b, names, out, n[b], path=f"image{b}.jpg", speed=speed, masks=mk,
+                                              annotator=eng))
                 continue
             bx = out[b, :n[b], :6]
             if not all(kb):
                 sel = torch.tensor([i for i, k in enumerate(kb) if k], dtype=torch.long, device=out.device)
                 bx, mk = bx.index_select(0, sel), mk.index_select(0, sel)
             if imsrc is None:
-                res.append(Results(im[b], names, bx, path=f"image{b}.jpg", speed=speed, masks=mk))
+                res.append(Results(im[b], names, bx, path=f"image{b}.jpg", speed=speed, masks=mk, annotator=eng))
             else:
-                res.append(Results.from_image(imsrc[0][b], imsrc[1][b], names, bx, speed=speed, masks=mk))
+                res.append(Results.from_image(imsrc[0][b], imsrc[1][b], names, bx, speed=speed, masks=mk,
+                                              annotator=eng))
         return res
 
     def __call__(self, source, **kwargs):

@@ -174,8 +174,12 @@ class LazyCounts:
 class Results:
     def __init__(self, orig_tensor: Optional[torch.Tensor], names: Dict[int, str], boxes: torch.Tensor,
                  masks: Optional[torch.Tensor] = None, path: str = "image0.jpg", speed=None,
-                 keypoints: Optional[torch.Tensor] = None):
-        """keypoints: (n, K, 2 | 3), already in the original image's coordinates and clipped to it (scale_coords)."""
+                 keypoints: Optional[torch.Tensor] = None, annotator=None):
+        """keypoints: (n, K, 2 | 3), already in the original image's coordinates and clipped to it (scale_coords).
+        annotator: what plot() draws with — an Engine (anything with its `annotate` and `device`); predict() and track()
+        hand in their own."""
+        self._annotator = annotator
+        self._mask_geo = None
         self._orig_tensor = orig_tensor
         self._orig_img = None
         self.orig_shape = tuple(orig_tensor.shape[-2:]) if orig_tensor is not None else None
@@ -193,7 +197,7 @@ class Results:
     def from_batch(cls, batch: torch.Tensor, b: int, names: Dict[int, str], dets: torch.Tensor, n,
                    path: str = "image0.jpg", speed=None, masks: Optional[torch.Tensor] = None,
                    moff: int = 0, kpt_shape: Optional[tuple] = None, tracked: bool = False,
-                   det_idx: Optional[torch.Tensor] = None) -> "Results":
+                   det_idx: Optional[torch.Tensor] = None, annotator=None) -> "Results":
         """Image b of a predict() batch: boxes = dets[b, :n, :6], the input slice batch[b] and (Segment) the masks
         masks[moff : moff + n], all taken (as tensor views) on first access, so building the B Results of a call
         costs no tensor operations.  n: the count, or the call's LazyCounts (read from the device on first access).
@@ -202,6 +206,8 @@ class Results:
         tracked: dets holds track() rows, [x1, y1, x2, y2, id, conf, cls, extras]: the boxes take 7 columns and the
         keypoints start at column 7; det_idx: the call's (B, max_det) detection row behind each track row."""
         r = cls.__new__(cls)
+        r._annotator = annotator
+        r._mask_geo = None
         r._ncol = 7 if tracked else 6
         r._didx = det_idx
         r._batch, r._b, r._dets, r._n = batch, b, dets, n
@@ -222,10 +228,13 @@ class Results:
     @classmethod
     def from_image(cls, img_bgr: np.ndarray, path: str, names: Dict[int, str], boxes: torch.Tensor,
                    masks: Optional[torch.Tensor] = None, speed=None,
-                   keypoints: Optional[torch.Tensor] = None) -> "Results":
+                   keypoints: Optional[torch.Tensor] = None, annotator=None, mask_geo=None) -> "Results":
         """An image-file / ndarray source: `orig_img` is the HWC uint8 BGR image as loaded (cv2.imread order),
-        boxes (and keypoints) are in its coordinates (already mapped back by scale_boxes / scale_coords)."""
-        r = cls(None, names, boxes, masks=masks, path=path, speed=speed, keypoints=keypoints)
+        boxes (and keypoints) are in its coordinates (already mapped back by scale_boxes / scale_coords).
+        mask_geo: (uh, uw, top, left), the letterbox window of the mask plane this image occupies (plot() maps canvas
+        pixels into it); None when the masks are at the image's own resolution."""
+        r = cls(None, names, boxes, masks=masks, path=path, speed=speed, keypoints=keypoints, annotator=annotator)
+        r._mask_geo = tuple(int(v) for v in mask_geo) if mask_geo is not None else None
         r._orig_img = img_bgr
         r.orig_shape = tuple(img_bgr.shape[:2])
         r.boxes.orig_shape = r.orig_shape
@@ -308,7 +317,9 @@ class Results:
         return len(self.boxes)
 
     def _like(self, orig_tensor, boxes, masks, keypoints=None):
-        r = Results(orig_tensor, self.names, boxes, masks, self.path, self.speed, keypoints=keypoints)
+        r = Results(orig_tensor, self.names, boxes, masks, self.path, self.speed, keypoints=keypoints,
+                    annotator=getattr(self, "_annotator", None))
+        r._mask_geo = getattr(self, "_mask_geo", None)
         if orig_tensor is None:  # image-file / ndarray source: keep the loaded image and its shape
             r._orig_img = self._orig_img
             r.orig_shape = self.orig_shape
@@ -330,6 +341,41 @@ class Results:
         return self._like(self._orig_tensor.cpu() if self._orig_tensor is not None else None, self.boxes.data.cpu(),
                           self.masks.data.cpu() if self.masks is not None else None,
                           k.data.cpu().clone() if k is not None else None)
+
+    def plot(self, conf=True, line_width=None, kpt_radius=5, kpt_line=True, labels=True, boxes=True, masks=True,
+             img=None, color_mode="class", save=False, filename=None, **ignored) -> np.ndarray:
+        """Upstream `Results.plot`: the HWC uint8 image (channel order of `orig_img`) with boxes, labels, masks, keypoints,
+        skeletons and track ids drawn in — by the GPU annotator of the engine that made this Results (csrc/ym_annot.hip,
+        Engine.annotate; the drawing rules are DESIGN.md §17's, not OpenCV's).  img replaces the canvas; color_mode
+        "class" | "instance"; save / filename as upstream.  font, font_size, pil, im_gpu, probs, show and any other
+        keyword (upstream's txt_color, say) are accepted and ignored, with one log line, so ported calls keep working.
+        A hand-built Results needs `annotator=`: there is no host painter, so RuntimeError without one.
+        `orig_img`, the rows and the masks are left as they are."""
+        from yolomi.annotate import plot_results
+        if ignored:
+            import logging
+            logging.getLogger(__name__).info(f"plot: ignoring {sorted(ignored)}")
+        ann = getattr(self, "_annotator", None)
+        if ann is None:
+            raise RuntimeError("Results.plot() draws on the GPU: this Results was built by hand without annotator= "
+                               "(an Engine, e.g. model.model.engine); there is no host fallback")
+        out = plot_results(self, ann, conf=conf, line_width=line_width, kpt_radius=kpt_radius, kpt_line=kpt_line,
+                           labels=labels, boxes=boxes, masks=masks, img=img, color_mode=color_mode)
+        if save:
+            self._write(out, filename)
+        return out
+
+    def save(self, filename=None, **plot_args):
+        """Upstream `Results.save`: plot() written to `filename` (default: results_<name of path>) through Pillow, the
+        BGR canvas converted to RGB.  Returns the file name."""
+        return self._write(self.plot(**plot_args), filename)
+
+    def _write(self, bgr: np.ndarray, filename=None) -> str:
+        import os
+        from PIL import Image
+        filename = str(filename) if filename else f"results_{os.path.basename(self.path)}"
+        Image.fromarray(np.ascontiguousarray(bgr[..., ::-1])).save(filename)
+        return filename
 
     def summary(self, normalize=False, decimals=5):
         out = []

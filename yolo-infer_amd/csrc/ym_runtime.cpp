@@ -26,6 +26,7 @@
 #include "ym_embed.h"
 #include "ym_tta.h"
 #include "ym_track.h"
+#include "ym_annot.h"
 
 namespace {
 
@@ -244,6 +245,9 @@ struct ym_ctx {
   long long embed_ld = 0;
   float* d_embed = nullptr;
   size_t embed_floats = 0;
+  // annotated frames (ym_annotate): the records of the B x max_det detection slots, grown on demand
+  AnnotRec* d_annot = nullptr;
+  size_t annot_recs = 0;
   // test-time augmentation: ym_tta_forward launches the forward without its NMS stage; the merged candidate set and the
   // NMS scratch over it (ym_tta_nms) belong to the first pass's context and are rebuilt only when the shape changes
   struct TtaWs {
@@ -317,6 +321,7 @@ struct ym_ctx {
     if (d_misc) (void)hipFree(d_misc);
     if (tta.d) (void)hipFree(tta.d);
     if (d_embed) (void)hipFree(d_embed);
+    if (d_annot) (void)hipFree(d_annot);
     if (cap_stream) (void)hipStreamDestroy(cap_stream);
     for (int l = 0; l < kMaxLanes; ++l) {
       if (lane_streams[l]) (void)hipStreamDestroy(lane_streams[l]);
@@ -2164,6 +2169,68 @@ int ym_track_read_state(ym_tracker* t, int* state, int n_streams) {
     o[0] = h[b].frame_id; o[1] = h[b].issued + 1; o[2] = h[b].n_tracked;
     o[3] = h[b].n_lost; o[4] = h[b].n_unconfirmed; o[5] = h[b].drops;
   }
+  return YM_OK;
+}
+
+// ---------------------------------------------------------------------------------- annotated frames
+int ym_annotate(ym_ctx* c, const void* d_frames, int frames_are_f32_chw, int B, int H, int W, const float* d_dets,
+                int max_det, const int* d_counts, const unsigned char* d_masks, const long long* d_mask_offsets,
+                int mask_h, int mask_w, const int* d_mask_geo, const unsigned char* d_names, const ym_annotate_args* args,
+                unsigned char* d_out, void* stream) {
+  if (!c) return fail(YM_EINVAL, "null context");
+  if (!d_frames || !d_dets || !d_counts || !args || !d_out) return fail(YM_EINVAL, "ym_annotate: null pointer argument");
+  if (!args->d_font) return fail(YM_EINVAL, "ym_annotate: no font table (ym_annotate_args.d_font)");
+  if (B < 1 || B > 65535 || H < 1 || W < 1 || H > YM_ANNOT_MAX_SIDE || W > YM_ANNOT_MAX_SIDE)
+    return fail(YM_EINVAL, "ym_annotate: batch %d of %d x %d frames (1..65535 of 1..%d a side)", B, H, W, YM_ANNOT_MAX_SIDE);
+  if (max_det < 1 || max_det > (1 << 20)) return fail(YM_EINVAL, "ym_annotate: max_det %d", max_det);
+  if (args->line_width < 1 || args->line_width > kAnnotMaxLw || args->kpt_radius < 0 || args->kpt_radius > kAnnotMaxLw)
+    return fail(YM_EINVAL, "ym_annotate: line width %d (1..%d), keypoint radius %d (0..%d)", args->line_width, kAnnotMaxLw,
+                args->kpt_radius, kAnnotMaxLw);
+  if (args->K < 0 || args->K > kAnnotMaxK || (args->K > 0 && args->ndim != 2 && args->ndim != 3))
+    return fail(YM_EINVAL, "ym_annotate: keypoint shape (%d, %d) (K 0..%d, ndim 2 | 3)", args->K, args->ndim, kAnnotMaxK);
+  const int tracked = args->tracked ? 1 : 0;
+  if (args->det_stride < 6 + tracked + args->K * (args->K ? args->ndim : 0) || args->det_stride > (1 << 16))
+    return fail(YM_EINVAL, "ym_annotate: row stride %d below the %d values of a row with %d x %d keypoints",
+                args->det_stride, 6 + tracked + args->K * args->ndim, args->K, args->ndim);
+  if (args->color_mode != YM_ANNOT_COLOR_CLASS && args->color_mode != YM_ANNOT_COLOR_INSTANCE)
+    return fail(YM_EINVAL, "ym_annotate: color_mode %d", args->color_mode);
+  if (args->flags & ~(YM_ANNOT_BOXES | YM_ANNOT_LABELS | YM_ANNOT_CONF | YM_ANNOT_MASKS | YM_ANNOT_KPT_LINE | YM_ANNOT_CLIP_KPTS))
+    return fail(YM_EINVAL, "ym_annotate: unknown switch bits 0x%x", args->flags);
+  if (args->nc < 0 || (args->nc > 0 && !d_names)) return fail(YM_EINVAL, "ym_annotate: %d class names, null table", args->nc);
+  if (d_masks && (!d_mask_offsets || mask_h < 1 || mask_w < 1 || mask_h > YM_ANNOT_MAX_SIDE || mask_w > YM_ANNOT_MAX_SIDE ||
+                  args->mask_cap < 0))
+    return fail(YM_EINVAL, "ym_annotate: masks of %d x %d bytes, offsets %p, cap %d", mask_h, mask_w,
+                (const void*)d_mask_offsets, args->mask_cap);
+  HIPCK(hipSetDevice(c->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const size_t need = (size_t)B * max_det;
+  if (need > c->annot_recs) {  // (an earlier call may still read the old records)
+    if (c->d_annot) {
+      HIPCK(hipDeviceSynchronize());
+      HIPCK(hipFree(c->d_annot));
+      c->d_annot = nullptr;
+      c->annot_recs = 0;
+    }
+    const hipError_t e = hipMalloc(&c->d_annot, need * sizeof(AnnotRec));
+    if (e != hipSuccess) {
+      c->d_annot = nullptr;
+      return fail(YM_ENOMEM, "ym_annotate: %zu records: %s", need, hipGetErrorString(e));
+    }
+    c->annot_recs = need;
+  }
+  AnnotArgs a{};
+  a.st.H = H; a.st.W = W; a.st.lw = args->line_width; a.st.radius = args->kpt_radius; a.st.flags = args->flags;
+  a.st.by_instance = args->color_mode == YM_ANNOT_COLOR_INSTANCE; a.st.tracked = tracked;
+  a.st.K = args->K; a.st.ndim = args->K ? args->ndim : 0; a.st.nc = args->nc;
+  a.st.det_stride = args->det_stride; a.st.max_det = max_det;
+  a.frames = d_frames; a.f32_chw = frames_are_f32_chw ? 1 : 0; a.B = B;
+  a.dets = d_dets; a.counts = d_counts;
+  a.masks = d_masks; a.mask_offsets = d_mask_offsets; a.mask_h = mask_h; a.mask_w = mask_w;
+  a.mask_cap = args->mask_cap ? args->mask_cap : max_det; a.mask_geo = d_mask_geo;
+  a.names = d_names; a.font = static_cast<const unsigned char*>(args->d_font);
+  a.recs = c->d_annot; a.out = d_out;
+  const hipError_t e = ym_launch_annotate(a, st);
+  if (e != hipSuccess) return fail(YM_EHIP, "annotate kernels: %s", hipGetErrorString(e));
   return YM_OK;
 }
 

@@ -8,7 +8,8 @@ detection); here one (n, 6) copy per Results feeds all three formats:
   * csv: header `class_id,confidence,x1,y1,x2,y2`, one row per detection.
 Values are the fp32 tensor values (printed through Python floats, as the reference's numpy float32 -> float).
 Pose results: the json format adds each detection's "keypoints" ([[x, y(, visibility)], ...]), and `draw_keypoints`
-paints them on an image.
+paints them on an image.  `draw_detections` (the reference's signature, utils/visualization.py:18) returns the image
+with boxes, labels, masks and skeletons drawn in by the GPU annotator behind `Results.plot`.
 """
 from __future__ import annotations
 
@@ -52,6 +53,24 @@ def draw_keypoints(image: np.ndarray, results: Any, radius: int = 2, color=(0, 2
         xi, yi = int(round(float(x))), int(round(float(y)))
         out[max(yi - radius, 0):min(yi + radius + 1, h), max(xi - radius, 0):min(xi + radius + 1, w)] = color
     return out
+
+
+def draw_detections(image: np.ndarray, results: Any, class_names=None, line_thickness: int = 2, font_scale: float = 0.5,
+                    font_thickness: int = 1) -> np.ndarray:
+    """The reference's `draw_detections(image, results, class_names, line_thickness, ...)`: a copy of the HWC uint8 BGR
+    `image` with the results drawn in — `results.plot(img=image, line_width=line_thickness)`, so the drawing runs on the
+    GPU and follows Results.plot's rules.  class_names (a dict or a list) replaces the results' own names for this
+    picture; font_scale and font_thickness have no meaning for the fixed bitmap font and are ignored.  results may be
+    one Results or predict()'s list (its first element); None returns a copy of the image."""
+    if isinstance(results, (list, tuple)):
+        results = results[0] if results else None
+    if results is None:
+        return np.array(image, copy=True)
+    if class_names:
+        import copy
+        results = copy.copy(results)
+        results.names = dict(class_names) if isinstance(class_names, dict) else dict(enumerate(class_names))
+    return results.plot(img=image, line_width=int(line_thickness))
 
 
 def save_detection_results(results: Any, output_path: str, format: str = "txt") -> None:

@@ -78,6 +78,8 @@ class Engine:
         self._trackers = {}        # track: (B, cfg items, capacity) -> yolomi.lib.Tracker
         self._live_tracker = None  # the key of the tracker the last track() call advanced
         self.tune_source: Dict[tuple, str] = {}
+        self.names = {i: f"class{i}" for i in range(nc or 0)}  # annotate's label names (set_names)
+        self._annot_tables = None  # annotate: (device font bytes, device name table, nc), uploaded once
 
     def broadcast_weights(self, comm: int, root: int = 0):
         """The root's side of the RCCL weight broadcast (ym_broadcast_weights): every rank of `comm` calls it or
@@ -406,6 +408,31 @@ class Engine:
             self._prepare_shape(x, B, H, W, args, self._embed_scratch[0], self._embed_scratch[1], stream)
         self.rt.embed(x.data_ptr(), B, H, W, args, views, out.data_ptr(), out.stride(0), stream)
         return out[:B, :width]
+
+    def set_names(self, names: Dict[int, str]):
+        """The class names annotate() writes into labels (YOLO11Model hands in its own)."""
+        self.names = dict(names)
+        self._annot_tables = None
+
+    def annotate(self, frames: torch.Tensor, dets: torch.Tensor, counts: torch.Tensor, *, masks=None,
+                 mask_offsets=None, mask_geo=None, mask_cap=None, tracked=False, out=None, kpt_shape=None, **switches):
+        """Annotated frames of a whole batch (csrc/ym_annot.hip): the (B, H, W, 3) uint8 device tensor of
+        `frames` with boxes, labels, masks, keypoints and skeletons drawn in, as Results.plot() draws one image.
+        frames: (B, 3, H, W) fp32 (predict's batch: converted like Results.orig_img, no channel flip) or (B, H, W, 3)
+        uint8; dets / counts: predict's or track's row buffers as they are, (B, max_det, stride) fp32 and (B,) int32 —
+        tracked=True for track's 7-column rows.  masks: (B, cap, mh, mw) uint8 / bool mask slots (instance i of image
+        b at masks[b, i]), or packed planes with mask_offsets ((B,) int64 first byte per image) and mask_cap planes per
+        image; mask_geo: (B, 4) int32 (uh, uw, top, left), default the identity.  kpt_shape: (K, ndim) of the rows'
+        keypoints (default: this engine's, for a pose plan).  switches: line_width (default upstream's rule from H and
+        W), kpt_radius, conf, labels, boxes, masks_on (the `masks` switch of plot), kpt_line, color_mode, names (a class-name
+        dict other than set_names's, uploaded for this call), clip_kpts (default True: keypoints are clipped to the
+        canvas first, as predict()'s Results hold them, so raw rows draw what Results.plot draws; plot passes False).
+        Enqueued on the current stream: no tensor value is read on the host and nothing synchronises.  Calls of one
+        engine must be stream-ordered (the records of a call live in one scratch buffer of its context); the first call
+        of a larger B * max_det grows that buffer with a device synchronisation, so it cannot be captured."""
+        from .annotate import annotate_batch
+        return annotate_batch(self, frames, dets, counts, masks=masks, mask_offsets=mask_offsets, mask_geo=mask_geo,
+                              mask_cap=mask_cap, tracked=tracked, out=out, kpt_shape=kpt_shape, **switches)
 
     def profile(self, x: torch.Tensor, **kw):
         B, _, H, W = x.shape

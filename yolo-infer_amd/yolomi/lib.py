@@ -52,6 +52,17 @@ class TrackCfg(C.Structure):
                 ("reserved", C.c_int)]
 
 
+class AnnotateArgs(C.Structure):
+    """ym_annotate_args: the drawing switches and the row layout of one ym_annotate call."""
+    _fields_ = [("line_width", C.c_int), ("kpt_radius", C.c_int), ("flags", C.c_int), ("color_mode", C.c_int),
+                ("tracked", C.c_int), ("det_stride", C.c_int), ("K", C.c_int), ("ndim", C.c_int), ("nc", C.c_int),
+                ("mask_cap", C.c_int), ("d_font", C.c_void_p), ("reserved", C.c_int * 2)]
+
+
+ANNOT_BOXES, ANNOT_LABELS, ANNOT_CONF, ANNOT_MASKS, ANNOT_KPT_LINE, ANNOT_CLIP_KPTS = 1, 2, 4, 8, 16, 32  # include/yolomi.h YM_ANNOT_*
+ANNOT_COLOR_MODES = {"class": 0, "instance": 1}
+ANNOT_NAME_BYTES = 24
+
 TRACK_CAPACITY, TRACK_MAX_DET, TRACK_STATE_WORDS = 512, 300, 6  # include/yolomi.h YM_TRACK_*
 
 _lib = None
@@ -101,6 +112,7 @@ def load_library(path: os.PathLike = LIB_PATH):
         "ym_track_reset": (I, [P, P]),
         "ym_track_update": (I, [P, P, I, I, I, P, P, P, P, P]),
         "ym_track_read_state": (I, [P, C.POINTER(I), I]),
+        "ym_annotate": (I, [P, P, I, I, I, I, P, I, P, P, P, I, I, P, P, C.POINTER(AnnotateArgs), P, P]),
         "ym_broadcast_weights": (I, [P, P, I, P]),
         "ym_broadcast_weights_local": (I, [C.POINTER(P), I, I, P]),
         "ym_rccl_get_unique_id": (I, [C.POINTER(RcclId)]),
@@ -127,7 +139,7 @@ EXPORTED = ("ym_create", "ym_load_weights", "ym_broadcast_weights", "ym_broadcas
             "ym_num_buffers", "ym_buffer_info", "ym_read_buffer", "ym_sync", "ym_last_error", "ym_destroy",
             "ym_version", "ym_num_conv_cfgs", "ym_set_debug", "ym_read_scratch", "ym_kpt_shape",
             "ym_tta_shape", "ym_tta_scale", "ym_tta_forward", "ym_tta_nms", "ym_tta_counts", "ym_embed",
-            "ym_track_create", "ym_track_destroy", "ym_track_reset", "ym_track_update", "ym_track_read_state")
+            "ym_track_create", "ym_track_destroy", "ym_track_reset", "ym_track_update", "ym_track_read_state", "ym_annotate")
 
 DBG_NMS, DBG_DW_MODE, DBG_DW_TILE, DBG_CHAIN, DBG_CHAIN_LAUNCHES, DBG_STEMFUSE, DBG_ATTN_KB = 1, 2, 3, 4, 5, 6, 7
 DBG_PAIRST, DBG_CONV_CFG = 8, 9  # value + 1 (0: default)  # ym_set_debug keys (include/yolomi.h)
@@ -271,6 +283,24 @@ class Runtime:
         """ym_embed: the forward up to the last named buffer, then the pooled means into (B, out_stride) floats."""
         _check(self.lib.ym_embed(self.ctx, C.c_void_p(x_ptr), B, H, W, C.byref(args), views, len(views),
                                  C.c_void_p(out_ptr), out_stride, C.c_void_p(stream)))
+
+    @staticmethod
+    def annotate_args(line_width, kpt_radius, flags, color_mode, tracked, det_stride, K, ndim, nc, mask_cap,
+                      font_ptr) -> AnnotateArgs:
+        a = AnnotateArgs()
+        a.line_width, a.kpt_radius, a.flags, a.color_mode = int(line_width), int(kpt_radius), int(flags), int(color_mode)
+        a.tracked, a.det_stride, a.K, a.ndim, a.nc = int(bool(tracked)), int(det_stride), int(K), int(ndim), int(nc)
+        a.mask_cap, a.d_font = int(mask_cap), font_ptr or None
+        return a
+
+    def annotate(self, frames_ptr: int, f32_chw: bool, B: int, H: int, W: int, dets_ptr: int, max_det: int,
+                 counts_ptr: int, masks_ptr: int, mask_offsets_ptr: int, mask_h: int, mask_w: int, mask_geo_ptr: int,
+                 names_ptr: int, args: AnnotateArgs, out_ptr: int, stream: int):
+        """ym_annotate: the B annotated frames into (B, H, W, 3) bytes; asynchronous on `stream`."""
+        V = C.c_void_p
+        _check(self.lib.ym_annotate(self.ctx, V(frames_ptr), int(bool(f32_chw)), B, H, W, V(dets_ptr), max_det,
+                                    V(counts_ptr), V(masks_ptr), V(mask_offsets_ptr), mask_h, mask_w, V(mask_geo_ptr),
+                                    V(names_ptr), C.byref(args), V(out_ptr), V(stream)))
 
     def track_create(self, streams: int, cfg: dict = None, capacity: int = 0) -> "Tracker":
         """ym_track_create: the ByteTrack state of `streams` video streams on this context's device."""

@@ -75,11 +75,18 @@ def expand_sources(source) -> Tuple[List[np.ndarray], List[str]]:
     return imgs, paths
 
 
-def letterbox_batch(rt, imgs: Sequence[np.ndarray], device: torch.device, imgsz: int = 640, stride: int = 32,
-                    stream: int = 0) -> Tuple[torch.Tensor, List[Tuple[int, int]]]:
-    """The predictor's preprocessed batch (B, 3, Hn, Wn) fp32 on `device`, built on the GPU."""
+def batch_geometry(imgs: Sequence[np.ndarray], imgsz: int = 640, stride: int = 32) -> List[Tuple]:
+    """letterbox_geometry of every image of a predict() batch (auto only when all images share one shape)."""
     same = len({im.shape for im in imgs}) == 1
-    geo = [letterbox_geometry(im.shape[0], im.shape[1], (imgsz, imgsz), auto=same, stride=stride) for im in imgs]
+    return [letterbox_geometry(im.shape[0], im.shape[1], (imgsz, imgsz), auto=same, stride=stride) for im in imgs]
+
+
+def letterbox_batch(rt, imgs: Sequence[np.ndarray], device: torch.device, imgsz: int = 640, stride: int = 32,
+                    stream: int = 0, geo: Sequence[Tuple] = None) -> Tuple[torch.Tensor, List[Tuple[int, int]]]:
+    """The predictor's preprocessed batch (B, 3, Hn, Wn) fp32 on `device`, built on the GPU.  geo: the images'
+    batch_geometry when the caller already has it (predict keeps it for the masks' window), else computed here."""
+    if geo is None:
+        geo = batch_geometry(imgs, imgsz, stride)
     uh, uw, t, b, l, r = geo[0]
     Hn, Wn = uh + t + b, uw + l + r
     out = torch.empty((len(imgs), 3, Hn, Wn), dtype=torch.float32, device=device)

@@ -387,6 +387,13 @@ int ym_version(void);
  * YM_EINVAL otherwise): the id space of the ym_get_op_cfg / ym_set_op_cfg tables, so a cached table is reused only
  * by a library with the same catalogue. */
 int ym_num_conv_cfgs(int dtype);
+/* Tests: whether the pinned configuration of each op (ym_set_op_cfg, ym_tune) was the kernel that ran in the last
+ * forward this context launched eagerly or captured, which must have been a B x H x W one (else YM_ESTATE).
+ * out: 2 * ym_num_ops ints.  out[2i]: 1 the kernel of op i's id ran, 0 the launcher fell back (the heuristic tile, the
+ * first variant that takes the shape, or a fused pair's two convs), -1 op i is not a conv, is the stem, has no id
+ * pinned, was not launched, or the plan is int8 / fp8 (not tracked).  For a fused pair whose id is a two-launch one
+ * out[2i] and out[2i + 1] are those values of its first and second conv; out[2i + 1] is -1 otherwise. */
+int ym_get_op_cfg_taken(ym_ctx* ctx, int B, int H, int W, int* out, int n);
 
 /* Process-wide debug switches for tests and A/B runs (not part of the reference interface; defaults 0), read when a
  * kernel is launched (so at graph capture for replayed forwards): YM_DBG_NMS (9 = the NMS kernel's per-box path
@@ -405,6 +412,10 @@ int ym_num_conv_cfgs(int dtype);
 #define YM_DBG_ATTN_KB 7 /* 1: x3 attention loads K fragments 8 key tiles per round trip; 0: all tiles at once */
 #define YM_DBG_PAIRST 8 /* x3 lane-pair epilogue store family mask + 1 (0: the default mask 21) */
 #define YM_DBG_CONV_CFG 9 /* a forced conv tile configuration id + 1 for untuned ops (0: the heuristic) */
+/* tests: 1 + the index of the last op an eager forward launches (0: a whole forward).  Every op of a stopped forward is
+ * its own launch and no decode / NMS output is written, so a test can read a view that a later op overwrites.  Eager
+ * only: while it is set, a call with args->use_graph returns YM_EINVAL (a stopped forward is never captured). */
+#define YM_DBG_STOP 10
 int ym_set_debug(int key, int value);
 
 #ifdef __cplusplus

@@ -315,6 +315,10 @@ def _force_cfg(eng, x, cfg):
 
 HALO_FIRST = STREAM_FIRST + 43  # then csrc/ym_conv_halo.hip: 12 halo-tile 3x3 configs
 HALO_CFGS = list(range(HALO_FIRST, HALO_FIRST + 12))
+# the two stride-2 halo tiles of 320 / 640 pixel slots (csrc/ym_conv_halo.hip YM_HALO_CFGS 9, 10): at 640x640 their three
+# LDS stages of (TH - 1) * 2 + 3 input rows pass kMaxLds on every stride-2 map (halo_geom's last line), so no op takes
+# them at this test's shape; the small maps of tests/test_gpu_conv_ops.py do
+HALO_NOT_AT_640 = (HALO_FIRST + 9, HALO_FIRST + 10)
 
 
 @pytest.mark.parametrize("cfg", list(range(DMA_FIRST, HALO_FIRST)) + HALO_CFGS)
@@ -329,6 +333,10 @@ def test_dma_conv_configs_match_oracle(cfg):
     try:
         _force_cfg(eng, xd, cfg)
         eng.run(xd, use_graph=False)
+        # the id ran on at least one op, or is on the list of ids that no op of this plan takes
+        from tests.test_gpu_conv_ops import NOT_ON_YOLO11N
+        ran = any(t[0] == 1 for t in eng.rt.get_op_cfg_taken(2, 640, 640))
+        assert ran or cfg in NOT_ON_YOLO11N["f16"] or cfg in HALO_NOT_AT_640, cfg
         for b in eng.graph.buffers:
             if b.name.startswith("L") and b.name[1:].isdigit() and int(b.name[1:]) in ex["saved"]:
                 ref = ex["saved"][int(b.name[1:])].permute(0, 2, 3, 1)

@@ -551,8 +551,11 @@ struct MaskNativeArgs {                 // ym_mask_native.hip: process_mask_nati
 
 // ------------------------------------------------------------------------------------------------------------
 // Host-side launchers (defined in the .hip translation units).
-// cfg < 0: heuristic; strict: an inapplicable cfg is an error (else the heuristic runs)
-hipError_t ym_launch_conv(int dtype, int out_f32, const ConvArgs& a, int cfg, hipStream_t st, bool strict = false);
+// cfg < 0: heuristic; strict: an inapplicable cfg is an error (else the heuristic runs).  taken (tests; may be null):
+// 1 when the kernel of `cfg` is the one launched, 0 when the launcher fell back (the heuristic tile, the first variant
+// that takes the shape), -1 when cfg < 0 or the plan is int8 / fp8 (not tracked)
+hipError_t ym_launch_conv(int dtype, int out_f32, const ConvArgs& a, int cfg, hipStream_t st, bool strict = false,
+                          int* taken = nullptr);
 int ym_conv_num_cfgs();
 hipError_t ym_launch_dwconv(int dtype, const DwArgs& a, hipStream_t st);
 hipError_t ym_launch_sppf(int dtype, const PoolArgs& a, hipStream_t st);
@@ -589,7 +592,8 @@ int ym_conv_bneck_x3_num_cfgs();  // x3-only Bottleneck variants (launch indices
 hipError_t ym_launch_conv_stream(int out_f32, const ConvArgs& a, int i, hipStream_t st);  // f16 1x1 only
 int ym_conv_stream_num_cfgs();
 hipError_t ym_launch_conv_halo(int out_f32, const ConvArgs& a, int i, hipStream_t st);  // f16 3x3 halo tiles
-hipError_t ym_launch_conv_dwpw(int dtype, int out_f32, const ConvArgs& a, int cfg, hipStream_t st, bool strict);
+hipError_t ym_launch_conv_dwpw(int dtype, int out_f32, const ConvArgs& a, int cfg, hipStream_t st, bool strict,
+                               int* taken = nullptr);  // taken: as ym_launch_conv's
 int ym_conv_dwpw_num_cfgs();  // fused depthwise → 1x1 (ConvArgs::dw_w): its own cfg id space 0 .. n-1
 int ym_conv_halo_num_cfgs();
 hipError_t ym_launch_masks(const MaskArgs& a, hipStream_t st);

@@ -711,9 +711,16 @@ int ym_conv_num_cfgs_dt(int dtype) {
   return ym_conv_num_cfgs() + (dtype == YM_DT_X3 ? ym_conv_dma_x3_num_cfgs() + ym_conv_bneck_x3_num_cfgs() : 0);
 }
 
-hipError_t ym_launch_conv(int dtype, int out_f32, const ConvArgs& a, int cfg, hipStream_t st, bool strict) {
+hipError_t ym_launch_conv(int dtype, int out_f32, const ConvArgs& a, int cfg, hipStream_t st, bool strict,
+                          int* taken) {
   // a depthwise-fused 1x1 (csrc/ym_conv_dwpw.hip) runs on its own kernel only: no other family computes the depthwise
-  if (a.dw_w) return ym_launch_conv_dwpw(dtype, out_f32, a, cfg, st, strict);
+  if (a.dw_w) return ym_launch_conv_dwpw(dtype, out_f32, a, cfg, st, strict, taken);
+  // *taken: 0 (a pinned cfg fell back) until the launch of cfg's own kernel succeeds (`ran`)
+  if (taken) *taken = (cfg >= 0 && !ym_dt_q8(dtype)) ? 0 : -1;
+  auto ran = [taken](hipError_t e) {
+    if (taken && e == hipSuccess) *taken = 1;
+    return e;
+  };
   int kind;
   if (a.nchw) kind = (a.k == 3 && a.Cin8 == 1) ? 0 : -1;
   else if (a.k == 1 && a.s == 1) kind = 1;
@@ -729,10 +736,10 @@ hipError_t ym_launch_conv(int dtype, int out_f32, const ConvArgs& a, int cfg, hi
     const int nb = ym_conv_bneck_num_cfgs();
     const int xb = ym_conv_num_cfgs() + ym_conv_dma_x3_num_cfgs();  // x3-only Bottleneck ids
     if (cfg >= bb && cfg < bb + nb) {
-      const hipError_t e = ym_launch_conv_bneck(out_f32, a, cfg - bb, st);
+      const hipError_t e = ran(ym_launch_conv_bneck(out_f32, a, cfg - bb, st));
       if (e != hipErrorInvalidValue || strict) return e;
     } else if (dtype == YM_DT_X3 && cfg >= xb && cfg < xb + ym_conv_bneck_x3_num_cfgs()) {
-      const hipError_t e = ym_launch_conv_bneck(out_f32, a, nb + cfg - xb, st);
+      const hipError_t e = ran(ym_launch_conv_bneck(out_f32, a, nb + cfg - xb, st));
       if (e != hipErrorInvalidValue || strict) return e;
     } else if (strict) {
       return hipErrorInvalidValue;
@@ -748,16 +755,16 @@ hipError_t ym_launch_conv(int dtype, int out_f32, const ConvArgs& a, int cfg, hi
     if (dtype != YM_DT_F16 && dtype != YM_DT_X3) return hipErrorInvalidValue;
     const int bb = kNumAllCfg + ym_conv_dma_num_cfgs() + ym_conv_stream_num_cfgs() + ym_conv_halo_num_cfgs();
     if (cfg >= bb && cfg < bb + ym_conv_bneck_num_cfgs()) {
-      const hipError_t e = ym_launch_conv_bneck(out_f32, a, cfg - bb, st);
+      const hipError_t e = ran(ym_launch_conv_bneck(out_f32, a, cfg - bb, st));
       if (e != hipErrorInvalidValue || strict) return e;
     }
     const int sbase = kNumAllCfg + ym_conv_dma_num_cfgs(), ns = ym_conv_stream_num_cfgs();
     if (dtype == YM_DT_X3 && a.k2 == 1 && cfg >= kNumAllCfg && cfg < sbase) {  // LDS-DMA ids: the fused-epilogue GEMM
-      const hipError_t e = ym_launch_conv_dma_fuse(out_f32, a, cfg - kNumAllCfg, st);
+      const hipError_t e = ran(ym_launch_conv_dma_fuse(out_f32, a, cfg - kNumAllCfg, st));
       if (e != hipErrorInvalidValue || strict) return e;
     }
     if (cfg >= sbase && cfg < sbase + ns) {
-      const hipError_t e = ym_launch_conv_stream(out_f32, a, cfg - sbase, st);
+      const hipError_t e = ran(ym_launch_conv_stream(out_f32, a, cfg - sbase, st));
       if (e != hipErrorInvalidValue || strict) return e;
     } else if (strict) {
       return hipErrorInvalidValue;
@@ -770,7 +777,7 @@ hipError_t ym_launch_conv(int dtype, int out_f32, const ConvArgs& a, int cfg, hi
   }
   if (dtype == YM_DT_X3 && cfg >= ym_conv_num_cfgs()) {  // the x3-only LDS-DMA configurations (and, past them, the
                                                           // x3-only Bottleneck ids: inapplicable to a single conv)
-    const hipError_t e = ym_launch_conv_dma(out_f32, a, ym_conv_dma_num_cfgs() + cfg - ym_conv_num_cfgs(), st);
+    const hipError_t e = ran(ym_launch_conv_dma(out_f32, a, ym_conv_dma_num_cfgs() + cfg - ym_conv_num_cfgs(), st));
     if (e != hipErrorInvalidValue || strict) return e;
     cfg = -1;
   }
@@ -784,19 +791,23 @@ hipError_t ym_launch_conv(int dtype, int out_f32, const ConvArgs& a, int cfg, hi
       e = i < ndma ? ym_launch_conv_dma(out_f32, a, i, st)
                    : (i < ndma + nstr ? ym_launch_conv_stream(out_f32, a, i - ndma, st)
                                       : ym_launch_conv_halo(out_f32, a, i - ndma - nstr, st));
+      ran(e);
     }
     if (e != hipErrorInvalidValue || strict) return e;
     cfg = -1;
   }
   int id = (cfg >= 0 && cfg < kNumAllCfg) ? cfg : choose_cfg(a);
   if (id >= kNumCfg && dtype == YM_DT_F32) id = choose_cfg(a);  // LDS variants: f16 and x3 plans
-  if (dtype == YM_DT_F16) return out_f32 ? launch_id<f16, float>(id, a, kind, st) : launch_id<f16, f16>(id, a, kind, st);
+  const bool pinned = id == cfg;  // (else the heuristic's tile)
+  auto ran_id = [&](hipError_t e) { return pinned ? ran(e) : e; };
+  if (dtype == YM_DT_F16)
+    return ran_id(out_f32 ? launch_id<f16, float>(id, a, kind, st) : launch_id<f16, f16>(id, a, kind, st));
   if (dtype == YM_DT_X3) {
     auto go = [&](int i) { return out_f32 ? launch_id<x3_t, float>(i, a, kind, st) : launch_id<x3_t, P2>(i, a, kind, st); };
-    const hipError_t e = go(id);
+    const hipError_t e = ran_id(go(id));
     // an LDS tile whose 64-deep stage does not divide this op's K: the tuner skips it (strict), a pinned table
     // falls back to the heuristic direct-to-register tile
     return (e == hipErrorInvalidValue && !strict && id >= kNumCfg) ? go(choose_cfg(a)) : e;
   }
-  return launch_id<float, float>(id, a, kind, st);
+  return ran_id(launch_id<float, float>(id, a, kind, st));
 }

@@ -1688,12 +1688,13 @@ hipError_t ym_launch_input_max(const float* x, long n, float* ctl, float* out, h
 // the setter — a launch reads an atomic instead of calling getenv (getenv per launch is not thread-safe
 // against setenv and costs time on every eager forward)
 namespace {
-constexpr int kDbgKeys = YM_DBG_CONV_CFG + 1;  // include/yolomi.h YM_DBG_* keys 1..9
+constexpr int kDbgKeys = YM_DBG_STOP + 1;  // include/yolomi.h YM_DBG_* keys 1..10
 std::atomic<int>* dbg_slots() {
   static std::atomic<int> v[kDbgKeys] = {};
   static const bool init = [] {
     const char* names[kDbgKeys] = {nullptr,       "YM_NMS_DBG", "YM_DW_MODE", "YM_DW_TILE", "YM_CHAIN",
-                                   nullptr,       "YM_STEMFUSE", "YM_ATTN_KB", "YM_PAIRST", "YM_CONV_CFG"};
+                                   nullptr,       "YM_STEMFUSE", "YM_ATTN_KB", "YM_PAIRST", "YM_CONV_CFG",
+                                   nullptr};  // (YM_DBG_STOP: set by a test only, never from the environment)
     for (int k = 1; k < kDbgKeys; ++k) {
       if (!names[k]) continue;
       const char* e = getenv(names[k]);

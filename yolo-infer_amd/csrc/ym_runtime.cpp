@@ -99,6 +99,7 @@ struct Launch {
   int B = 0;              // images of the whole call (all lanes)
   bool skip_nms = false;  // ym_tta_forward: the passes' candidates are merged first (ym_tta_nms)
   int stop = -1;          // ym_embed: the last op of the truncated forward (-1: a whole forward)
+  bool pool = true;       // (stop >= 0) the embedding pooling stage follows; false: YM_DBG_STOP, a test's bare stop
   float* const* calib_raw = nullptr;  // ym_calibrate: per-op pre-activation output buffers (f32 plans)
 };
 
@@ -306,6 +307,10 @@ struct ym_ctx {
     for (size_t i = 0; i < cfgs.size(); ++i)
       if (cfgs[i].B == B && cfgs[i].H == H && cfgs[i].W == W) { cfgs.erase(cfgs.begin() + i); return; }
   }
+  // tests (ym_get_op_cfg_taken): per op of the last forward launched, whether its pinned cfg was the kernel that ran
+  // ([2i]: the op, or the first conv of a kSplitTag pair; [2i + 1]: the pair's second conv; ym_launch_conv's `taken`)
+  std::vector<int> taken;
+  int tkB = 0, tkH = 0, tkW = 0;
   int op_cfg(long i, int B) const {  // for the current workspace height/width
     const std::vector<int>* v = find_cfg(B, cH, cW);
     return (v && i >= 0 && i < (long)v->size()) ? (*v)[i] : -1;
@@ -561,17 +566,27 @@ void split_args(ym_ctx* c, const Launch& L, const Op& op, const ConvArgs& a, Con
   Bc.s0_elems = (long)xs * c->cB * c->buf_P(mid) * c->bufs[mid].C;
 }
 
+// taken[2]: ym_launch_conv's `taken` of the fused launch, or of the two convs of a kSplitTag cfg (a half's id 255 is
+// "heuristic": -1); a fused cfg that fell back to the split pair is {0, -1}
 hipError_t launch_fused(ym_ctx* c, const Launch& L, const Op& op, const ConvArgs& a, int out_f32, int cfg,
-                        hipStream_t st) {
-  if (cfg < kSplitTag) {
-    const hipError_t e = ym_launch_conv(c->dtype, out_f32, a, cfg, st);
+                        hipStream_t st, int* taken) {
+  const bool tagged = cfg >= kSplitTag;
+  if (!tagged) {
+    const hipError_t e = ym_launch_conv(c->dtype, out_f32, a, cfg, st, false, &taken[0]);
     if (e != hipErrorInvalidValue) return e;
     cfg = kSplitTag + 256 * 255 + 255;  // no fused kernel takes this shape (e.g. a map width the Bottleneck kernel
   }                                     // does not tile): the two convs with their heuristic tiles
   ConvArgs A, Bc;
   split_args(c, L, op, a, A, Bc);
-  const hipError_t e = ym_launch_conv(c->dtype, 0, A, ((cfg - kSplitTag) >> 8) & 255, st);
-  return e != hipSuccess ? e : ym_launch_conv(c->dtype, out_f32, Bc, (cfg - kSplitTag) & 255, st);
+  const int ca = ((cfg - kSplitTag) >> 8) & 255, cb = (cfg - kSplitTag) & 255;
+  int ta = -1, tb = -1;
+  hipError_t e = ym_launch_conv(c->dtype, 0, A, ca, st, false, &ta);
+  if (e == hipSuccess) e = ym_launch_conv(c->dtype, out_f32, Bc, cb, st, false, &tb);
+  if (tagged) {
+    taken[0] = ca == 255 ? -1 : ta;
+    taken[1] = cb == 255 ? -1 : tb;
+  }
+  return e;
 }
 
 // Where an NMS stage reads per-candidate rows: the nm extras the NMS kernel copies behind each kept box, and the
@@ -643,9 +658,13 @@ int launch_op(ym_ctx* c, const Launch& L, const Op& op, int B, const float* d_in
       int out_f32 = 0;
       const int rc = conv_args(c, L, op, B, d_in, args->in_eps, a, out_f32);
       if (rc) return rc;
-      const int cfg = c->op_cfg(&op - c->ops.data(), B);
+      const size_t oi = (size_t)(&op - c->ops.data());
+      const int cfg = c->op_cfg((long)oi, B);
+      int tk[2] = {-1, -1};
       e = a.nchw ? ym_launch_stem(dt, a, st)
-                 : (a.w2 ? launch_fused(c, L, op, a, out_f32, cfg, st) : ym_launch_conv(dt, out_f32, a, cfg, st));
+                 : (a.w2 ? launch_fused(c, L, op, a, out_f32, cfg, st, tk)
+                         : ym_launch_conv(dt, out_f32, a, cfg, st, false, &tk[0]));
+      if (c->taken.size() == 2 * c->ops.size()) { c->taken[2 * oi] = tk[0]; c->taken[2 * oi + 1] = tk[1]; }
       break;
     }
     case OP_DW: {
@@ -840,7 +859,7 @@ int ym_num_conv_cfgs(int dtype) {  // public dtype codes (ym_model_desc): 1 f16,
 
 const char* ym_last_error(void) { return g_err.c_str(); }
 int ym_set_debug(int key, int value) {
-  if (key < YM_DBG_NMS || key > YM_DBG_CONV_CFG) return fail(YM_EINVAL, "unknown debug key %d", key);
+  if (key < YM_DBG_NMS || key > YM_DBG_STOP) return fail(YM_EINVAL, "unknown debug key %d", key);
   return ym_debug_set(key, value);
 }
 
@@ -1207,7 +1226,7 @@ static int launch_forward(ym_ctx* c, const Launch& call, const float* d_in, cons
       HIPCK(hipEventRecord(c->join_ev[s], bs[s]));
       HIPCK(hipStreamWaitEvent(st, c->join_ev[s], 0));
     }
-    return embed ? launch_embed(c, B, st) : YM_OK;  // (the pooling stage reads behind the join)
+    return embed && call.pool ? launch_embed(c, B, st) : YM_OK;  // (the pooling stage reads behind the join)
   }
   size_t o = 0;
   for (o = 0; o < nops && c->ops[o].kind == OP_INPUT; ++o)
@@ -1231,7 +1250,7 @@ static int launch_forward(ym_ctx* c, const Launch& call, const float* d_in, cons
       HIPCK(hipStreamWaitEvent(st, c->join_ev[ln], 0));
     }
   }
-  return embed ? launch_embed(c, B, st) : YM_OK;  // (ym_embed runs one lane: everything above is on `st`)
+  return embed && call.pool ? launch_embed(c, B, st) : YM_OK;  // (ym_embed runs one lane: everything above is on `st`)
 }
 
 // Behind check_call, for every entry point that launches ops: device, workspace, stream order; L: one whole-batch launch
@@ -1252,6 +1271,17 @@ static int infer_impl(ym_ctx* c, const float* d_in, int B, int H, int W, const y
   Launch L;
   if ((rc = begin_launch(c, B, H, W, st, L))) return rc;
   L.skip_nms = skip_nms; L.stop = stop;
+  // YM_DBG_STOP (tests): an eager forward that ends behind op value - 1, every op its own launch as ym_embed's
+  // truncated forward but with no pooling stage.  Never captured: a stopped forward must not be cached as, or
+  // replayed for, a whole one
+  if (const int dbg_stop = ym_debug_get(YM_DBG_STOP); dbg_stop > 0 && stop < 0) {
+    if (args->use_graph) return fail(YM_EINVAL, "YM_DBG_STOP is set: eager forwards only (use_graph = 0)");
+    if (dbg_stop > (int)c->ops.size()) return fail(YM_EINVAL, "YM_DBG_STOP: op %d of %zu", dbg_stop - 1, c->ops.size());
+    L.stop = dbg_stop - 1;
+    L.pool = false;
+  }
+  c->taken.assign(2 * c->ops.size(), -1);
+  c->tkB = B; c->tkH = H; c->tkW = W;
   if (!args->use_graph) {
     if ((rc = launch_forward(c, L, d_in, args, d_dets, d_counts, st))) return rc;
     return c->mark_last(st);
@@ -1685,6 +1715,15 @@ int ym_set_op_cfg(ym_ctx* c, int B, int H, int W, const int* cfg, int n) {
   }
   c->put_cfg(B, H, W, std::vector<int>(cfg, cfg + n));
   c->clear_graphs();
+  return YM_OK;
+}
+
+int ym_get_op_cfg_taken(ym_ctx* c, int B, int H, int W, int* out, int n) {
+  if (!c || !out || n < 2 * (int)c->ops.size())
+    return fail(YM_EINVAL, "taken array must hold %zu entries", c ? 2 * c->ops.size() : 0);
+  if (c->taken.size() != 2 * c->ops.size() || B != c->tkB || H != c->tkH || W != c->tkW)
+    return fail(YM_ESTATE, "ym_get_op_cfg_taken: the last forward was not a %d x %d x %d one", B, H, W);
+  for (size_t i = 0; i < c->taken.size(); ++i) out[i] = c->taken[i];
   return YM_OK;
 }
 

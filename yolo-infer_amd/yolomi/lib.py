@@ -93,6 +93,7 @@ def load_library(path: os.PathLike = LIB_PATH):
         "ym_letterbox": (I, [P, P, I, I, I, I, I, I, I, I, P, I, I, P]),
         "ym_get_op_cfg": (I, [P, I, I, I, C.POINTER(I), I]),
         "ym_set_op_cfg": (I, [P, I, I, I, C.POINTER(I), I]),
+        "ym_get_op_cfg_taken": (I, [P, I, I, I, C.POINTER(I), I]),
         "ym_num_ops": (I, [P]),
         "ym_op_name": (C.c_char_p, [P, I]),
         "ym_num_buffers": (I, [P]),
@@ -135,7 +136,8 @@ def load_library(path: os.PathLike = LIB_PATH):
 
 EXPORTED = ("ym_create", "ym_load_weights", "ym_broadcast_weights", "ym_broadcast_weights_local", "ym_rccl_get_unique_id", "ym_rccl_comm_init",
             "ym_rccl_comm_destroy", "ym_infer", "ym_input_max", "ym_calibrate", "ym_masks", "ym_masks_slots", "ym_masks_native",
-            "ym_letterbox", "ym_profile", "ym_profile_replay", "ym_tune", "ym_get_op_cfg", "ym_set_op_cfg", "ym_num_ops", "ym_op_name",
+            "ym_letterbox", "ym_profile", "ym_profile_replay", "ym_tune", "ym_get_op_cfg", "ym_set_op_cfg", "ym_get_op_cfg_taken", "ym_num_ops",
+            "ym_op_name",
             "ym_num_buffers", "ym_buffer_info", "ym_read_buffer", "ym_sync", "ym_last_error", "ym_destroy",
             "ym_version", "ym_num_conv_cfgs", "ym_set_debug", "ym_read_scratch", "ym_kpt_shape",
             "ym_tta_shape", "ym_tta_scale", "ym_tta_forward", "ym_tta_nms", "ym_tta_counts", "ym_embed",
@@ -143,6 +145,7 @@ EXPORTED = ("ym_create", "ym_load_weights", "ym_broadcast_weights", "ym_broadcas
 
 DBG_NMS, DBG_DW_MODE, DBG_DW_TILE, DBG_CHAIN, DBG_CHAIN_LAUNCHES, DBG_STEMFUSE, DBG_ATTN_KB = 1, 2, 3, 4, 5, 6, 7
 DBG_PAIRST, DBG_CONV_CFG = 8, 9  # value + 1 (0: default)  # ym_set_debug keys (include/yolomi.h)
+DBG_STOP = 10  # tests: 1 + the last op an eager forward launches (0: a whole forward); graph calls are refused
 
 
 def set_debug(key: int, value: int) -> int:
@@ -360,6 +363,14 @@ class Runtime:
     def set_op_cfg(self, B, H, W, cfg):
         arr = (C.c_int * self.n_ops)(*cfg)
         _check(self.lib.ym_set_op_cfg(self.ctx, B, H, W, arr, self.n_ops))
+
+    def get_op_cfg_taken(self, B, H, W):
+        """Per op of the last (eager or captured) B x H x W forward, (taken, taken of a two-launch pair's second conv):
+        1 the op's pinned conv config was the kernel that ran, 0 the launcher fell back, -1 not a conv / not pinned
+        (include/yolomi.h ym_get_op_cfg_taken)."""
+        arr = (C.c_int * (2 * self.n_ops))()
+        _check(self.lib.ym_get_op_cfg_taken(self.ctx, B, H, W, arr, 2 * self.n_ops))
+        return [(arr[2 * i], arr[2 * i + 1]) for i in range(self.n_ops)]
 
     def buffer_info(self, buf: int):
         p, c, h, w, e = C.c_void_p(), C.c_int(), C.c_int(), C.c_int(), C.c_int()

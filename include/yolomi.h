@@ -379,6 +379,25 @@ int ym_annotate(ym_ctx* ctx, const void* d_frames, int frames_are_f32_chw, int B
                 int mask_h, int mask_w, const int* d_mask_geo, const unsigned char* d_names, const ym_annotate_args* args,
                 unsigned char* d_out, void* stream);
 
+/* Instance polygons (Ultralytics Masks.xy: masks2segments' cv2.findContours(RETR_EXTERNAL, CHAIN_APPROX_SIMPLE) and
+ * strategy "largest"), traced on the device (csrc/ym_contour.hip; the definition is this project's own):
+ * per plane, the outer border of one top-level 8-connected component — the one with the most points after
+ * compression, a tie going to the one that starts last in raster order — as (x, y) int32 pixel coordinates.  Works on
+ * any context, loaded or not: it reads planes, not activations.
+ * d_masks: n planes of H x W bytes (non-zero = inside), plane i at d_masks + i * plane_stride; the output of ym_masks,
+ * ym_masks_slots, ym_masks_native or any other byte tensor, box-cropped or not.  d_offsets: n + 1 int64 words,
+ * offsets[i] = the first point of plane i, offsets[n] = the points of all planes (a plane without foreground has
+ * none).  d_points: cap_points x 2 int32, plane i's points at d_points + 2 * offsets[i], back to back, for every plane
+ * with offsets[i + 1] <= cap_points; the points of the other planes are not written, so a caller that reads
+ * offsets[n] > cap_points calls again with that capacity (d_points may be null with cap_points 0: a count-only call).
+ * Reading a result is two device->host copies: the offsets, then offsets[n] points.
+ * YM_EINVAL: a null pointer, n < 0, H or W below 1 (or H * W above 2^27), plane_stride < H * W, cap_points < 0; n = 0
+ * is valid and writes offsets[0] = 0.  Asynchronous on `stream`.  Scratch: 16 bytes per plane, and for planes of more
+ * than about 480k pixels (whose bit plane does not fit LDS) (H + 2) * (ceil(W / 32) + 2) * 4 bytes per plane more; ONE
+ * buffer per context, grown like ym_annotate's (same rules: stream-ordered calls, no growth while capturing). */
+int ym_mask_contours(ym_ctx* ctx, const unsigned char* d_masks, int n, int H, int W, long long plane_stride,
+                     int* d_points, long long cap_points, long long* d_offsets, void* stream);
+
 int ym_sync(ym_ctx* ctx);
 const char* ym_last_error(void);
 void ym_destroy(ym_ctx* ctx);

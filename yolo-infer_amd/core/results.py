@@ -107,14 +107,76 @@ class Boxes(_TensorView):
 
 
 class Masks(_TensorView):
-    """(n, H, W) binary instance masks of one image."""
+    """(n, H, W) binary instance masks of one image (upstream `ultralytics.engine.results.Masks`).
 
-    def __init__(self, masks, orig_shape=None):
+    `xy` / `xyn`: the instances' polygons, upstream's `masks2segments` (strategy "largest") traced on the GPU by the
+    engine that made the masks (Engine.mask_contours, csrc/ym_contour.hip; the contour definition is DESIGN.md §18's,
+    not cv2's), then `scale_coords((H, W), points, orig_shape)`.  Computed on first access (one launch, two small
+    device->host reads for all n instances) and cached; a hand-built Masks needs `engine=`: there is no host tracer."""
+
+    def __init__(self, masks, orig_shape=None, engine=None):
         super().__init__(masks)
         self.orig_shape = orig_shape
+        self._engine = engine
+        self._xy = None
 
     def _extra(self):
-        return (self.orig_shape,)
+        return (self.orig_shape, self._engine)
+
+    def _carry(self, other, idx=None):
+        """Hand the computed polygons (all, or those `idx` selects) to `other`, a view of the same planes."""
+        if self._xy is not None:
+            if idx is None:
+                other._xy = self._xy
+            else:
+                if isinstance(idx, torch.Tensor):
+                    idx = idx.cpu().numpy()
+                sel = np.arange(len(self._xy))[idx]
+                other._xy = [self._xy[i] for i in np.atleast_1d(sel).tolist()]
+        return other
+
+    def __getitem__(self, idx):
+        return self._carry(super().__getitem__(idx), idx)
+
+    def cpu(self):
+        return self._carry(super().cpu())
+
+    def numpy(self):
+        return self._carry(super().numpy())
+
+    def cuda(self):
+        return self._carry(super().cuda())
+
+    def to(self, *args, **kwargs):
+        return self._carry(super().to(*args, **kwargs))
+
+    @property
+    def xy(self):
+        """A list of n (k_i, 2) float32 numpy arrays: each instance's polygon, (x, y) in the original image's pixels."""
+        if self._xy is None:
+            if self._engine is None:
+                raise RuntimeError("Masks.xy traces the polygons on the GPU: this Masks was built by hand without "
+                                   "engine= (an Engine, e.g. model.model.engine); there is no host fallback")
+            from yolomi.preprocess import scale_coords
+            planes = torch.as_tensor(self.data)
+            if planes.dim() == 2:
+                planes = planes[None]
+            if planes.dtype not in (torch.uint8, torch.bool):
+                planes = planes != 0
+            if planes.device != self._engine.device:  # after Results.cpu(): one upload
+                planes = planes.to(self._engine.device)
+            shape = tuple(planes.shape[-2:])
+            orig = self.orig_shape if self.orig_shape is not None else shape
+            self._xy = [scale_coords(shape, torch.from_numpy(p.astype(np.float32)), orig).numpy()
+                        for p in self._engine.mask_contours(planes)]
+        return self._xy
+
+    @property
+    def xyn(self):
+        """`xy` with x divided by the original image's width and y by its height."""
+        shape = self.orig_shape if self.orig_shape is not None else tuple(self.data.shape[-2:])
+        wh = np.array([shape[1], shape[0]], dtype=np.float32)
+        return [p / wh for p in self.xy]
 
 
 class Keypoints(_TensorView):
@@ -185,7 +247,7 @@ class Results:
         self.orig_shape = tuple(orig_tensor.shape[-2:]) if orig_tensor is not None else None
         self.names = names
         self.boxes = Boxes(boxes, self.orig_shape)
-        self.masks = Masks(masks, self.orig_shape) if masks is not None else None
+        self.masks = Masks(masks, self.orig_shape, engine=annotator) if masks is not None else None
         self.path = path
         self.speed = speed or {"preprocess": None, "inference": None, "postprocess": None}
         self.probs = None
@@ -273,7 +335,7 @@ class Results:
     def masks(self) -> Optional["Masks"]:
         if self._masks is None and getattr(self, "_msrc", None) is not None:
             mb, moff = self._msrc
-            self._masks = Masks(mb[moff:moff + self._count], self.orig_shape)
+            self._masks = Masks(mb[moff:moff + self._count], self.orig_shape, engine=self._annotator)
         return self._masks
 
     @masks.setter
@@ -332,15 +394,21 @@ class Results:
 
     def __getitem__(self, idx):
         k = self.keypoints
-        return self._like(self._orig_tensor, self.boxes.data[idx],
-                          self.masks.data[idx] if self.masks is not None else None,
-                          k.data[idx].clone() if k is not None else None)
+        r = self._like(self._orig_tensor, self.boxes.data[idx],
+                       self.masks.data[idx] if self.masks is not None else None,
+                       k.data[idx].clone() if k is not None else None)
+        if self.masks is not None:  # polygons already traced are sliced, not traced again
+            self.masks._carry(r.masks, idx)
+        return r
 
     def cpu(self):
         k = self.keypoints
-        return self._like(self._orig_tensor.cpu() if self._orig_tensor is not None else None, self.boxes.data.cpu(),
-                          self.masks.data.cpu() if self.masks is not None else None,
-                          k.data.cpu().clone() if k is not None else None)
+        r = self._like(self._orig_tensor.cpu() if self._orig_tensor is not None else None, self.boxes.data.cpu(),
+                       self.masks.data.cpu() if self.masks is not None else None,
+                       k.data.cpu().clone() if k is not None else None)
+        if self.masks is not None:
+            self.masks._carry(r.masks)
+        return r
 
     def plot(self, conf=True, line_width=None, kpt_radius=5, kpt_line=True, labels=True, boxes=True, masks=True,
              img=None, color_mode="class", save=False, filename=None, **ignored) -> np.ndarray:
@@ -378,16 +446,52 @@ class Results:
         return filename
 
     def summary(self, normalize=False, decimals=5):
+        """Upstream `Results.summary`: one dict per detection; with masks, its polygon as "segments": {"x": [...],
+        "y": [...]} (Masks.xy, divided by the image's width / height when `normalize`), rounded to `decimals`."""
         out = []
         is_track = self.boxes.is_track
-        for row in self.boxes.data.tolist():
+        segs = self.masks.xy if self.masks is not None else None
+        h, w = self.orig_shape if normalize and self.orig_shape is not None else (1, 1)
+        for i, row in enumerate(self.boxes.data.tolist()):
             (x1, y1, x2, y2), conf, c = row[:4], row[-2], row[-1]
             out.append({"name": self.names[int(c)], "class": int(c), "confidence": round(conf, decimals),
                         "box": {"x1": round(x1, decimals), "y1": round(y1, decimals), "x2": round(x2, decimals),
                                 "y2": round(y2, decimals)}})
             if is_track:
                 out[-1]["track_id"] = int(row[-3])
+            if segs is not None:
+                out[-1]["segments"] = {"x": (segs[i][:, 0].astype(np.float64) / w).round(decimals).tolist(),
+                                       "y": (segs[i][:, 1].astype(np.float64) / h).round(decimals).tolist()}
         return out
+
+    def save_txt(self, txt_file, save_conf=False):
+        """Upstream `Results.save_txt`: one line per detection appended to `txt_file` — `cls x y w h` (the box,
+        normalised) for detect, `cls x1 y1 x2 y2 ...` (Masks.xyn) for segment, the box then the normalised keypoints
+        (with their visibility when they have one) for pose; then the confidence when `save_conf`, then the track id of
+        tracked rows.  Values are written with %g.  Nothing is written for an image without detections."""
+        import os
+        boxes, masks, kpts = self.boxes, self.masks, self.keypoints
+        xywhn = torch.as_tensor(boxes.xywhn).cpu().tolist()
+        rows = torch.as_tensor(boxes.data).cpu().tolist()
+        segs = masks.xyn if masks is not None else None
+        kxyn = torch.as_tensor(kpts.xyn).cpu() if kpts is not None else None
+        kconf = torch.as_tensor(kpts.conf).cpu() if kpts is not None and kpts.has_visible else None
+        texts = []
+        for j, row in enumerate(rows):
+            line = (int(row[-1]), *xywhn[j])
+            if segs is not None:
+                line = (int(row[-1]), *segs[j].reshape(-1).tolist())
+            if kxyn is not None:
+                k = torch.cat((kxyn[j], kconf[j][:, None]), 1) if kconf is not None else kxyn[j]
+                line += (*k.reshape(-1).tolist(),)
+            line += (row[-2],) * bool(save_conf) + ((int(row[-3]),) if boxes.is_track else ())
+            texts.append(("%g " * len(line)).rstrip() % line)
+        if texts:
+            d = os.path.dirname(str(txt_file))
+            if d:
+                os.makedirs(d, exist_ok=True)
+            with open(txt_file, "a", encoding="utf-8") as f:
+                f.writelines(t + "\n" for t in texts)
 
     def __repr__(self):
         return f"Results(boxes={len(self.boxes)}, orig_shape={self.orig_shape})"

@@ -27,6 +27,7 @@
 #include "ym_tta.h"
 #include "ym_track.h"
 #include "ym_annot.h"
+#include "ym_contour.h"
 
 namespace {
 
@@ -249,6 +250,10 @@ struct ym_ctx {
   // annotated frames (ym_annotate): the records of the B x max_det detection slots, grown on demand
   AnnotRec* d_annot = nullptr;
   size_t annot_recs = 0;
+  // instance polygons (ym_mask_contours): n CtSel records, then (planes too large for LDS only) n bit planes of
+  // ym_ct_words(H, W) words; grown on demand
+  char* d_contour = nullptr;
+  size_t contour_bytes = 0;
   // test-time augmentation: ym_tta_forward launches the forward without its NMS stage; the merged candidate set and the
   // NMS scratch over it (ym_tta_nms) belong to the first pass's context and are rebuilt only when the shape changes
   struct TtaWs {
@@ -327,6 +332,7 @@ struct ym_ctx {
     if (tta.d) (void)hipFree(tta.d);
     if (d_embed) (void)hipFree(d_embed);
     if (d_annot) (void)hipFree(d_annot);
+    if (d_contour) (void)hipFree(d_contour);
     if (cap_stream) (void)hipStreamDestroy(cap_stream);
     for (int l = 0; l < kMaxLanes; ++l) {
       if (lane_streams[l]) (void)hipStreamDestroy(lane_streams[l]);
@@ -2270,6 +2276,43 @@ int ym_annotate(ym_ctx* c, const void* d_frames, int frames_are_f32_chw, int B, 
   a.recs = c->d_annot; a.out = d_out;
   const hipError_t e = ym_launch_annotate(a, st);
   if (e != hipSuccess) return fail(YM_EHIP, "annotate kernels: %s", hipGetErrorString(e));
+  return YM_OK;
+}
+
+// ---------------------------------------------------------------------------------- instance polygons
+int ym_mask_contours(ym_ctx* c, const unsigned char* d_masks, int n, int H, int W, long long plane_stride, int* d_points,
+                     long long cap_points, long long* d_offsets, void* stream) {
+  if (!c) return fail(YM_EINVAL, "null context");
+  if (!d_offsets || (n > 0 && !d_masks) || (cap_points > 0 && !d_points))
+    return fail(YM_EINVAL, "ym_mask_contours: null pointer argument");
+  if (n < 0 || H < 1 || W < 1 || (long long)H * W > kContourMaxPixels || cap_points < 0)
+    return fail(YM_EINVAL, "ym_mask_contours: %d planes of %d x %d (1 x 1 .. 2^27 pixels), capacity %lld", n, H, W, cap_points);
+  if (plane_stride < (long long)H * W)
+    return fail(YM_EINVAL, "ym_mask_contours: plane stride %lld below %d x %d", plane_stride, H, W);
+  HIPCK(hipSetDevice(c->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const long long words = ym_ct_words(H, W);
+  const bool in_lds = words <= kContourLdsWords;
+  const size_t sel_bytes = ((size_t)n * sizeof(CtSel) + 255) & ~(size_t)255;
+  const size_t need = sel_bytes + (in_lds ? 0 : (size_t)n * (size_t)words * sizeof(uint32_t));
+  if (need > c->contour_bytes) {  // (an earlier call may still use the old scratch)
+    if (c->d_contour) {
+      HIPCK(hipDeviceSynchronize());
+      HIPCK(hipFree(c->d_contour));
+      c->d_contour = nullptr;
+      c->contour_bytes = 0;
+    }
+    const hipError_t e = hipMalloc(&c->d_contour, need);
+    if (e != hipSuccess) {
+      c->d_contour = nullptr;
+      return fail(YM_ENOMEM, "ym_mask_contours: %zu scratch bytes: %s", need, hipGetErrorString(e));
+    }
+    c->contour_bytes = need;
+  }
+  const hipError_t e = ym_launch_contours(d_masks, plane_stride, n, H, W,
+                                          in_lds ? nullptr : reinterpret_cast<uint32_t*>(c->d_contour + sel_bytes),
+                                          reinterpret_cast<CtSel*>(c->d_contour), d_points, cap_points, d_offsets, st);
+  if (e != hipSuccess) return fail(YM_EHIP, "contour kernels: %s", hipGetErrorString(e));
   return YM_OK;
 }
 

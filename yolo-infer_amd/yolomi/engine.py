@@ -80,6 +80,7 @@ class Engine:
         self.tune_source: Dict[tuple, str] = {}
         self.names = {i: f"class{i}" for i in range(nc or 0)}  # annotate's label names (set_names)
         self._annot_tables = None  # annotate: (device font bytes, device name table, nc), uploaded once
+        self.contour_launches = 0  # ym_mask_contours calls so far (tests: Masks.xy caches)
 
     def broadcast_weights(self, comm: int, root: int = 0):
         """The root's side of the RCCL weight broadcast (ym_broadcast_weights): every rank of `comm` calls it or
@@ -433,6 +434,41 @@ class Engine:
         from .annotate import annotate_batch
         return annotate_batch(self, frames, dets, counts, masks=masks, mask_offsets=mask_offsets, mask_geo=mask_geo,
                               mask_cap=mask_cap, tracked=tracked, out=out, kpt_shape=kpt_shape, **switches)
+
+    def mask_contours_device(self, masks: torch.Tensor, cap: Optional[int] = None):
+        """Instance polygons of n mask planes, left on the device (csrc/ym_contour.hip).  masks: an
+        (n, H, W) bool / uint8 tensor on the engine's device whose planes are contiguous (masks.stride(0) >= H * W is
+        the plane stride: a slice of mask slots works as it is).  Returns (points, offsets): (cap, 2) int32 (x, y) and
+        (n + 1,) int64; plane i's points are points[offsets[i]:offsets[i + 1]].  cap: the capacity in points (default
+        max(4096, 64 n)); when offsets[n] exceeds it, the planes that did not fit are unwritten and the call is to
+        be repeated with cap = offsets[n] (mask_contours does).  Enqueued on the current stream; nothing is read."""
+        if masks.dim() != 3 or masks.dtype not in (torch.uint8, torch.bool) or masks.device != self.device:
+            raise ValueError("mask_contours: masks must be an (n, H, W) uint8 / bool tensor on the engine's device")
+        n, H, W = masks.shape
+        if H < 1 or W < 1:
+            raise ValueError(f"mask_contours: planes of {H} x {W}")
+        if n and (masks.stride(2) != 1 or masks.stride(1) != W or (n > 1 and masks.stride(0) < H * W)):
+            masks = masks.contiguous()
+        cap = max(4096, 64 * n) if cap is None else int(cap)
+        points = torch.empty((cap, 2), dtype=torch.int32, device=self.device)
+        offsets = torch.empty((n + 1,), dtype=torch.int64, device=self.device)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        self.rt.mask_contours(masks.data_ptr() if n else 0, n, H, W, masks.stride(0) if n > 1 else H * W,
+                              points.data_ptr() if cap else 0, cap, offsets.data_ptr(), stream)
+        self.contour_launches += 1
+        return points, offsets
+
+    def mask_contours(self, masks: torch.Tensor, cap: Optional[int] = None):
+        """Instance polygons of n mask planes: a list of n (k_i, 2) int32 numpy arrays of (x, y) pixel coordinates, the
+        outer border of each plane's chosen component ((0, 2) for a plane without foreground).  Two device->host reads:
+        the offsets, then exactly the points; a first capacity that proves too small costs one more launch."""
+        points, offsets = self.mask_contours_device(masks, cap)
+        offs = offsets.cpu().numpy()
+        total = int(offs[-1])
+        if total > points.shape[0]:
+            points, offsets = self.mask_contours_device(masks, total)
+        pts = points[:total].cpu().numpy() if total else np.zeros((0, 2), dtype=np.int32)
+        return [pts[offs[i]:offs[i + 1]] for i in range(len(offs) - 1)]
 
     def profile(self, x: torch.Tensor, **kw):
         B, _, H, W = x.shape

@@ -114,6 +114,7 @@ def load_library(path: os.PathLike = LIB_PATH):
         "ym_track_update": (I, [P, P, I, I, I, P, P, P, P, P]),
         "ym_track_read_state": (I, [P, C.POINTER(I), I]),
         "ym_annotate": (I, [P, P, I, I, I, I, P, I, P, P, P, I, I, P, P, C.POINTER(AnnotateArgs), P, P]),
+        "ym_mask_contours": (I, [P, P, I, I, I, C.c_longlong, P, C.c_longlong, P, P]),
         "ym_broadcast_weights": (I, [P, P, I, P]),
         "ym_broadcast_weights_local": (I, [C.POINTER(P), I, I, P]),
         "ym_rccl_get_unique_id": (I, [C.POINTER(RcclId)]),
@@ -141,7 +142,8 @@ EXPORTED = ("ym_create", "ym_load_weights", "ym_broadcast_weights", "ym_broadcas
             "ym_num_buffers", "ym_buffer_info", "ym_read_buffer", "ym_sync", "ym_last_error", "ym_destroy",
             "ym_version", "ym_num_conv_cfgs", "ym_set_debug", "ym_read_scratch", "ym_kpt_shape",
             "ym_tta_shape", "ym_tta_scale", "ym_tta_forward", "ym_tta_nms", "ym_tta_counts", "ym_embed",
-            "ym_track_create", "ym_track_destroy", "ym_track_reset", "ym_track_update", "ym_track_read_state", "ym_annotate")
+            "ym_track_create", "ym_track_destroy", "ym_track_reset", "ym_track_update", "ym_track_read_state", "ym_annotate",
+            "ym_mask_contours")
 
 DBG_NMS, DBG_DW_MODE, DBG_DW_TILE, DBG_CHAIN, DBG_CHAIN_LAUNCHES, DBG_STEMFUSE, DBG_ATTN_KB = 1, 2, 3, 4, 5, 6, 7
 DBG_PAIRST, DBG_CONV_CFG = 8, 9  # value + 1 (0: default)  # ym_set_debug keys (include/yolomi.h)
@@ -304,6 +306,14 @@ class Runtime:
         _check(self.lib.ym_annotate(self.ctx, V(frames_ptr), int(bool(f32_chw)), B, H, W, V(dets_ptr), max_det,
                                     V(counts_ptr), V(masks_ptr), V(mask_offsets_ptr), mask_h, mask_w, V(mask_geo_ptr),
                                     V(names_ptr), C.byref(args), V(out_ptr), V(stream)))
+
+    def mask_contours(self, masks_ptr: int, n: int, H: int, W: int, plane_stride: int, points_ptr: int, cap: int,
+                      offsets_ptr: int, stream: int):
+        """ym_mask_contours: per plane the chosen border's (x, y) int32 points into (cap, 2) and the n + 1 int64
+        offsets; asynchronous on `stream`."""
+        V = C.c_void_p
+        _check(self.lib.ym_mask_contours(self.ctx, V(masks_ptr), n, H, W, plane_stride, V(points_ptr), cap,
+                                         V(offsets_ptr), V(stream)))
 
     def track_create(self, streams: int, cfg: dict = None, capacity: int = 0) -> "Tracker":
         """ym_track_create: the ByteTrack state of `streams` video streams on this context's device."""

@@ -487,7 +487,7 @@ def test_ultralytics_pt_model_path(tmp_path):
 
 
 # ------------------------------------------------------------------------------------------------ fused conv pairs
-SPLIT_TAG = 1 << 20  # csrc/ym_runtime.cpp kSplitTag: op cfg of a fused pair run as its two convs
+SPLIT_TAG = 1 << 20  # csrc/ym_conv_catalog.h kSplitTag: op cfg of a fused pair run as its two convs
 
 
 def test_fused_pairs_split_equals_unfused_plan():

@@ -202,7 +202,7 @@ def test_x3_1280_n1600_attention_and_max_nms():
     check(oracle().predict(x, conf=0.001), model("n").predict(x.to(DEV), conf=0.001), conf=0.001, x=x)
 
 
-SPLIT_TAG = 1 << 20  # csrc/ym_runtime.cpp kSplitTag: op cfg of a fused pair run as its two convs
+SPLIT_TAG = 1 << 20  # csrc/ym_conv_catalog.h kSplitTag: op cfg of a fused pair run as its two convs
 STREAM_BASE, N_STREAM = 17 + 30, 31  # csrc/ym_conv.hip: first-gen + LDS-DMA ids, then the streaming kernels
 BNECK_BASE, N_BNECK = 17 + 30 + 43 + 12, 14  # ... + streaming/small-M + halo ids, then the fused Bottleneck kernels
 X3_BNECK = (116 + 9, 116 + 11)  # x3-only ids: after the f16 catalogue and the 9 x3-only LDS-DMA configurations

@@ -5,6 +5,7 @@
 
 #include "../../include/yolomi.h"
 #include "ym_plan.h"  // the plan dtypes (YM_DT_*, ym_dt_f32s, ym_dt_q8) and the blob format
+#include "ym_conv_catalog.h"  // conv config ids: families, resolver, dispatch (host only)
 
 typedef _Float16 f16;
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
@@ -551,12 +552,11 @@ struct MaskNativeArgs {                 // ym_mask_native.hip: process_mask_nati
 
 // ------------------------------------------------------------------------------------------------------------
 // Host-side launchers (defined in the .hip translation units).
-// cfg < 0: heuristic; strict: an inapplicable cfg is an error (else the heuristic runs).  taken (tests; may be null):
-// 1 when the kernel of `cfg` is the one launched, 0 when the launcher fell back (the heuristic tile, the first variant
-// that takes the shape), -1 when cfg < 0 or the plan is int8 / fp8 (not tracked)
+// cfg: a conv config id of csrc/ym_conv_catalog.h (cfg < 0: heuristic); strict: an inapplicable cfg is an error (else the
+// heuristic runs).  taken (tests; may be null): 1 when the kernel of `cfg` is the one launched, 0 when the launcher fell
+// back (the heuristic tile, the first variant that takes the shape), -1 when cfg < 0 or the plan is int8 / fp8
 hipError_t ym_launch_conv(int dtype, int out_f32, const ConvArgs& a, int cfg, hipStream_t st, bool strict = false,
                           int* taken = nullptr);
-int ym_conv_num_cfgs();
 hipError_t ym_launch_dwconv(int dtype, const DwArgs& a, hipStream_t st);
 hipError_t ym_launch_sppf(int dtype, const PoolArgs& a, hipStream_t st);
 hipError_t ym_launch_attn(int dtype, const AttnArgs& a, hipStream_t st);
@@ -581,31 +581,22 @@ const void* ym_nms_kernel();  // the NMS kernel's function (graph replays re-poi
 hipError_t ym_launch_stem(int dtype, const ConvArgs& a, hipStream_t st);
 hipError_t ym_launch_letterbox(const LetterboxArgs& a, hipStream_t st);
 hipError_t ym_launch_spin(int usec, hipStream_t st);  // profiling: park the stream for usec (wall clock)
-hipError_t ym_launch_conv_dma(int out_f32, const ConvArgs& a, int i, hipStream_t st);  // f16 plans only
-int ym_conv_dma_num_cfgs();
+hipError_t ym_launch_conv_dma(int out_f32, const ConvArgs& a, int i, hipStream_t st);  // f16 and x3 plans
 hipError_t ym_launch_conv_dma_fuse(int out_f32, const ConvArgs& a, int i, hipStream_t st);  // x3 conv -> 1x1 pairs
-int ym_conv_dma_x3_num_cfgs();  // x3-only LDS-DMA configurations (op cfg ids from ym_conv_num_cfgs() on)
-int ym_conv_num_cfgs_dt(int dtype);  // conv-config catalogue size of a plan dtype (YM_DT_*)
 hipError_t ym_launch_conv_bneck(int out_f32, const ConvArgs& a, int i, hipStream_t st);  // fused Bottleneck
-int ym_conv_bneck_num_cfgs();
-int ym_conv_bneck_x3_num_cfgs();  // x3-only Bottleneck variants (launch indices from ym_conv_bneck_num_cfgs() on)
 hipError_t ym_launch_conv_stream(int out_f32, const ConvArgs& a, int i, hipStream_t st);  // f16 1x1 only
-int ym_conv_stream_num_cfgs();
 hipError_t ym_launch_conv_halo(int out_f32, const ConvArgs& a, int i, hipStream_t st);  // f16 3x3 halo tiles
-hipError_t ym_launch_conv_dwpw(int dtype, int out_f32, const ConvArgs& a, int cfg, hipStream_t st, bool strict,
-                               int* taken = nullptr);  // taken: as ym_launch_conv's
-int ym_conv_dwpw_num_cfgs();  // fused depthwise → 1x1 (ConvArgs::dw_w): its own cfg id space 0 .. n-1
-int ym_conv_halo_num_cfgs();
+// fused depthwise → 1x1 (ConvArgs::dw_w), configuration i of its own id space (i < 0: heuristic)
+hipError_t ym_launch_conv_dwpw(int dtype, int out_f32, const ConvArgs& a, int i, hipStream_t st);
 hipError_t ym_launch_masks(const MaskArgs& a, hipStream_t st);
 bool ym_masks_fused(const MaskArgs& a);  // the one-launch path (no (total, MH, MW) scratch)  // Segment: process_mask(upsample=True)
 // max_bytes: the largest h0 * w0 of the batch (sizes the grid)
 hipError_t ym_launch_masks_native(const MaskNativeArgs& a, long long max_bytes, hipStream_t st);
 // int8 (PTQ) plans: csrc/ym_conv_i8.hip
 // (f8: the fp8 e4m3 PTQ plan on the same kernels, csrc/ym_quant.h Q8<true>)
-hipError_t ym_launch_conv_i8(const ConvArgs& a, int cfg, hipStream_t st, bool strict, bool f8);
-int ym_conv_i8_num_cfgs();
+bool ym_conv_i8_applies(const ConvArgs& a);  // the preconditions of every int8 / fp8 conv kernel
+hipError_t ym_launch_conv_i8(const ConvArgs& a, int i, hipStream_t st, bool f8);  // conv_i8 tile i (i < 0: heuristic)
 hipError_t ym_launch_conv_i8_stream(const ConvArgs& a, int i, hipStream_t st, bool f8);
-int ym_conv_i8_stream_num_cfgs();
 hipError_t ym_launch_dwconv_i8(const DwArgs& a, hipStream_t st, bool f8);
 hipError_t ym_launch_attn_i8(const AttnArgs& a, hipStream_t st, bool f8);
 hipError_t ym_launch_requant(const ReqArgs& a, hipStream_t st, bool f8);

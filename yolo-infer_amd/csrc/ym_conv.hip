@@ -115,8 +115,8 @@ __device__ __forceinline__ void load_res4(const T* p, float* v) {
 }
 
 // WTM: 32-pixel blocks per wave; WTN: 32-channel blocks per wave; WM x WN x WK waves per workgroup.
-// KIND 1: 1x1 stride-1 (two sources, optional up-sampled first source); KIND 3: 3x3 (one source, stride a.s);
-// KIND 0: the stem, a 3x3 whose source is the caller's NCHW fp32 batch (3 channels, /255 rule applied on load).
+// KIND 1: 1x1 stride-1 (two sources, optional up-sampled first source); KIND 3: 3x3 (one source, stride a.s).
+// (The stem, whose source is the caller's NCHW fp32 batch, has its own kernel: csrc/ym_stem.hip.)
 // One K step = 64 (4 MFMAs per block pair): 4x fewer dependent memory round trips than a 16-deep step.
 constexpr int KSTEP = 64;
 constexpr int KS64 = KSTEP / 16;
@@ -177,8 +177,7 @@ __global__ __launch_bounds__(WM * WN * WK * 64) void conv_igemm(const ConvArgs a
                              ((size_t)(pb[i] * a.s1_P + py[i] * a.Win + px[i]) * a.s1_ctot + a.s1_coff - a.C0)
                        : row0[i];
     } else {
-      row0[i] = KIND == 3 ? static_cast<const T*>(a.src0) + ((size_t)pb[i] * a.s0_P * a.s0_ctot + a.s0_coff)
-                          : nullptr;
+      row0[i] = static_cast<const T*>(a.src0) + ((size_t)pb[i] * a.s0_P * a.s0_ctot + a.s0_coff);
       row1[i] = nullptr;
       iy0[i] = py[i] * a.s - 1;  // top-left input coordinate of the 3x3 window (pad 1)
       ix0[i] = px[i] * a.s - 1;
@@ -205,25 +204,12 @@ __global__ __launch_bounds__(WM * WN * WK * 64) void conv_igemm(const ConvArgs a
     cb0 = c - tap0 * Cin8;
   }
 
-  bool div255 = false;
-  if constexpr (KIND == 0) div255 = ym_input_max(a.ctl) > 1.0f + a.eps;
   auto gather = [&](int i, int s) -> F {
     const int chunk = g * 2 * KS + 2 * s + h;
     if (!pv[i] || chunk >= Kc) return xzero<M>();
     if constexpr (KIND == 1) {
       const int c = chunk * 8;
       return xload<M>((c < a.C0 ? row0[i] : row1[i]) + c);
-    } else if constexpr (KIND == 0) {  // Cin8 == 1: chunk = tap; channels 3..7 are zero padding
-      const int ky = chunk / 3, kx = chunk - (chunk / 3) * 3;
-      const int iy = iy0[i] + ky, ix = ix0[i] + kx;
-      if ((unsigned)iy >= (unsigned)a.Hin || (unsigned)ix >= (unsigned)a.Win) return Vec8<T>::zero();
-      const size_t HW = (size_t)a.Hin * a.Win;
-      const float* p = a.nchw + (size_t)pb[i] * 3 * HW + (size_t)iy * a.Win + ix;
-      float x0 = p[0], x1 = p[HW], x2 = p[2 * HW];
-      if (div255) { x0 = x0 / 255.0f; x1 = x1 / 255.0f; x2 = x2 / 255.0f; }
-      F v = Vec8<T>::zero();
-      v[0] = (T)x0; v[1] = (T)x1; v[2] = (T)x2;
-      return v;
     } else {
       int cb = cb0 + 2 * s, t = tap0;
       while (cb >= Cin8) { cb -= Cin8; ++t; }
@@ -642,15 +628,20 @@ hipError_t launch_lds(ConvArgs a, int kind, hipStream_t st) {
   X(10, 1, 2, 2, 2, 1)  \
   X(11, 1, 1, 1, 1, 4)
 
-constexpr int kNumCfg = 12;
+constexpr int kNumCfg = ymc::count(ymc::F_DIRECT);
 constexpr Cfg kCfgs[kNumCfg] = {
 #define YM_X(id, a, b, c, d, e) {a, b, c, d, e},
     YM_CONV_CFGS(YM_X)
 #undef YM_X
 };
 
-constexpr int kNumAllCfg = 17;
+constexpr int kNumLds = 0
+#define YM_X(id, BM_, BN_) +1
+    YM_LDS_CFGS(YM_X);
+#undef YM_X
+static_assert(kNumLds == ymc::count(ymc::F_LDS), "csrc/ym_conv_catalog.h");
 
+// id: a direct tile, or from kNumCfg on an LDS tile (ymc::table_index)
 template <typename M, typename OutT>
 hipError_t launch_id(int id, const ConvArgs& a, int kind, hipStream_t st) {
   switch (id) {
@@ -694,120 +685,36 @@ int choose_cfg(const ConvArgs& a) {
 
 }  // namespace
 
-// ids [0, 17): first-generation kernels above; [17, 17 + ym_conv_dma_num_cfgs()): LDS-DMA / split-K kernels;
-// then ym_conv_stream_num_cfgs() streaming / small-M kernels (csrc/ym_conv_stream.hip), then
-// ym_conv_halo_num_cfgs() halo-tile 3x3 kernels (csrc/ym_conv_halo.hip), then ym_conv_bneck_num_cfgs() fused
-// Bottleneck kernels (csrc/ym_conv_bneck.hip; fused pairs with a 3x3 successor only) — appended last so the ids of
-// committed tables stay valid
-int ym_conv_num_cfgs() {
-  return kNumAllCfg + ym_conv_dma_num_cfgs() + ym_conv_stream_num_cfgs() + ym_conv_halo_num_cfgs() +
-         ym_conv_bneck_num_cfgs();
-}
-// x3 plans: + the x3-only LDS-DMA configurations, appended (the f16 ids, and so the f16 tables, are unchanged)
-int ym_conv_num_cfgs_dt(int dtype) {
-  // int8: conv_i8 / streaming ids, then the LDS-DMA configurations in their Q8 mode (round 6); fp8: conv_i8 only
-  if (dtype == YM_DT_I8) return ym_conv_i8_num_cfgs() + ym_conv_dma_num_cfgs();
-  if (ym_dt_q8(dtype)) return ym_conv_i8_num_cfgs();
-  return ym_conv_num_cfgs() + (dtype == YM_DT_X3 ? ym_conv_dma_x3_num_cfgs() + ym_conv_bneck_x3_num_cfgs() : 0);
-}
-
+// The id space of `cfg`, the families behind it and which of them a shape admits: csrc/ym_conv_catalog.h.  Here: the
+// shape facts its dispatch routine reads, and the launcher of each family.
 hipError_t ym_launch_conv(int dtype, int out_f32, const ConvArgs& a, int cfg, hipStream_t st, bool strict,
                           int* taken) {
-  // a depthwise-fused 1x1 (csrc/ym_conv_dwpw.hip) runs on its own kernel only: no other family computes the depthwise
-  if (a.dw_w) return ym_launch_conv_dwpw(dtype, out_f32, a, cfg, st, strict, taken);
-  // *taken: 0 (a pinned cfg fell back) until the launch of cfg's own kernel succeeds (`ran`)
-  if (taken) *taken = (cfg >= 0 && !ym_dt_q8(dtype)) ? 0 : -1;
-  auto ran = [taken](hipError_t e) {
-    if (taken && e == hipSuccess) *taken = 1;
-    return e;
+  static_assert(hipSuccess == ymc::kOk && hipErrorInvalidValue == ymc::kRefused, "csrc/ym_conv_catalog.h");
+  const ymc::ConvShape shape = {a.dw_w != nullptr, a.nchw != nullptr, a.k, a.s, a.src1 != nullptr, a.up0 != 0,
+                                a.w2 != nullptr, a.k2, a.Kpad % KSTEP == 0, ym_dt_q8(dtype) && ym_conv_i8_applies(a)};
+  const int kind = ymc::conv_kind(dtype, shape);
+  const bool f8 = dtype == YM_DT_F8;
+  auto tile = [&](int id) -> hipError_t {  // launch_id's tile (id < 0: the heuristic's) in the plan's arithmetic mode
+    if (id < 0) id = choose_cfg(a);
+    if (dtype == YM_DT_F16) return out_f32 ? launch_id<f16, float>(id, a, kind, st) : launch_id<f16, f16>(id, a, kind, st);
+    if (dtype == YM_DT_X3) return out_f32 ? launch_id<x3_t, float>(id, a, kind, st) : launch_id<x3_t, P2>(id, a, kind, st);
+    return launch_id<float, float>(id, a, kind, st);
   };
-  int kind;
-  if (a.nchw) kind = (a.k == 3 && a.Cin8 == 1) ? 0 : -1;
-  else if (a.k == 1 && a.s == 1) kind = 1;
-  else if (a.k == 3 && !a.src1 && !a.up0) kind = 3;
-  else kind = -1;
-  if (kind < 0) return hipErrorInvalidValue;
-  if (ym_dt_q8(dtype)) return ym_launch_conv_i8(a, cfg, st, strict, dtype == YM_DT_F8);  // csrc/ym_conv_i8.hip
-  // (concat/upsample sources only feed 1x1 convs; YOLO11 has k in {1, 3})
-  if (a.Kpad % KSTEP) return hipErrorInvalidValue;
-  if (a.w2 && a.k2 == 3) {  // fused Bottleneck (3x3 -> 3x3): csrc/ym_conv_bneck.hip (f16 and x3 plans)
-    if (dtype != YM_DT_F16 && dtype != YM_DT_X3) return hipErrorInvalidValue;
-    const int bb = kNumAllCfg + ym_conv_dma_num_cfgs() + ym_conv_stream_num_cfgs() + ym_conv_halo_num_cfgs();
-    const int nb = ym_conv_bneck_num_cfgs();
-    const int xb = ym_conv_num_cfgs() + ym_conv_dma_x3_num_cfgs();  // x3-only Bottleneck ids
-    if (cfg >= bb && cfg < bb + nb) {
-      const hipError_t e = ran(ym_launch_conv_bneck(out_f32, a, cfg - bb, st));
-      if (e != hipErrorInvalidValue || strict) return e;
-    } else if (dtype == YM_DT_X3 && cfg >= xb && cfg < xb + ym_conv_bneck_x3_num_cfgs()) {
-      const hipError_t e = ran(ym_launch_conv_bneck(out_f32, a, nb + cfg - xb, st));
-      if (e != hipErrorInvalidValue || strict) return e;
-    } else if (strict) {
-      return hipErrorInvalidValue;
+  auto launch = [&](ymc::Family f, int local) -> int {
+    const int i = ymc::table_index(f, local);
+    switch (f) {
+      case ymc::F_DIRECT: case ymc::F_LDS: return tile(i);
+      case ymc::F_DMA: case ymc::F_DMA_X3:
+        return ym_dt_q8(dtype) ? ym_launch_conv_dma_i8(a, i, st)
+                               : (a.w2 ? ym_launch_conv_dma_fuse(out_f32, a, i, st) : ym_launch_conv_dma(out_f32, a, i, st));
+      case ymc::F_STREAM: case ymc::F_SMALL: return ym_launch_conv_stream(out_f32, a, i, st);
+      case ymc::F_HALO: return ym_launch_conv_halo(out_f32, a, i, st);
+      case ymc::F_BNECK: case ymc::F_BNECK_X3: return ym_launch_conv_bneck(out_f32, a, i, st);
+      case ymc::F_I8: return ym_launch_conv_i8(a, i, st, f8);
+      case ymc::F_I8_STREAM: return ym_launch_conv_i8_stream(a, i, st, f8);
+      case ymc::F_DWPW: return ym_launch_conv_dwpw(dtype, out_f32, a, i, st);
+      default: return hipErrorInvalidValue;
     }
-    for (int i = 0; i < nb; ++i) {  // untuned: the first variant that takes the shape
-      const hipError_t e = ym_launch_conv_bneck(out_f32, a, i, st);
-      if (e != hipErrorInvalidValue) return e;
-    }
-    return hipErrorInvalidValue;
-  }
-  if (a.w2) {  // fused pair: the streaming kernels hold a whole N in one wave (csrc/ym_conv_stream.hip); a stride-2
-    // 3x3 followed by a 1x1 can also take the band kernel of csrc/ym_conv_bneck.hip (f16 only)
-    if (dtype != YM_DT_F16 && dtype != YM_DT_X3) return hipErrorInvalidValue;
-    const int bb = kNumAllCfg + ym_conv_dma_num_cfgs() + ym_conv_stream_num_cfgs() + ym_conv_halo_num_cfgs();
-    if (cfg >= bb && cfg < bb + ym_conv_bneck_num_cfgs()) {
-      const hipError_t e = ran(ym_launch_conv_bneck(out_f32, a, cfg - bb, st));
-      if (e != hipErrorInvalidValue || strict) return e;
-    }
-    const int sbase = kNumAllCfg + ym_conv_dma_num_cfgs(), ns = ym_conv_stream_num_cfgs();
-    if (dtype == YM_DT_X3 && a.k2 == 1 && cfg >= kNumAllCfg && cfg < sbase) {  // LDS-DMA ids: the fused-epilogue GEMM
-      const hipError_t e = ran(ym_launch_conv_dma_fuse(out_f32, a, cfg - kNumAllCfg, st));
-      if (e != hipErrorInvalidValue || strict) return e;
-    }
-    if (cfg >= sbase && cfg < sbase + ns) {
-      const hipError_t e = ran(ym_launch_conv_stream(out_f32, a, cfg - sbase, st));
-      if (e != hipErrorInvalidValue || strict) return e;
-    } else if (strict) {
-      return hipErrorInvalidValue;
-    }
-    for (int i = 0; i < ns; ++i) {  // untuned: the first streaming variant that takes the shape
-      const hipError_t e = ym_launch_conv_stream(out_f32, a, i, st);
-      if (e != hipErrorInvalidValue) return e;
-    }
-    return hipErrorInvalidValue;
-  }
-  if (dtype == YM_DT_X3 && cfg >= ym_conv_num_cfgs()) {  // the x3-only LDS-DMA configurations (and, past them, the
-                                                          // x3-only Bottleneck ids: inapplicable to a single conv)
-    const hipError_t e = ran(ym_launch_conv_dma(out_f32, a, ym_conv_dma_num_cfgs() + cfg - ym_conv_num_cfgs(), st));
-    if (e != hipErrorInvalidValue || strict) return e;
-    cfg = -1;
-  }
-  if (cfg >= kNumAllCfg) {
-    // a DMA config that does not apply to this op (checked before anything is launched): the tuner skips the
-    // candidate (strict); a pinned table falls back to the heuristic
-    const int ndma = ym_conv_dma_num_cfgs(), nstr = ym_conv_stream_num_cfgs();
-    hipError_t e = hipErrorInvalidValue;
-    if (dtype == YM_DT_F16 || (dtype == YM_DT_X3 && cfg - kNumAllCfg < ndma + nstr)) {  // x3: LDS-DMA, streaming
-      const int i = cfg - kNumAllCfg;
-      e = i < ndma ? ym_launch_conv_dma(out_f32, a, i, st)
-                   : (i < ndma + nstr ? ym_launch_conv_stream(out_f32, a, i - ndma, st)
-                                      : ym_launch_conv_halo(out_f32, a, i - ndma - nstr, st));
-      ran(e);
-    }
-    if (e != hipErrorInvalidValue || strict) return e;
-    cfg = -1;
-  }
-  int id = (cfg >= 0 && cfg < kNumAllCfg) ? cfg : choose_cfg(a);
-  if (id >= kNumCfg && dtype == YM_DT_F32) id = choose_cfg(a);  // LDS variants: f16 and x3 plans
-  const bool pinned = id == cfg;  // (else the heuristic's tile)
-  auto ran_id = [&](hipError_t e) { return pinned ? ran(e) : e; };
-  if (dtype == YM_DT_F16)
-    return ran_id(out_f32 ? launch_id<f16, float>(id, a, kind, st) : launch_id<f16, f16>(id, a, kind, st));
-  if (dtype == YM_DT_X3) {
-    auto go = [&](int i) { return out_f32 ? launch_id<x3_t, float>(i, a, kind, st) : launch_id<x3_t, P2>(i, a, kind, st); };
-    const hipError_t e = ran_id(go(id));
-    // an LDS tile whose 64-deep stage does not divide this op's K: the tuner skips it (strict), a pinned table
-    // falls back to the heuristic direct-to-register tile
-    return (e == hipErrorInvalidValue && !strict && id >= kNumCfg) ? go(choose_cfg(a)) : e;
-  }
-  return ran_id(launch_id<float, float>(id, a, kind, st));
+  };
+  return (hipError_t)ymc::dispatch_conv(dtype, shape, cfg, strict, taken, launch);
 }

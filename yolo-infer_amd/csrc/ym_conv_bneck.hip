@@ -437,8 +437,7 @@ hipError_t dispatch_cfg(const ConvArgs& a, int i, hipStream_t st) {
 
 }  // namespace
 
-int ym_conv_bneck_num_cfgs() { return kNumBneck; }
-int ym_conv_bneck_x3_num_cfgs() { return kNumBneckX3; }
+static_assert(kNumBneck == ymc::count(ymc::F_BNECK) && kNumBneckX3 == ymc::count(ymc::F_BNECK_X3), "csrc/ym_conv_catalog.h");
 
 // Host-side applicability: a fused pair (w2) of a 3x3 / pad 1 conv on one plain source followed by either
 //   * a 3x3 stride-1 conv (k2 == 3, first conv stride 1): a Bottleneck; the residual, if any, IS the input view, or

@@ -1194,8 +1194,7 @@ hipError_t ym_launch_conv_dma_fuse(int out_f32, const ConvArgs& a, int i, hipStr
   return out_f32 ? dispatch_fuse<float>(a, kind, i, st) : dispatch_fuse<P2>(a, kind, i, st);
 }
 
-int ym_conv_dma_num_cfgs() { return kNumDma; }
-int ym_conv_dma_x3_num_cfgs() { return kNumDmaX3; }
+static_assert(kNumDma == ymc::count(ymc::F_DMA) && kNumDmaX3 == ymc::count(ymc::F_DMA_X3), "csrc/ym_conv_catalog.h");
 
 // Host-side applicability: f16 plans, 1x1 stride-1 or 3x3 convs, byte offsets < 2^31 for every operand, and a
 // 64-aligned concat split (a stage never straddles the two sources).  i >= kNumDma: the x3-only configurations.

@@ -323,13 +323,10 @@ hipError_t launch_cfg(const ConvArgs& a, int cfg, hipStream_t st) {
 
 }  // namespace
 
-int ym_conv_dwpw_num_cfgs() { return kNumDwpw; }
+static_assert(kNumDwpw == ymc::count(ymc::F_DWPW), "csrc/ym_conv_catalog.h");
 
-// cfg: a configuration index (the tuner's id space for these ops; ym_launch_conv), or -1 / out of range: heuristic
-// (strict: out of range is rejected)
-hipError_t ym_launch_conv_dwpw(int dtype, int out_f32, const ConvArgs& a, int cfg, hipStream_t st, bool strict,
-                               int* taken) {
-  if (taken) *taken = cfg >= 0 ? 0 : -1;
+// cfg: a configuration index (the tuner's id space for these ops; ym_launch_conv), or < 0: the heuristic
+hipError_t ym_launch_conv_dwpw(int dtype, int out_f32, const ConvArgs& a, int cfg, hipStream_t st) {
   if (dtype != YM_DT_F16 && dtype != YM_DT_X3) return hipErrorInvalidValue;
   if (out_f32 || a.k != 1 || a.s != 1 || a.src1 || a.up0 || a.shuffle || a.res || a.w2 || a.nchw) return hipErrorInvalidValue;
   if (a.N > 16 * kDwpwNB || a.N % 4 || a.C0 % 8 || a.C0 > kDwpwMaxC || a.Hin != a.Ho || a.Win != a.Wo) return hipErrorInvalidValue;
@@ -337,13 +334,6 @@ hipError_t ym_launch_conv_dwpw(int dtype, int out_f32, const ConvArgs& a, int cf
   // 32-bit offsets of the buffer loads
   if (a.s0_elems * 2 >= 0x7FFFFFF0L || (long)a.N * a.Kpad * 2 >= 0x7FFFFFF0L) return hipErrorInvalidValue;
   const bool x3 = dtype == YM_DT_X3;
-  if (cfg >= 0 && cfg < kNumDwpw) {
-    const hipError_t e = x3 ? launch_cfg<P2>(a, cfg, st) : launch_cfg<f16>(a, cfg, st);
-    if (taken && e == hipSuccess) *taken = 1;
-    if (e != hipErrorInvalidValue || strict) return e;  // (not strict: a split this shape cannot take → heuristic)
-  } else if (strict) {
-    return hipErrorInvalidValue;
-  }
-  cfg = a.Wo % 16 == 0 ? 0 : (a.Wo % 8 == 0 ? 1 : 2);  // a tile width that divides the map, no K split
+  if (cfg < 0) cfg = a.Wo % 16 == 0 ? 0 : (a.Wo % 8 == 0 ? 1 : 2);  // a tile width that divides the map, no K split
   return x3 ? launch_cfg<P2>(a, cfg, st) : launch_cfg<f16>(a, cfg, st);
 }

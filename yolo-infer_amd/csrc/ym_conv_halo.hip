@@ -394,7 +394,7 @@ hipError_t dispatch(const ConvArgs& a, int i, hipStream_t st) {
 
 }  // namespace
 
-int ym_conv_halo_num_cfgs() { return kNumHalo; }
+static_assert(kNumHalo == ymc::count(ymc::F_HALO), "csrc/ym_conv_catalog.h");
 
 // Host-side applicability: f16 plans; 3x3, pad 1, stride 1 or 2, one plain source (no concat / upsample), Cin a
 // multiple of the chunk, 4-aligned output channel slices (8-byte stores), element offsets < 2^30 (byte offsets of

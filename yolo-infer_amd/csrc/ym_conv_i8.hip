@@ -576,8 +576,10 @@ __global__ __launch_bounds__(256) void requant_copy(const ReqArgs a) {
 
 }  // namespace
 
-// ids [0, kNumCfg): conv_i8 above; then the streaming / small-M int8 kernels (csrc/ym_conv_i8_stream.hip)
-int ym_conv_i8_num_cfgs() { return kNumCfg + ym_conv_i8_stream_num_cfgs(); }
+static_assert(kNumCfg == ymc::count(ymc::F_I8), "csrc/ym_conv_catalog.h");
+#define YM_X(id, a, b, c, d, wk) static_assert((wk == 1) == ((ymc::kI8OneChain >> id & 1) != 0), "ymc::kI8OneChain");
+YM_I8_CFGS(YM_X)
+#undef YM_X
 
 // fp8 plans: one K chain per output (WK = 1), so the oracle's restated fp8 MFMA accumulation (oracle/quant.py
 // mfma_f8_conv) follows the kernel's order; the heuristic's choice among those configurations
@@ -593,27 +595,17 @@ int choose_cfg_f8(const ConvArgs& a) {
   return waves(0) >= 1024 ? 0 : 10;
 }
 
-hipError_t ym_launch_conv_i8(const ConvArgs& a, int cfg, hipStream_t st, bool strict, bool f8) {
+bool ym_conv_i8_applies(const ConvArgs& a) {
+  return !(a.Kpad % KSTEP || !a.q || !a.sasw || !a.biasi || (a.N & 3) || (a.s0_ctot & 15) || (a.s0_coff & 15));
+}
+
+// conv_i8 tile cfg, or (cfg < 0) the heuristic's; fp8 plans run the one-K-chain tiles only (ymc::kI8OneChain)
+hipError_t ym_launch_conv_i8(const ConvArgs& a, int cfg, hipStream_t st, bool f8) {
   int kind;
   if (a.k == 1 && a.s == 1 && !a.src1 && !a.up0) kind = 1;
   else if (a.k == 3 && !a.src1 && !a.up0) kind = 3;
   else return hipErrorInvalidValue;
-  if (a.Kpad % KSTEP || !a.q || !a.sasw || !a.biasi || (a.N & 3) || (a.s0_ctot & 15) || (a.s0_coff & 15))
-    return hipErrorInvalidValue;
-  if (f8 && (cfg >= kNumCfg || (cfg >= 0 && kCfgs[cfg].wk != 1))) {  // fp8: conv_i8 with one K chain only
-    if (strict) return hipErrorInvalidValue;
-    cfg = -1;
-  }
-  if (!f8 && cfg >= ym_conv_i8_num_cfgs()) {  // int8: the LDS-DMA kernel's Q8 mode (csrc/ym_conv_dma.hip)
-    const hipError_t e = ym_launch_conv_dma_i8(a, cfg - ym_conv_i8_num_cfgs(), st);
-    if (e != hipErrorInvalidValue || strict) return e;
-    cfg = -1;
-  }
-  if (cfg >= kNumCfg) {
-    const hipError_t e = ym_launch_conv_i8_stream(a, cfg - kNumCfg, st, f8);
-    if (e != hipErrorInvalidValue || strict) return e;
-    cfg = -1;  // a pinned table entry that does not apply: the heuristic
-  }
+  if (!ym_conv_i8_applies(a)) return hipErrorInvalidValue;
   return launch_id(cfg >= 0 ? cfg : (f8 ? choose_cfg_f8(a) : choose_cfg(a)), a, kind, st, f8);
 }
 

@@ -289,7 +289,7 @@ hipError_t launch_small(const ConvArgs& a, hipStream_t st) {
 
 }  // namespace
 
-int ym_conv_i8_stream_num_cfgs() { return kNumStream + kNumSmall; }
+static_assert(kNumStream + kNumSmall == ymc::count(ymc::F_I8_STREAM), "csrc/ym_conv_catalog.h");
 
 // Host-side applicability: one plain source (int8 plans materialise concats and upsamples), no pixel shuffle,
 // N % 4 == 0, 16-aligned channel slices, 1x1 stride 1 or 3x3 pad 1, LDS within 80 KB.

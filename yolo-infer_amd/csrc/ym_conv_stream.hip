@@ -581,7 +581,7 @@ hipError_t dispatch(const ConvArgs& a, int i, hipStream_t st) {
 
 }  // namespace
 
-int ym_conv_stream_num_cfgs() { return kNumStream + kNumSmall; }
+static_assert(kNumStream == ymc::count(ymc::F_STREAM) && kNumSmall == ymc::count(ymc::F_SMALL), "csrc/ym_conv_catalog.h");
 
 // Host-side applicability: f16 plans; 1x1 stride-1 convs without pixel shuffle (8-channel-aligned concat split) or
 // 3x3 convs on one plain source; N % 4 == 0 and 4-aligned output channel slices

@@ -313,7 +313,7 @@ struct ym_ctx {
       if (cfgs[i].B == B && cfgs[i].H == H && cfgs[i].W == W) { cfgs.erase(cfgs.begin() + i); return; }
   }
   // tests (ym_get_op_cfg_taken): per op of the last forward launched, whether its pinned cfg was the kernel that ran
-  // ([2i]: the op, or the first conv of a kSplitTag pair; [2i + 1]: the pair's second conv; ym_launch_conv's `taken`)
+  // ([2i]: the op, or the first conv of a split pair; [2i + 1]: the pair's second conv; ym_launch_conv's `taken`)
   std::vector<int> taken;
   int tkB = 0, tkH = 0, tkW = 0;
   int op_cfg(long i, int B) const {  // for the current workspace height/width
@@ -507,7 +507,6 @@ int conv_args(ym_ctx* c, const Launch& L, const Op& op, int B, const float* d_in
         mid >= (int)c->bufs.size() || cout % 8 || c->buf_H(mid) != a.Ho || c->buf_Wd(mid) != a.Wo ||
         c->bufs[mid].C != cout || c->bufs[mid].f32)
       return fail(YM_EBLOB, "op %s: bad fused-pair geometry", op.name);
-    if (ym_conv_num_cfgs_dt(c->dtype) > 255) return fail(YM_EBLOB, "split cfg encoding needs < 256 conv configs");
   }
   if (op.has_fused_dw() && !ym_dt_q8(c->dtype)) {  // fused depthwise (yolomi/arch.py fuse_dw): [9][C] weights ‖ [C] bias
     if ((c->dtype != YM_DT_F16 && c->dtype != YM_DT_X3) || k != 1 || s != 1 || b1 >= 0 || up0 || op.k2)
@@ -552,8 +551,7 @@ int conv_args(ym_ctx* c, const Launch& L, const Op& op, int B, const float* d_in
 }
 
 // A fused pair (ConvArgs::w2) run as its two convs: A writes the intermediate buffer (the record's `mid`), B reads it.
-// The tuner picks this when the two tuned single launches beat every fused variant (op cfg kSplitTag + ...).
-constexpr int kSplitTag = 1 << 20;  // op cfg = kSplitTag + 256 * cfg(A) + cfg(B)
+// The tuner picks this when the two tuned single launches beat every fused variant (op cfg ymc::split_encode).
 void split_args(ym_ctx* c, const Launch& L, const Op& op, const ConvArgs& a, ConvArgs& A, ConvArgs& Bc) {
   const int mid = op.mid;
   A = a;
@@ -572,27 +570,24 @@ void split_args(ym_ctx* c, const Launch& L, const Op& op, const ConvArgs& a, Con
   Bc.s0_elems = (long)xs * c->cB * c->buf_P(mid) * c->bufs[mid].C;
 }
 
-// taken[2]: ym_launch_conv's `taken` of the fused launch, or of the two convs of a kSplitTag cfg (a half's id 255 is
-// "heuristic": -1); a fused cfg that fell back to the split pair is {0, -1}
+// taken[2]: ym_launch_conv's `taken` of the fused launch, or of the two convs of a split cfg (a "heuristic" half:
+// -1); a fused cfg that fell back to the split pair is {0, -1}
 hipError_t launch_fused(ym_ctx* c, const Launch& L, const Op& op, const ConvArgs& a, int out_f32, int cfg,
                         hipStream_t st, int* taken) {
-  const bool tagged = cfg >= kSplitTag;
+  const bool tagged = ymc::is_split(cfg);
   if (!tagged) {
     const hipError_t e = ym_launch_conv(c->dtype, out_f32, a, cfg, st, false, &taken[0]);
     if (e != hipErrorInvalidValue) return e;
-    cfg = kSplitTag + 256 * 255 + 255;  // no fused kernel takes this shape (e.g. a map width the Bottleneck kernel
-  }                                     // does not tile): the two convs with their heuristic tiles
+    // no fused kernel takes this shape (e.g. a map width the Bottleneck kernel does not tile): the two convs with
+    cfg = ymc::split_encode(ymc::kSplitHeuristic, ymc::kSplitHeuristic);  // their heuristic tiles
+  }
   ConvArgs A, Bc;
   split_args(c, L, op, a, A, Bc);
-  const int ca = ((cfg - kSplitTag) >> 8) & 255, cb = (cfg - kSplitTag) & 255;
-  int ta = -1, tb = -1;
-  hipError_t e = ym_launch_conv(c->dtype, 0, A, ca, st, false, &ta);
-  if (e == hipSuccess) e = ym_launch_conv(c->dtype, out_f32, Bc, cb, st, false, &tb);
-  if (tagged) {
-    taken[0] = ca == 255 ? -1 : ta;
-    taken[1] = cb == 255 ? -1 : tb;
-  }
-  return e;
+  int* const ta = tagged ? &taken[0] : nullptr;  // (a fallback from the fused cfg keeps that launch's {0, -1})
+  int* const tb = tagged ? &taken[1] : nullptr;
+  const hipError_t e = ym_launch_conv(c->dtype, 0, A, ymc::split_cfg(ymc::split_first(cfg)), st, false, ta);
+  if (e != hipSuccess) return e;
+  return ym_launch_conv(c->dtype, out_f32, Bc, ymc::split_cfg(ymc::split_second(cfg)), st, false, tb);
 }
 
 // Where an NMS stage reads per-candidate rows: the nm extras the NMS kernel copies behind each kept box, and the
@@ -860,7 +855,7 @@ int ym_version(void) { return 1; }
 int ym_num_conv_cfgs(int dtype) {  // public dtype codes (ym_model_desc): 1 f16, 2 f32, 3 i8, 4 f8, 5 x3
   if (dtype < 1 || dtype > 5) return YM_EINVAL;
   static const int dt[6] = {0, YM_DT_F16, YM_DT_F32, YM_DT_I8, YM_DT_F8, YM_DT_X3};
-  return ym_conv_num_cfgs_dt(dt[dtype]);
+  return ymc::num_cfgs(dt[dtype]);
 }
 
 const char* ym_last_error(void) { return g_err.c_str(); }
@@ -1659,7 +1654,7 @@ int ym_tune(ym_ctx* c, const float* d_in, int B, int H, int W, const ym_infer_ar
     if ((rc = launch_op(c, L, op, B, d_in, args, d_dets, d_counts, st))) return rc;
   HIPCK(hipStreamSynchronize(st));
   std::vector<int> best(c->ops.size(), -1);
-  const int ncfg = ym_conv_num_cfgs_dt(c->dtype);
+  const int ncfg = ymc::num_cfgs(c->dtype);
   const char* tl = getenv("YM_TUNE_LOG");  // per-candidate timings to stderr (tools/)
   const bool tune_log = tl && *tl && *tl != '0';
   for (size_t i = 0; i < c->ops.size(); ++i) {
@@ -1695,7 +1690,7 @@ int ym_tune(ym_ctx* c, const float* d_in, int B, int H, int W, const ym_infer_ar
       int ca = -1, cb = -1;
       float ta = 0.f, tb = 0.f;
       if ((rc = tune_one(A, 0, ca, ta)) || (rc = tune_one(Bc, out_f32, cb, tb))) return rc;
-      if (ca >= 0 && cb >= 0 && ta + tb < tf) best[i] = kSplitTag + 256 * ca + cb;
+      if (ca >= 0 && cb >= 0 && ta + tb < tf) best[i] = ymc::split_encode(ca, cb);
     }
   }
   c->clear_graphs();
@@ -1712,12 +1707,12 @@ int ym_get_op_cfg(ym_ctx* c, int B, int H, int W, int* cfg, int n) {
 
 int ym_set_op_cfg(ym_ctx* c, int B, int H, int W, const int* cfg, int n) {
   if (!c || !cfg || n != (int)c->ops.size()) return fail(YM_EINVAL, "cfg array must hold %zu entries", c ? c->ops.size() : 0);
+  const int ncfg = ymc::num_cfgs(c->dtype);
   for (int i = 0; i < n; ++i) {
-    if (cfg[i] >= kSplitTag && c->ops[i].kind == OP_CONV && c->ops[i].k2 &&
-        ((cfg[i] - kSplitTag) >> 8) < ym_conv_num_cfgs_dt(c->dtype) &&
-        ((cfg[i] - kSplitTag) & 255) < ym_conv_num_cfgs_dt(c->dtype))
+    if (ymc::is_split(cfg[i]) && c->ops[i].kind == OP_CONV && c->ops[i].k2 && ymc::split_first(cfg[i]) < ncfg &&
+        ymc::split_second(cfg[i]) < ncfg)
       continue;  // a fused pair run as two launches
-    if (cfg[i] >= ym_conv_num_cfgs_dt(c->dtype)) return fail(YM_EINVAL, "cfg[%d] = %d out of range", i, cfg[i]);
+    if (cfg[i] >= ncfg) return fail(YM_EINVAL, "cfg[%d] = %d out of range", i, cfg[i]);
   }
   c->put_cfg(B, H, W, std::vector<int>(cfg, cfg + n));
   c->clear_graphs();

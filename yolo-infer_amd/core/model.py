@@ -90,6 +90,83 @@ def _load_state_dict(path: Path) -> Dict[str, np.ndarray]:
     raise ValueError(f"unsupported weights file {path} (use an Ultralytics .pt, a state-dict .pt, .safetensors or .npz)")
 
 
+# ---------------------------------------------------------------------- the call path's shared pieces
+# predict(), track() and retina_masks share these; they take tensors and plain values (and run on CPU tensors).
+def _nms_kwargs(kwargs, conf: float = 0.25) -> Dict[str, Any]:
+    """The NMS keywords of a predict / track call under Engine.run's names (conf: the call's default threshold)."""
+    return {"conf": float(kwargs.get("conf", conf)), "iou": float(kwargs.get("iou", 0.7)),
+            "max_det": int(kwargs.get("max_det", 300)), "classes": kwargs.get("classes", None),
+            "agnostic": bool(kwargs.get("agnostic_nms", False))}
+
+
+def _speed(t0, t1) -> Dict[str, float]:
+    """Host ms of the call so far: preprocess = between the two stamps, inference = since the second (a forward still
+    in flight on the asynchronous path is not in it)."""
+    return {"preprocess": (t1 - t0) * 1e3, "inference": (time.perf_counter() - t1) * 1e3, "postprocess": 0.0}
+
+
+def _rows_to_source(out, n, in_shape, shapes, kcol: Optional[int] = None, kpt_shape=None):
+    """ops.scale_boxes of image b's first n[b] rows back to its source image of shapes[b], in place; kcol: the rows'
+    first keypoint column (6, track rows 7) — the (K, ndim) keypoints go through ops.scale_coords; None: boxes only."""
+    from yolomi.preprocess import scale_boxes, scale_coords
+    for b in range(len(n)):
+        if n[b]:
+            scale_boxes(in_shape, out[b, : n[b], :4], shapes[b])
+            if kcol is not None:
+                K, nd = kpt_shape
+                scale_coords(in_shape, out[b, : n[b], kcol:kcol + K * nd].view(n[b], K, nd), shapes[b])
+
+
+def _lazy_results(im, out, cnt, names, eng, t0, t1, sync, tracked=False, det_idx=None) -> List[Results]:
+    """The tail of an asynchronous call (tensor source, detect / pose): the NMS kernel wrote this call's rows AND its B
+    counts (the int32 words behind the rows) into a fresh buffer, so no host sync is needed: the Results read the counts
+    on first access (one device->host read shared by the call's B Results), and back-to-back calls queue their forwards
+    with no host gap between them.  sync (per-call latency loops): return only once the forward is done.  tracked,
+    det_idx: track()'s rows and the detection row behind each."""
+    lazy = LazyCounts(cnt, torch.cuda.current_stream(im.device))
+    if sync:
+        lazy[0]
+    speed = _speed(t0, t1)  # host time of the calls (the forward itself runs asynchronously)
+    kpt_shape = eng.kpt_shape
+    return [Results.from_batch(im, b, names, out, lazy, path=f"image{b}.jpg", speed=speed, kpt_shape=kpt_shape,
+                               tracked=tracked, det_idx=det_idx, annotator=eng) for b in range(im.shape[0])]
+
+
+def _image_results(imsrc, out, n, names, eng, speed, ncol: int, pose: bool) -> List[Results]:
+    """The tail of an image-source detect / pose call: boxes = the first ncol columns of the rows (already in each
+    source image's coordinates), a pose model's keypoints the nk columns behind them."""
+    return [Results.from_image(imsrc[0][b], imsrc[1][b], names, out[b, : n[b], :ncol], speed=speed,
+                               keypoints=(out[b, : n[b], ncol:ncol + eng.nk].reshape(n[b], *eng.kpt_shape)
+                                          if pose else None), annotator=eng)
+            for b in range(len(n))]
+
+
+def _segment_results(im, imsrc, names, eng, speed, out, n, keep, offs, planes, whole: bool, geo=None) -> List[Results]:
+    """The B Results of a segment call; the predictor keeps only detections whose mask is non-empty (keep: the flags,
+    image b's at offs[b]).  whole: planes is one bool tensor of all the call's mask planes, image b's at offs[b] (the
+    Results get it whole, with that offset); else a list of B per-image (n[b], h, w) views (retina_masks: native sizes
+    differ).  geo: per image (uh, uw, top, left) when an image source's masks are in letterboxed coordinates."""
+    res = []
+    for b in range(len(n)):
+        kb = keep[offs[b]:offs[b] + n[b]]
+        if all(kb) and imsrc is None:  # the common case: boxes, masks and input slice as views taken on access
+            res.append(Results.from_batch(im, b, names, out, n[b], path=f"image{b}.jpg", speed=speed,
+                                          masks=planes if whole else planes[b], moff=offs[b] if whole else 0,
+                                          annotator=eng))
+            continue
+        bx, mk = out[b, :n[b], :6], planes[offs[b]:offs[b] + n[b]] if whole else planes[b]
+        if not all(kb):  # else every kept detection has a mask pixel — views, no gathers
+            sel = torch.tensor([i for i, k in enumerate(kb) if k], dtype=torch.long, device=out.device)
+            bx = out[b].index_select(0, sel)[:, :6] if whole else bx.index_select(0, sel)  # (strides as they were)
+            mk = mk.index_select(0, sel)
+        if imsrc is None:
+            res.append(Results(im[b], names, bx, path=f"image{b}.jpg", speed=speed, masks=mk, annotator=eng))
+        else:  # letterboxed masks: plot() maps the image into its window of the plane (geo)
+            res.append(Results.from_image(imsrc[0][b], imsrc[1][b], names, bx, speed=speed, masks=mk, annotator=eng,
+                                          mask_geo=geo[b] if geo is not None else None))
+    return res
+
+
 class YOLO11Model:
     SUPPORTED_TASKS = {
         "detect": "yolo11n.pt",
@@ -216,124 +293,89 @@ class YOLO11Model:
         im = im.float().contiguous()
         return im, eps, None
 
+    def _begin(self, source, kwargs):
+        """The start of every call: (batch, LoadTensor eps, image-source info or None, the global batch max or None,
+        the time stamps before and after preprocessing)."""
+        t0 = time.perf_counter()
+        im, eps, imsrc = self._as_batch(source, int(kwargs.get("imgsz", 640)))
+        t1 = time.perf_counter()
+        bm = self.global_batch_max(im) if self.global_batch_max is not None and imsrc is None else None
+        return im, eps, imsrc, bm, t0, t1
+
     def predict(self, source, **kwargs) -> List[Results]:
-        conf = float(kwargs.get("conf", 0.25))
-        iou = float(kwargs.get("iou", 0.7))
-        max_det = int(kwargs.get("max_det", 300))
-        classes = kwargs.get("classes", None)
-        agnostic = bool(kwargs.get("agnostic_nms", False))
+        nms = _nms_kwargs(kwargs)
         augment = bool(kwargs.get("augment", False))
         if kwargs.get("embed", None) is not None:
             return self._predict_embed(source, kwargs)
         if augment and self.task != "detect":  # as upstream: only the Detect head is augmented
             logger.warning(f"augment=True is not supported for {self.task} models: predicting at a single scale")
             augment = False
-        t0 = time.perf_counter()
-        im, eps, imsrc = self._as_batch(source, int(kwargs.get("imgsz", 640)))
-        t1 = time.perf_counter()
+        im, eps, imsrc, bm, t0, t1 = self._begin(source, kwargs)
         eng = self.model.engine
-        run = eng.run_tta if augment else eng.run  # test-time augmentation: three scaled passes, one NMS
-        bm = self.global_batch_max(im) if self.global_batch_max is not None and imsrc is None else None
-        B = im.shape[0]
         names = self.model.names
         if self.task == "segment" and bool(kwargs.get("retina_masks", False)):  # detect / pose ignore it, as upstream
-            return self._predict_retina(im, eps, imsrc, bm, (t0, t1), conf=conf, iou=iou, max_det=max_det,
-                                        classes=classes, agnostic=agnostic)
-        if self.task != "segment" and imsrc is None:
-            # Asynchronous call: the NMS kernel writes this call's rows AND its B detection counts (the int32 words
-            # behind the rows) into a fresh buffer, so no host sync is needed here: the Results read the counts on
-            # first access (one device->host read shared by the call's B Results), and back-to-back predict() calls
-            # queue their forwards with no host gap between them.
+            return self._predict_retina(im, eps, imsrc, bm, t0, t1, nms)
+        run = eng.run_tta if augment else eng.run  # test-time augmentation: three scaled passes, one NMS
+        B, max_det = im.shape[0], nms["max_det"]
+        if self.task != "segment" and imsrc is None:  # asynchronous: rows and counts in one fresh buffer, no host sync
             out, cnt = eng.rows_buffer(B, max_det)
-            run(im, conf=conf, iou=iou, max_det=max_det, classes=classes, agnostic=agnostic, in_eps=eps,
-                batch_max=bm, dets_out=out, counts_after=True)
-            lazy = LazyCounts(cnt, torch.cuda.current_stream(im.device))
-            if kwargs.get("sync", False):  # per-call latency loops: return only once the forward is done
-                lazy[0]
-            speed = {"preprocess": (t1 - t0) * 1e3, "inference": (time.perf_counter() - t1) * 1e3,
-                     "postprocess": 0.0}  # host time of the calls (the forward itself runs asynchronously)
-            return [Results.from_batch(im, b, names, out, lazy, path=f"image{b}.jpg", speed=speed,
-                                       kpt_shape=eng.kpt_shape, annotator=eng) for b in range(B)]
+            run(im, in_eps=eps, batch_max=bm, dets_out=out, counts_after=True, **nms)
+            return _lazy_results(im, out, cnt, names, eng, t0, t1, kwargs.get("sync", False))
         # the NMS kernel writes this call's rows straight into a fresh tensor (the Results keep views into it)
         out = torch.empty((B, max_det, 6 + eng.nm), dtype=torch.float32, device=im.device)
-        dets, counts = run(im, conf=conf, iou=iou, max_det=max_det, classes=classes, agnostic=agnostic,
-                           in_eps=eps, batch_max=bm, dets_out=out)
-        masks = None
+        _, counts = run(im, in_eps=eps, batch_max=bm, dets_out=out, **nms)
+        pose = self.task == "pose"
         if self.task == "segment":  # process_mask(upsample=True) on the GPU, in letterboxed coordinates
-            # the masks of the first `cap` detections per image are enqueued behind the forward, reading the device
-            # counts, so ONE device→host read returns counts and non-empty flags; a batch with more detections per
-            # image than `cap` takes the exact-size two-read path (and raises `cap` for the next call)
-            # Memory: the slot buffer is B x cap x H x W bytes, so it is only used within
-            # YM_MASK_BUDGET_MB (256 MB by default; larger batches take the exact-size path), `cap` follows the recent
-            # detection counts down as well as up (1.25x the last maximum rounded up to 16, 16..max_det: a steady
-            # stream of batches keeps its slots over half full, so no compaction copy runs), and a mostly empty slot
-            # buffer is compacted before the Results views are taken, so results kept by the caller retain at most
-            # twice the bytes of their masks.
-            H, W = im.shape[2:]
-            cap = min(self._mask_cap, max_det)
-            budget = int(os.environ.get("YM_MASK_BUDGET_MB", "256")) << 20
-            fl = None
-            if B * cap * H * W <= budget:
-                mslots, flags = eng.masks_slots(out, counts[:B], cap, H, W)
-                fl = flags.tolist()  # the device→host sync of a segment predict call
-                n = fl[B * cap:]
-            else:
-                n = counts[:B].tolist()
-            if fl is not None and max(n) <= cap:
-                masks, keep = mslots, fl
-                offs = [b * cap for b in range(B + 1)]
-                if 2 * sum(n) < B * cap:  # compact the kept slots: one gather
-                    rows = [b * cap + i for b in range(B) for i in range(n[b])]
-                    masks = mslots.reshape(B * cap, H, W).index_select(
-                        0, torch.tensor(rows, dtype=torch.long, device=mslots.device))
-                    keep = [fl[r] for r in rows]
-                    offs = [0]
-                    for b in range(B):
-                        offs.append(offs[-1] + n[b])
-            else:
-                masks, nonempty, offs = eng.masks(out, n, H, W)
-                keep = nonempty.tolist()
-            self._mask_cap = max(16, min(max_det, -(-(5 * max(max(n), 1)) // 64) * 16))  # ceil(1.25 max / 16) * 16
+            masks, keep, offs, n = self._masks_for(out, counts[:B], max_det, *im.shape[2:])
         else:
             n = counts[:B].tolist()  # the device→host sync of a predict call
-        if imsrc is not None:  # ops.scale_boxes (pose: and ops.scale_coords) back to each original image
-            from yolomi.preprocess import scale_boxes, scale_coords
-            for b in range(B):
-                if n[b]:
-                    scale_boxes(im.shape[2:], out[b, : n[b], :4], imsrc[2][b])
-                    if self.task == "pose":
-                        K, nd = eng.kpt_shape
-                        scale_coords(im.shape[2:], out[b, : n[b], 6:6 + eng.nk].view(n[b], K, nd), imsrc[2][b])
-        t2 = time.perf_counter()
-        speed = {"preprocess": (t1 - t0) * 1e3, "inference": (t2 - t1) * 1e3, "postprocess": 0.0}
-        if masks is None:
-            if imsrc is None:
-                return [Results.from_batch(im, b, names, out, n[b], path=f"image{b}.jpg", speed=speed, annotator=eng)
-                        for b in range(B)]
-            return [Results.from_image(imsrc[0][b], imsrc[1][b], names, out[b, : n[b], :6], speed=speed,
-                                       keypoints=(out[b, : n[b], 6:6 + eng.nk].reshape(n[b], *eng.kpt_shape)
-                                                  if self.task == "pose" else None), annotator=eng)
-                    for b in range(B)]
-        res = []  # Segment: the predictor keeps only non-empty masks
-        mb = masks.view(torch.bool).reshape(-1, H, W)  # the kernel writes 0/1 bytes: a bool view, no copy
-        for b in range(B):
-            kb = keep[offs[b]:offs[b] + n[b]]
-            if all(kb) and imsrc is None:  # the common case: boxes, masks and input slice as views taken on access
-                res.append(Results.from_batch(im, b, names, out, n[b], path=f"image{b}.jpg", speed=speed, masks=mb,
-                                              moff=offs[b], annotator=eng))
-                continue
-            if all(kb):  # every kept detection has a mask pixel — views, no gathers
-                bx, mk = out[b, :n[b], :6], mb[offs[b]:offs[b] + n[b]]
-            else:
-                sel = torch.tensor([i for i, k in enumerate(kb) if k], dtype=torch.long, device=out.device)
-                bx = out[b].index_select(0, sel)[:, :6]
-                mk = mb[offs[b]:offs[b] + n[b]].index_select(0, sel)
-            if imsrc is None:
-                res.append(Results(im[b], names, bx, path=f"image{b}.jpg", speed=speed, masks=mk, annotator=eng))
-            else:  # the masks are in letterboxed coordinates: plot() maps the image into its window of the plane
-                res.append(Results.from_image(imsrc[0][b], imsrc[1][b], names, bx, speed=speed, masks=mk,
-                                              annotator=eng, mask_geo=imsrc[3][b]))
-        return res
+        if imsrc is not None:  # back to each original image
+            _rows_to_source(out, n, im.shape[2:], imsrc[2], 6 if pose else None, eng.kpt_shape)
+        speed = _speed(t0, t1)
+        if self.task != "segment":
+            return _image_results(imsrc, out, n, names, eng, speed, 6, pose)
+        mb = masks.view(torch.bool).reshape(-1, *im.shape[2:])  # the kernel writes 0/1 bytes: a bool view, no copy
+        return _segment_results(im, imsrc, names, eng, speed, out, n, keep, offs, mb, True,
+                                imsrc[3] if imsrc is not None else None)
+
+    def _masks_for(self, out, counts, max_det, H, W):
+        """The mask planes of a segment call's rows, and the slot policy: (masks, keep, offs, n) — uint8 planes, image
+        b's n[b] at plane offs[b], and their non-empty flags at the same offsets — and `_mask_cap` for the next call.
+        The masks of the first `cap` detections per image are enqueued behind the forward, reading the device counts, so
+        ONE device→host read returns counts and non-empty flags; a batch with more detections per image than `cap` takes
+        the exact-size two-read path (and raises `cap` for the next call).
+        Memory: the slot buffer is B x cap x H x W bytes, so it is only used within YM_MASK_BUDGET_MB
+        (256 MB by default; larger batches take the exact-size path), `cap` follows the recent detection counts down as
+        well as up (1.25x the last maximum rounded up to 16, 16..max_det: a steady stream of batches keeps its slots
+        over half full, so no compaction copy runs), and a mostly empty slot buffer is compacted before the Results
+        views are taken, so results kept by the caller retain at most twice the bytes of their masks."""
+        eng = self.model.engine
+        B = counts.shape[0]
+        cap = min(self._mask_cap, max_det)
+        budget = int(os.environ.get("YM_MASK_BUDGET_MB", "256")) << 20
+        fl = None
+        if B * cap * H * W <= budget:
+            mslots, flags = eng.masks_slots(out, counts, cap, H, W)
+            fl = flags.tolist()  # the device→host sync of a segment predict call
+            n = fl[B * cap:]
+        else:
+            n = counts.tolist()
+        if fl is not None and max(n) <= cap:
+            masks, keep = mslots, fl
+            offs = [b * cap for b in range(B + 1)]
+            if 2 * sum(n) < B * cap:  # compact the kept slots: one gather
+                rows = [b * cap + i for b in range(B) for i in range(n[b])]
+                masks = mslots.reshape(B * cap, H, W).index_select(
+                    0, torch.tensor(rows, dtype=torch.long, device=mslots.device))
+                keep = [fl[r] for r in rows]
+                offs = [0]
+                for b in range(B):
+                    offs.append(offs[-1] + n[b])
+        else:
+            masks, nonempty, offs = eng.masks(out, n, H, W)
+            keep = nonempty.tolist()
+        self._mask_cap = max(16, min(max_det, -(-(5 * max(max(n), 1)) // 64) * 16))  # ceil(1.25 max / 16) * 16
+        return masks, keep, offs, n
 
     def track(self, source, persist: bool = False, tracker="bytetrack.yaml", **kwargs) -> List[Results]:
         """Ultralytics `model.track(source, persist=..., tracker="bytetrack.yaml")`: predict(), then ByteTrack on the GPU
@@ -355,38 +397,17 @@ class YOLO11Model:
         ignored = [k for k in ("augment", "retina_masks") if kwargs.get(k, False)]
         if ignored:
             logger.debug(f"track: {', '.join(ignored)} ignored")
-        t0 = time.perf_counter()
-        im, eps, imsrc = self._as_batch(source, int(kwargs.get("imgsz", 640)))
-        t1 = time.perf_counter()
+        im, eps, imsrc, bm, t0, t1 = self._begin(source, kwargs)
         eng = self.model.engine
-        bm = self.global_batch_max(im) if self.global_batch_max is not None and imsrc is None else None
-        B = im.shape[0]
         names = self.model.names
-        out, cnt, idx = eng.track(im, cfg, persist=bool(persist), conf=float(kwargs.get("conf", 0.1)),
-                                  iou=float(kwargs.get("iou", 0.7)), max_det=int(kwargs.get("max_det", 300)),
-                                  classes=kwargs.get("classes", None), agnostic=bool(kwargs.get("agnostic_nms", False)),
-                                  in_eps=eps, batch_max=bm)
+        out, cnt, idx = eng.track(im, cfg, persist=bool(persist), **_nms_kwargs(kwargs, conf=0.1), in_eps=eps,
+                                  batch_max=bm)
         if imsrc is None:  # asynchronous, as predict(): the counts are read on first access
-            lazy = LazyCounts(cnt, torch.cuda.current_stream(im.device))
-            if kwargs.get("sync", False):
-                lazy[0]
-            speed = {"preprocess": (t1 - t0) * 1e3, "inference": (time.perf_counter() - t1) * 1e3, "postprocess": 0.0}
-            return [Results.from_batch(im, b, names, out, lazy, path=f"image{b}.jpg", speed=speed,
-                                       kpt_shape=eng.kpt_shape, tracked=True, det_idx=idx, annotator=eng)
-                    for b in range(B)]
+            return _lazy_results(im, out, cnt, names, eng, t0, t1, kwargs.get("sync", False), True, idx)
         n = cnt.tolist()  # the device->host sync of an image-source call
-        from yolomi.preprocess import scale_boxes, scale_coords
-        for b in range(B):  # ops.scale_boxes / scale_coords after tracking, on the track rows
-            if n[b]:
-                scale_boxes(im.shape[2:], out[b, : n[b], :4], imsrc[2][b])
-                if self.task == "pose":
-                    K, nd = eng.kpt_shape
-                    scale_coords(im.shape[2:], out[b, : n[b], 7:7 + eng.nk].view(n[b], K, nd), imsrc[2][b])
-        speed = {"preprocess": (t1 - t0) * 1e3, "inference": (time.perf_counter() - t1) * 1e3, "postprocess": 0.0}
-        return [Results.from_image(imsrc[0][b], imsrc[1][b], names, out[b, : n[b], :7], speed=speed,
-                                   keypoints=(out[b, : n[b], 7:7 + eng.nk].reshape(n[b], *eng.kpt_shape)
-                                              if self.task == "pose" else None), annotator=eng)
-                for b in range(B)]
+        pose = self.task == "pose"  # scale_boxes / scale_coords after tracking, on the track rows
+        _rows_to_source(out, n, im.shape[2:], imsrc[2], 7 if pose else None, eng.kpt_shape)
+        return _image_results(imsrc, out, n, names, eng, _speed(t0, t1), 7, pose)
 
     def _predict_embed(self, source, kwargs) -> List[torch.Tensor]:
         """predict(source, embed=[layers]): Ultralytics _predict_once's embed branch.  One 1-D fp32 device tensor per
@@ -402,8 +423,7 @@ class YOLO11Model:
         ignored = [k for k in ("augment", "retina_masks") if kwargs.get(k, False)]
         if ignored:
             logger.debug(f"embed={list(layers)}: {', '.join(ignored)} ignored (the forward stops at layer {layers[-1]})")
-        im, eps, imsrc = self._as_batch(source, int(kwargs.get("imgsz", 640)))
-        bm = self.global_batch_max(im) if self.global_batch_max is not None and imsrc is None else None
+        im, eps, _, bm, _, _ = self._begin(source, kwargs)
         # the captured pooling stage writes the engine's own (B, sum C) tensor (its address is part of the graph key:
         # fresh rows per call would capture a graph per call); the caller gets a copy that later calls leave alone
         return list(eng.embed(im, layers, in_eps=eps, batch_max=bm).clone().unbind(0))
@@ -416,7 +436,7 @@ class YOLO11Model:
             kwargs["embed"] = list(DEFAULT_EMBED)
         return self.predict(source, **kwargs)
 
-    def _predict_retina(self, im, eps, imsrc, bm, t01, conf, iou, max_det, classes, agnostic) -> List[Results]:
+    def _predict_retina(self, im, eps, imsrc, bm, t0, t1, nms) -> List[Results]:
         """predict(..., retina_masks=True) on a segment model: SegmentationPredictor.construct_result's other branch.
         The boxes go to each image's native pixels first (scale_boxes; a tensor source is its own native image), then
         ops.process_mask_native on the GPU (Engine.masks_native, csrc/ym_mask_native.hip): the prototype-resolution
@@ -426,41 +446,19 @@ class YOLO11Model:
         is no slot buffer and `_mask_cap` is not touched.  No memory cap either: the packed mask buffer is the sum of
         n_b * h0_b * w0_b bytes, and torch's allocator error propagates when that does not fit."""
         eng = self.model.engine
-        names = self.model.names
         B, _, H, W = im.shape
-        out = torch.empty((B, max_det, 6 + eng.nm), dtype=torch.float32, device=im.device)
-        _, counts = eng.run(im, conf=conf, iou=iou, max_det=max_det, classes=classes, agnostic=agnostic, in_eps=eps,
-                            batch_max=bm, dets_out=out)
+        out = torch.empty((B, nms["max_det"], 6 + eng.nm), dtype=torch.float32, device=im.device)
+        _, counts = eng.run(im, in_eps=eps, batch_max=bm, dets_out=out, **nms)
         n = counts[:B].tolist()  # the first device→host read: the counts size the packed mask buffer
         shapes = [(H, W)] * B if imsrc is None else [tuple(s) for s in imsrc[2]]
         if imsrc is not None:
-            from yolomi.preprocess import scale_boxes
-            for b in range(B):
-                if n[b]:
-                    scale_boxes((H, W), out[b, : n[b], :4], shapes[b])
+            _rows_to_source(out, n, (H, W), shapes)
         packed, nonempty, offs, boffs = eng.masks_native(out, n, H, W, shapes)
         keep = nonempty.tolist()  # the second read
-        t2 = time.perf_counter()
-        speed = {"preprocess": (t01[1] - t01[0]) * 1e3, "inference": (t2 - t01[1]) * 1e3, "postprocess": 0.0}
+        speed = _speed(t0, t1)
         pb = packed.view(torch.bool)  # the kernel writes 0/1 bytes: a bool view, no copy
-        res = []
-        for b in range(B):
-            mk = pb[boffs[b]:boffs[b + 1]].view(n[b], *shapes[b])
-            kb = keep[offs[b]:offs[b + 1]]
-            if all(kb) and imsrc is None:  # boxes, masks and input slice as views taken on access
-                res.append(Results.from_batch(im, b, names, out, n[b], path=f"image{b}.jpg", speed=speed, masks=mk,
-                                              annotator=eng))
-                continue
-            bx = out[b, :n[b], :6]
-            if not all(kb):
-                sel = torch.tensor([i for i, k in enumerate(kb) if k], dtype=torch.long, device=out.device)
-                bx, mk = bx.index_select(0, sel), mk.index_select(0, sel)
-            if imsrc is None:
-                res.append(Results(im[b], names, bx, path=f"image{b}.jpg", speed=speed, masks=mk, annotator=eng))
-            else:
-                res.append(Results.from_image(imsrc[0][b], imsrc[1][b], names, bx, speed=speed, masks=mk,
-                                              annotator=eng))
-        return res
+        return _segment_results(im, imsrc, self.model.names, eng, speed, out, n, keep, offs,
+                                [pb[boffs[b]:boffs[b + 1]].view(n[b], *shapes[b]) for b in range(B)], False)
 
     def __call__(self, source, **kwargs):
         return self.predict(source, **kwargs)

@@ -38,6 +38,11 @@ REG_MAX = 16
 STRIDES = (8, 16, 32)
 
 
+def num_anchors(H: int, W: int) -> int:
+    """Anchors of an H x W input: one per cell of the three Detect levels."""
+    return sum((H // s) * (W // s) for s in STRIDES)
+
+
 def make_divisible(x: float, d: int = 8) -> int:
     return int(math.ceil(x / d) * d)
 

@@ -51,7 +51,7 @@ class Engine:
         elif receive is not None:  # a non-root rank: the model arrives over RCCL from the root's context
             self.blob = None
             self.rt = Runtime(dev_index, None, scale=scale, task=task, dtype=dtype)
-            self.rt.broadcast_weights(receive[0], receive[1], torch.cuda.current_stream(device).cuda_stream)
+            self.rt.broadcast_weights(receive[0], receive[1], self._stream())
         else:
             self.blob = blob if blob is not None else pack_graph(self.graph, state_dict, dtype, qparams)
             self.rt = Runtime(dev_index, self.blob, scale=scale, task=task, dtype=dtype)
@@ -85,7 +85,11 @@ class Engine:
     def broadcast_weights(self, comm: int, root: int = 0):
         """The root's side of the RCCL weight broadcast (ym_broadcast_weights): every rank of `comm` calls it or
         constructs its Engine with receive=(comm, root)."""
-        self.rt.broadcast_weights(comm, root, torch.cuda.current_stream(self.device).cuda_stream)
+        self.rt.broadcast_weights(comm, root, self._stream())
+
+    def _stream(self) -> int:
+        """The current HIP stream's handle: every launch of a call goes to the stream current when it is made."""
+        return torch.cuda.current_stream(self.device).cuda_stream
 
     def _table_name(self, B, H, W):
         return f"{self.scale}-{self.task}-{self.dtype}-b{B}-{H}x{W}.json"
@@ -140,6 +144,48 @@ class Engine:
         self.tune_source[(B, H, W)] = src or "heuristic"
         self._tuned.add((B, H, W))
 
+    def _ready(self, x, B, H, W, args, stream, dets=None, counts=None):
+        """This (B, H, W) has its conv tile table: its first call takes or measures one (_prepare_shape).  x: a batch of
+        at least B images (its address is all that is used); dets, counts: the rows and counts a measuring run may
+        write (default: outputs(B, args.max_det))."""
+        if (B, H, W) not in self._tuned:
+            if dets is None:
+                dets, counts = self.outputs(B, args.max_det)
+            self._prepare_shape(x, B, H, W, args, dets, counts, stream)
+
+    def _check_input(self, x, in_eps, lanes, batch_max):
+        """x is a (B, 3, H, W) fp32 contiguous batch on the device; returns (in_eps, lanes, batch_max pointer) with
+        the defaults filled in: fp32's eps, the engine's lanes, 0 for no global max."""
+        assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4 and x.shape[1] == 3
+        if in_eps is None:
+            in_eps = torch.finfo(torch.float32).eps
+        bm = 0
+        if batch_max is not None:
+            assert batch_max.is_cuda and batch_max.dtype == torch.float32 and batch_max.numel() >= 1
+            bm = batch_max.data_ptr()
+        return in_eps, self.lanes if lanes is None else lanes, bm
+
+    def _cache_args(self, key, args):
+        """The ctypes argument block(s) of a repeated call are reused (predict loops pass the same thresholds): callers
+        look `_args_cache` up by key and build the block(s) only on a miss; this is the insert, with its eviction."""
+        if len(self._args_cache) > 64:
+            self._args_cache.clear()
+        self._args_cache[key] = args
+        return args
+
+    def _target(self, B, max_det, dets_out, counts_after):
+        """The (rows, counts) a call's NMS writes: the engine's own, or the caller's dets_out once checked."""
+        dets, counts = self.outputs(B, max_det)
+        if dets_out is not None:
+            assert (dets_out.is_cuda and dets_out.dtype == torch.float32 and dets_out.is_contiguous()
+                    and dets_out.dim() == 3 and dets_out.shape[0] >= B and tuple(dets_out.shape[1:]) == tuple(dets.shape[1:]))
+            dets = dets_out
+        if counts_after:  # room for the B count words behind the rows, in dets_out's own storage
+            need = dets_out.storage_offset() * 4 + B * max_det * (6 + self.nm) * 4 + 4 * B if dets_out is not None else -1
+            if dets_out is None or dets_out.untyped_storage().nbytes() < need:
+                raise ValueError("counts_after needs dets_out from Engine.rows_buffer (rows followed by B int32 words)")
+        return dets, counts
+
     def outputs(self, B: int, max_det: int):
         key = (B, max_det)
         if key not in self._out:
@@ -148,10 +194,10 @@ class Engine:
             self._out[key] = (dets, counts)
         return self._out[key]
 
-    def rows_buffer(self, B: int, max_det: int):
+    def rows_buffer(self, B: int, max_det: int, cols: Optional[int] = None):
         """A fresh flat fp32 device buffer for one call: (rows (B, max_det, 6 + nm) view, counts (B,) int32 view of the
-        words behind the rows) — for run(..., dets_out=rows, counts_after=True)."""
-        no = 6 + self.nm
+        words behind the rows) — for run(..., dets_out=rows, counts_after=True).  cols: another row width (track's)."""
+        no = 6 + self.nm if cols is None else cols
         flat = torch.empty((B * max_det * no + B,), dtype=torch.float32, device=self.device)
         return flat[: B * max_det * no].view(B, max_det, no), flat[B * max_det * no:].view(torch.int32)
 
@@ -174,38 +220,16 @@ class Engine:
         (predict() reads them lazily: no host sync per call).
         multi_label: validation mode — every (anchor, class) pair above conf is an NMS candidate (Ultralytics
         non_max_suppression(multi_label=True)); detect plans."""
-        assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4 and x.shape[1] == 3
+        in_eps, lanes, bm = self._check_input(x, in_eps, lanes, batch_max)
         B, _, H, W = x.shape
-        if in_eps is None:
-            in_eps = torch.finfo(torch.float32).eps
-        lanes = self.lanes if lanes is None else lanes
-        # the ctypes argument block of a repeated call is reused (predict loops pass the same thresholds)
-        bm = 0
-        if batch_max is not None:
-            assert batch_max.is_cuda and batch_max.dtype == torch.float32 and batch_max.numel() >= 1
-            bm = batch_max.data_ptr()
         akey = (conf, iou, max_det, max_nms, agnostic, max_wh, in_eps, tuple(classes) if classes is not None else None,
                 use_graph, lanes, bm, counts_after, multi_label)
-        args = self._args_cache.get(akey)
-        if args is None:
-            if len(self._args_cache) > 64:
-                self._args_cache.clear()
-            args = self._args_cache[akey] = Runtime.make_args(conf, iou, max_det, max_nms, agnostic, max_wh, in_eps,
-                                                              classes, use_graph, lanes, bm, counts_after,
-                                                              multi_label)
-        dets, counts = self.outputs(B, max_det)
-        if dets_out is not None:
-            assert (dets_out.is_cuda and dets_out.dtype == torch.float32 and dets_out.is_contiguous()
-                    and dets_out.dim() == 3 and dets_out.shape[0] >= B and tuple(dets_out.shape[1:]) == tuple(dets.shape[1:]))
-            dets = dets_out
-        if counts_after:  # room for the B count words behind the rows, in dets_out's own storage
-            need = dets_out.storage_offset() * 4 + B * max_det * (6 + self.nm) * 4 + 4 * B if dets_out is not None else -1
-            if dets_out is None or dets_out.untyped_storage().nbytes() < need:
-                raise ValueError("counts_after needs dets_out from Engine.rows_buffer (rows followed by B int32 words)")
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        Bl = self.lane_batch(B, lanes)
-        if (Bl, H, W) not in self._tuned:
-            self._prepare_shape(x[:Bl], Bl, H, W, args, dets, counts, stream)
+        args = self._args_cache.get(akey) or self._cache_args(akey, Runtime.make_args(
+            conf, iou, max_det, max_nms, agnostic, max_wh, in_eps, classes, use_graph, lanes, bm, counts_after,
+            multi_label))
+        dets, counts = self._target(B, max_det, dets_out, counts_after)
+        stream = self._stream()
+        self._ready(x, self.lane_batch(B, lanes), H, W, args, stream, dets, counts)
         self.rt.infer(x.data_ptr(), B, H, W, args, dets.data_ptr(), counts.data_ptr(), stream)
         return dets, counts
 
@@ -234,7 +258,7 @@ class Engine:
         if persist and live is not None and live[0] != B:
             raise ValueError(f"track(persist=True): the live tracker follows {live[0]} streams, this batch has {B} "
                              f"(image b of a batch is stream b); pass persist=False to start over")
-        stream = torch.cuda.current_stream(self.device).cuda_stream
+        stream = self._stream()
         trk = self._trackers.get(key)
         if trk is None:
             trk = self._trackers[key] = self.rt.track_create(B, full, capacity)
@@ -243,9 +267,7 @@ class Engine:
         self._live_tracker = key
         dets, cnt = self.rows_buffer(B, max_det)
         self.run(x, dets_out=dets, counts_after=True, **kw)
-        no = 7 + self.nm
-        flat = torch.empty((B * max_det * no + B,), dtype=torch.float32, device=self.device)
-        tracks, tcnt = flat[: B * max_det * no].view(B, max_det, no), flat[B * max_det * no:].view(torch.int32)
+        tracks, tcnt = self.rows_buffer(B, max_det, 7 + self.nm)
         idx = torch.empty((B, max_det), dtype=torch.int32, device=self.device)
         trk.update(dets.data_ptr(), 6 + self.nm, B, max_det, cnt.data_ptr(), tracks.data_ptr(), idx.data_ptr(),
                    tcnt.data_ptr(), stream)
@@ -284,20 +306,14 @@ class Engine:
         return value as run().  Everything is queued on the current stream; after the first call of a shape nothing
         is allocated and no graph is captured."""
         from .tta import pass_shapes
-        assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4 and x.shape[1] == 3
+        in_eps, lanes, bm = self._check_input(x, in_eps, lanes, batch_max)
         engines = self._tta_engines()
         B, _, H, W = x.shape
-        if in_eps is None:
-            in_eps = torch.finfo(torch.float32).eps
-        lanes = self.lanes if lanes is None else lanes
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        if batch_max is not None:
-            assert batch_max.is_cuda and batch_max.dtype == torch.float32 and batch_max.numel() >= 1
-            bm = batch_max
-        else:  # LoadTensor's statistic once: the scaled views and pass 0's forward read the same word
+        stream = self._stream()
+        if batch_max is None:  # LoadTensor's statistic once: the scaled views and pass 0's forward read the same word
             if self._tta_max is None:
                 self._tta_max = torch.empty((1,), dtype=torch.float32, device=self.device)
-            bm = self.input_max(x, out=self._tta_max)
+            bm = self.input_max(x, out=self._tta_max).data_ptr()
         shapes = pass_shapes(H, W)
         xs = [x]
         for p in (1, 2):
@@ -305,35 +321,22 @@ class Engine:
             xp = self._tta_in.get((p, B, H, W))
             if xp is None:
                 xp = self._tta_in[(p, B, H, W)] = torch.empty((B, 3, Hs, Ws), dtype=torch.float32, device=self.device)
-            self.rt.tta_scale(x.data_ptr(), B, H, W, p, bm.data_ptr(), in_eps, xp.data_ptr(), stream)
+            self.rt.tta_scale(x.data_ptr(), B, H, W, p, bm, in_eps, xp.data_ptr(), stream)
             xs.append(xp)
-        cl = tuple(classes) if classes is not None else None
-        akey = ("tta", conf, iou, max_det, max_nms, agnostic, max_wh, in_eps, cl, use_graph, lanes, bm.data_ptr(),
-                counts_after, multi_label)
+        akey = ("tta", conf, iou, max_det, max_nms, agnostic, max_wh, in_eps,
+                tuple(classes) if classes is not None else None, use_graph, lanes, bm, counts_after, multi_label)
         args = self._args_cache.get(akey)
         if args is None:
-            if len(self._args_cache) > 64:
-                self._args_cache.clear()
             mk = lambda bmp, ca, ml: Runtime.make_args(conf, iou, max_det, max_nms, agnostic, max_wh, in_eps, classes,
                                                        use_graph, lanes, bmp, ca, ml)
             # pass 0's forward (the caller's values, the given max), the scaled passes' (already normalised), the NMS
-            args = self._args_cache[akey] = (mk(bm.data_ptr(), False, False), mk(0, False, False),
-                                             mk(0, counts_after, multi_label))
-        dets, counts = self.outputs(B, max_det)
-        if dets_out is not None:
-            assert (dets_out.is_cuda and dets_out.dtype == torch.float32 and dets_out.is_contiguous()
-                    and dets_out.dim() == 3 and dets_out.shape[0] >= B and tuple(dets_out.shape[1:]) == tuple(dets.shape[1:]))
-            dets = dets_out
-        if counts_after:
-            need = dets_out.storage_offset() * 4 + B * max_det * 6 * 4 + 4 * B if dets_out is not None else -1
-            if dets_out is None or dets_out.untyped_storage().nbytes() < need:
-                raise ValueError("counts_after needs dets_out from Engine.rows_buffer (rows followed by B int32 words)")
+            args = self._cache_args(akey, (mk(bm, False, False), mk(0, False, False),
+                                           mk(0, counts_after, multi_label)))
+        dets, counts = self._target(B, max_det, dets_out, counts_after)
         for p, e in enumerate(engines):
             Hs, Ws = shapes[p][:2]
             Bl = e.lane_batch(B, lanes)
-            if (Bl, Hs, Ws) not in e._tuned:
-                d, c = e.outputs(Bl, max_det)
-                e._prepare_shape(xs[p][:Bl], Bl, Hs, Ws, args[min(p, 1)], d, c, stream)
+            e._ready(xs[p], Bl, Hs, Ws, args[min(p, 1)], stream)
             e.rt.tta_forward(xs[p].data_ptr(), B, Hs, Ws, args[min(p, 1)], stream)
         Runtime.tta_nms([e.rt for e in engines], B, H, W, args[2], dets.data_ptr(), counts.data_ptr(), stream)
         return dets, counts
@@ -347,7 +350,7 @@ class Engine:
         assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
         if out is None:
             out = torch.empty((1,), dtype=torch.float32, device=self.device)
-        self.rt.input_max(x.data_ptr(), x.numel(), out.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
+        self.rt.input_max(x.data_ptr(), x.numel(), out.data_ptr(), self._stream())
         return out
 
     def embed_layers(self):
@@ -378,7 +381,7 @@ class Engine:
         ValueError: an index outside 0..22, a non-integer, an empty list, a layer this plan does not store, or a
         quantized plan."""
         from .arch import DEFAULT_EMBED, normalize_embed
-        assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4 and x.shape[1] == 3
+        in_eps, _, bm = self._check_input(x, in_eps, 1, batch_max)
         layers = normalize_embed(DEFAULT_EMBED if layers is None else layers)
         views, width = self._embed_table(layers)
         B, _, H, W = x.shape
@@ -389,24 +392,16 @@ class Engine:
         else:
             assert (out.is_cuda and out.dtype == torch.float32 and out.dim() == 2 and out.shape[0] >= B
                     and out.shape[1] >= width and out.stride(1) == 1 and out.stride(0) >= width)
-        if in_eps is None:
-            in_eps = torch.finfo(torch.float32).eps
-        bm = 0
-        if batch_max is not None:
-            assert batch_max.is_cuda and batch_max.dtype == torch.float32 and batch_max.numel() >= 1
-            bm = batch_max.data_ptr()
         akey = ("embed", in_eps, use_graph, bm)
-        args = self._args_cache.get(akey)
-        if args is None:
-            args = self._args_cache[akey] = Runtime.make_args(in_eps=in_eps, use_graph=use_graph, lanes=1,
-                                                              batch_max_ptr=bm)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
+        args = self._args_cache.get(akey) or self._cache_args(akey, Runtime.make_args(
+            in_eps=in_eps, use_graph=use_graph, lanes=1, batch_max_ptr=bm))
+        stream = self._stream()
         if (B, H, W) not in self._tuned:  # the conv tile table of the shape, as run() takes it (one lane)
             if self._embed_scratch is None or self._embed_scratch[0].shape[0] < B:
                 self._embed_scratch = (torch.zeros((B, args.max_det, 6 + self.nm), dtype=torch.float32,
                                                    device=self.device),
                                        torch.zeros((B,), dtype=torch.int32, device=self.device))
-            self._prepare_shape(x, B, H, W, args, self._embed_scratch[0], self._embed_scratch[1], stream)
+            self._ready(x, B, H, W, args, stream, *self._embed_scratch)  # (outputs()'s buffers are not touched)
         self.rt.embed(x.data_ptr(), B, H, W, args, views, out.data_ptr(), out.stride(0), stream)
         return out[:B, :width]
 
@@ -452,7 +447,7 @@ class Engine:
         cap = max(4096, 64 * n) if cap is None else int(cap)
         points = torch.empty((cap, 2), dtype=torch.int32, device=self.device)
         offsets = torch.empty((n + 1,), dtype=torch.int64, device=self.device)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
+        stream = self._stream()
         self.rt.mask_contours(masks.data_ptr() if n else 0, n, H, W, masks.stride(0) if n > 1 else H * W,
                               points.data_ptr() if cap else 0, cap, offsets.data_ptr(), stream)
         self.contour_launches += 1
@@ -470,24 +465,21 @@ class Engine:
         pts = points[:total].cpu().numpy() if total else np.zeros((0, 2), dtype=np.int32)
         return [pts[offs[i]:offs[i + 1]] for i in range(len(offs) - 1)]
 
-    def profile(self, x: torch.Tensor, **kw):
+    def _profile_call(self, x, kw):
+        """profile's and profile_replay's common arguments: an eager argument block, the engine's outputs, a table."""
         B, _, H, W = x.shape
         args = Runtime.make_args(use_graph=False, **kw)
         dets, counts = self.outputs(B, args.max_det)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        if (B, H, W) not in self._tuned:
-            self._prepare_shape(x, B, H, W, args, dets, counts, stream)
-        return self.rt.profile(x.data_ptr(), B, H, W, args, dets.data_ptr(), counts.data_ptr(), stream)
+        stream = self._stream()
+        self._ready(x, B, H, W, args, stream, dets, counts)
+        return x.data_ptr(), B, H, W, args, dets.data_ptr(), counts.data_ptr(), stream
+
+    def profile(self, x: torch.Tensor, **kw):
+        return self.rt.profile(*self._profile_call(x, kw))
 
     def profile_replay(self, x: torch.Tensor, reps=20, **kw):
         """Per-op device ms from graph-captured back-to-back launches (-1 for input/decode/NMS); clobbers buffers."""
-        B, _, H, W = x.shape
-        args = Runtime.make_args(use_graph=False, **kw)
-        dets, counts = self.outputs(B, args.max_det)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        if (B, H, W) not in self._tuned:
-            self._prepare_shape(x, B, H, W, args, dets, counts, stream)
-        return self.rt.profile_replay(x.data_ptr(), B, H, W, args, dets.data_ptr(), counts.data_ptr(), stream, reps)
+        return self.rt.profile_replay(*self._profile_call(x, kw), reps)
 
     def masks(self, dets: torch.Tensor, counts: Sequence[int], H: int, W: int):
         """Segment plans: instance masks of the last run()'s detections (process_mask, upsample=True).  Returns the
@@ -501,7 +493,7 @@ class Engine:
         nonempty = torch.empty((total,), dtype=torch.int32, device=self.device)  # zeroed by ym_masks
         if total:
             off_t = torch.tensor(offs, dtype=torch.int32).to(self.device, non_blocking=True)
-            stream = torch.cuda.current_stream(self.device).cuda_stream
+            stream = self._stream()
             self.rt.masks(dets.data_ptr(), B, dets.shape[1], off_t.data_ptr(), total, H, W, masks.data_ptr(),
                           nonempty.data_ptr(), stream)
         return masks, nonempty, offs
@@ -530,7 +522,7 @@ class Engine:
         host[B + 1: 3 * B + 1] = np.asarray([(int(h), int(w)) for h, w in shapes], dtype=np.int32).reshape(-1)
         host[n32:].view(np.int64)[:] = boffs[:B]
         par = torch.from_numpy(host).to(self.device, non_blocking=True)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
+        stream = self._stream()
         self.rt.masks_native(dets.data_ptr(), dets.stride(1), B, dets.shape[1], par.data_ptr(), total, H, W, shapes,
                              par[B + 1:].data_ptr(), par[n32:].data_ptr(), masks.data_ptr(), nonempty.data_ptr(),
                              stream)
@@ -543,7 +535,7 @@ class Engine:
         B = counts.shape[0]
         masks = torch.empty((B, cap, H, W), dtype=torch.uint8, device=self.device)
         flags = torch.empty((B * cap + B,), dtype=torch.int32, device=self.device)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
+        stream = self._stream()
         self.rt.masks_slots(dets.data_ptr(), B, dets.shape[1], counts.data_ptr(), cap, H, W, masks.data_ptr(),
                             flags.data_ptr(), stream)
         return masks, flags
@@ -574,9 +566,9 @@ class Engine:
     def candidates(self, B: int, H: int, W: int):
         """The last forward's NMS candidates of the first B images (tests): per image the int64 anchor indices, in
         no fixed order (the low 32 bits of a candidate key are ~anchor)."""
-        from .arch import STRIDES
+        from .arch import num_anchors
         from .lib import SCRATCH_COUNTS, SCRATCH_KEYS
-        A = sum((H // s) * (W // s) for s in STRIDES)
+        A = num_anchors(H, W)
         kstride = 1
         while kstride < A:
             kstride <<= 1
@@ -598,10 +590,9 @@ class Engine:
     def keypoint_rows(self, B: int, H: int, W: int) -> torch.Tensor:
         """Pose plans: the decoded keypoint buffer (B, A, nm) of the last forward as a CPU tensor (tests).  Only the
         candidates' rows (candidates()) were written by that forward."""
-        from .arch import STRIDES
+        from .arch import num_anchors
         from .lib import SCRATCH_KPTS
-        A = sum((H // s) * (W // s) for s in STRIDES)
-        out = torch.empty((B, A, self.nm), dtype=torch.float32)
+        out = torch.empty((B, num_anchors(H, W), self.nm), dtype=torch.float32)
         self.rt.read_scratch(SCRATCH_KPTS, out.data_ptr(), out.numel() * 4)
         return out
 
@@ -631,7 +622,7 @@ class Engine:
         raws = {i: torch.empty(sh, dtype=torch.float32, device=self.device)
                 for i, sh in self.raw_shapes(B, H, W).items()}
         ptrs = [raws[i].data_ptr() if i in raws else 0 for i in range(len(self.graph.ops))]
-        stream = torch.cuda.current_stream(self.device).cuda_stream
+        stream = self._stream()
         self.rt.calibrate(x.data_ptr(), B, H, W, args, dets.data_ptr(), counts.data_ptr(), ptrs, stream)
         torch.cuda.synchronize(self.device)
         return raws

@@ -5,7 +5,7 @@ from __future__ import annotations
 import math
 from typing import List, Tuple
 
-from .arch import STRIDES
+from .arch import num_anchors  # noqa: F401  (tta.num_anchors: the passes' anchor counts)
 
 RATIOS = (1.0, 0.83, 0.67)
 FLIPS = (False, True, False)  # True: the W axis is mirrored
@@ -23,10 +23,6 @@ def pass_shapes(H: int, W: int) -> List[Tuple[int, int, int, int]]:
         else:
             out.append((math.ceil(H * s / GRID) * GRID, math.ceil(W * s / GRID) * GRID, int(H * s), int(W * s)))
     return out
-
-
-def num_anchors(H: int, W: int) -> int:
-    return sum((H // s) * (W // s) for s in STRIDES)
 
 
 def kept_anchors(H: int, W: int) -> List[Tuple[int, int]]:

@@ -413,6 +413,39 @@ int ym_num_conv_cfgs(int dtype);
  * pinned, was not launched, or the plan is int8 / fp8 (not tracked).  For a fused pair whose id is a two-launch one
  * out[2i] and out[2i + 1] are those values of its first and second conv; out[2i + 1] is -1 otherwise. */
 int ym_get_op_cfg_taken(ym_ctx* ctx, int B, int H, int W, int* out, int n);
+/* Tests: which kernel instantiation the depthwise, SPPF and attention ops of that same last forward launched (set on
+ * the host next to the launch actually issued; ym_get_op_cfg_taken and its values are untouched by it).  out:
+ * ym_num_ops ints, -1 for every other op kind, an op not launched, and every op of an int8 / fp8 plan.  The storage
+ * type (f16 / f32 / x3 pairs) is the plan's and not part of the code.
+ *   YM_OP_DWCONV   0 dwconv3x3 (one pixel per thread), 1 dwconv3x3_row PXT 2, 2 dwconv3x3_row PXT 4 (f16 only),
+ *                  3 dwconv3x3_strip PXT 2 RT 2, 4 dwconv3x3_strip PXT 4 RT 4,
+ *                  5..8 dwconv3x3_lds tile 0..3 (8x16x4, 4x32x4, 8x32x2, 16x16x2: YM_DBG_DW_TILE)
+ *   YM_OP_SPPF     0 sppf_pool separable (row then column maxima in LDS), 1 sppf_pool direct 2-D windows
+ *   YM_OP_ATTN     0..3 attn_psa QB 4 / 8 / 16 / 32, 4..7 attn_psa_mfma NKT 8 / 16 / 26 / 32,
+ *                  8..11 attn_psa_x3 NKT 8 / 16 / 26 / 32 (either KB: YM_DBG_ATTN_KB does not change the code),
+ *                  12 attn_psa_flash<false> (f16), 13 attn_psa_flash<true> (x3)
+ * ym_op_variant_count(kind): the number of distinct codes of an op kind (9, 2, 14), YM_EINVAL for another kind. */
+#define YM_OP_DWCONV 1
+#define YM_OP_SPPF 2
+#define YM_OP_ATTN 3
+#define YM_DWV_PIXEL 0
+#define YM_DWV_ROW2 1
+#define YM_DWV_ROW4 2
+#define YM_DWV_STRIP2 3
+#define YM_DWV_STRIP4 4
+#define YM_DWV_LDS0 5
+#define YM_DWV_COUNT 9
+#define YM_SPPFV_SEP 0
+#define YM_SPPFV_DIRECT 1
+#define YM_SPPFV_COUNT 2
+#define YM_ATTNV_SCALAR_QB4 0
+#define YM_ATTNV_MFMA_NKT8 4
+#define YM_ATTNV_X3_NKT8 8
+#define YM_ATTNV_FLASH_F16 12
+#define YM_ATTNV_FLASH_X3 13
+#define YM_ATTNV_COUNT 14
+int ym_get_op_variant(ym_ctx* ctx, int B, int H, int W, int* out, int n);
+int ym_op_variant_count(int kind);
 
 /* Process-wide debug switches for tests and A/B runs (not part of the reference interface; defaults 0), read when a
  * kernel is launched (so at graph capture for replayed forwards): YM_DBG_NMS (9 = the NMS kernel's per-box path

@@ -48,6 +48,16 @@ def test_dwconv_variants_match_float64(scale, B, dtype, mode):
         eng.run(x, use_graph=False)
     finally:
         L.set_debug(L.DBG_DW_MODE, prev)
+    # the instantiation each depthwise op launched (ym_get_op_variant), on the 80x80 maps: at B = 8 mode 2 is a column
+    # strip where the grid keeps 256 workgroups (yolo11s: 128 channels; yolo11n's 64 / 80 leave 200 / 250 and take the
+    # rows) and mode 1 in f16 is four pixels per thread; tests/test_gpu_misc_ops.py runs small maps, where neither can
+    ran = {op.name: L.DW_VARIANTS[v] for op, v in zip(eng.graph.ops, eng.rt.get_op_variant(B, 640, 640))
+           if op.kind == "dwconv" and op.args["src"].buf.f == 8}
+    assert len(ran) == 2, ran
+    if B == 8 and mode == "2" and scale == "s":
+        assert set(ran.values()) <= {"strip2", "strip4"}, ran
+    if B == 8 and mode == "1" and dtype == "f16":
+        assert set(ran.values()) == {"row4"}, ran
     n = 0
     for op in eng.graph.ops:
         if op.kind != "dwconv":

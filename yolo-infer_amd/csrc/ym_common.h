@@ -557,9 +557,11 @@ struct MaskNativeArgs {                 // ym_mask_native.hip: process_mask_nati
 // back (the heuristic tile, the first variant that takes the shape), -1 when cfg < 0 or the plan is int8 / fp8
 hipError_t ym_launch_conv(int dtype, int out_f32, const ConvArgs& a, int cfg, hipStream_t st, bool strict = false,
                           int* taken = nullptr);
-hipError_t ym_launch_dwconv(int dtype, const DwArgs& a, hipStream_t st);
-hipError_t ym_launch_sppf(int dtype, const PoolArgs& a, hipStream_t st);
-hipError_t ym_launch_attn(int dtype, const AttnArgs& a, hipStream_t st);
+// variant (tests; may be null): the YM_DWV_* / YM_SPPFV_* / YM_ATTNV_* code (include/yolomi.h) of the instantiation that
+// is launched, set on the host beside that launch; left as it is by the int8 / fp8 launchers and on an error
+hipError_t ym_launch_dwconv(int dtype, const DwArgs& a, hipStream_t st, int* variant = nullptr);
+hipError_t ym_launch_sppf(int dtype, const PoolArgs& a, hipStream_t st, int* variant = nullptr);
+hipError_t ym_launch_attn(int dtype, const AttnArgs& a, hipStream_t st, int* variant = nullptr);
 hipError_t ym_launch_prep(int dtype, const PrepArgs& a, int* counts, int B, hipStream_t st);
 hipError_t ym_launch_input_max(const float* x, long n, float* ctl, float* out, hipStream_t st);
 hipError_t ym_launch_decode(const DecodeArgs& a, hipStream_t st);

@@ -1717,7 +1717,8 @@ void ym_debug_add(int key, int d) {
   if (key > 0 && key < kDbgKeys) dbg_slots()[key].fetch_add(d);
 }
 
-hipError_t ym_launch_dwconv(int dtype, const DwArgs& a, hipStream_t st) {
+hipError_t ym_launch_dwconv(int dtype, const DwArgs& a, hipStream_t st, int* variant) {
+  auto ran = [&](int code) { if (variant) *variant = code; };
   if (ym_dt_q8(dtype)) return ym_launch_dwconv_i8(a, st, dtype == YM_DT_F8);
   const long total = (long)a.B * a.H * a.W * (a.C / 8);
   if (total >= 0x7FFFFFFFL - 256) return hipErrorInvalidValue;  // the kernel indexes in 32 bits
@@ -1731,19 +1732,20 @@ hipError_t ym_launch_dwconv(int dtype, const DwArgs& a, hipStream_t st) {
   if (mode == 0 && !a.raw) {
     // LDS tile shape (TH x TW pixels x CG chunks; YM_DBG_DW_TILE 0..3 for A/B, read at every launch): 0 = 8 x 16 x 4
     const int ti = ym_debug_get(YM_DBG_DW_TILE);
-    auto go = [&](auto th, auto tw, auto cg) -> hipError_t {
+    auto go = [&](auto th, auto tw, auto cg, int code) -> hipError_t {
       constexpr int TH = decltype(th)::value, TW = decltype(tw)::value, CG = decltype(cg)::value;
       const long tiles = (long)a.B * ((a.H + TH - 1) / TH) * ((a.W + TW - 1) / TW) * ((a.C / 8 + CG - 1) / CG);
       if (tiles >= 0x7FFFFFFFL) return hipErrorInvalidValue;
       if (dtype == YM_DT_F16) hipLaunchKernelGGL((dwconv3x3_lds<f16, TH, TW, CG>), dim3(tiles), dim3(256), 0, st, a);
       else if (dtype == YM_DT_X3) hipLaunchKernelGGL((dwconv3x3_lds<P2, TH, TW, CG>), dim3(tiles), dim3(256), 0, st, a);
       else hipLaunchKernelGGL((dwconv3x3_lds<float, TH, TW, CG>), dim3(tiles), dim3(256), 0, st, a);
+      ran(code);
       return hipGetLastError();
     };
-    if (ti == 1) return go(std::integral_constant<int, 4>(), std::integral_constant<int, 32>(), std::integral_constant<int, 4>());
-    if (ti == 2) return go(std::integral_constant<int, 8>(), std::integral_constant<int, 32>(), std::integral_constant<int, 2>());
-    if (ti == 3) return go(std::integral_constant<int, 16>(), std::integral_constant<int, 16>(), std::integral_constant<int, 2>());
-    return go(std::integral_constant<int, 8>(), std::integral_constant<int, 16>(), std::integral_constant<int, 4>());
+    if (ti == 1) return go(std::integral_constant<int, 4>(), std::integral_constant<int, 32>(), std::integral_constant<int, 4>(), YM_DWV_LDS0 + 1);
+    if (ti == 2) return go(std::integral_constant<int, 8>(), std::integral_constant<int, 32>(), std::integral_constant<int, 2>(), YM_DWV_LDS0 + 2);
+    if (ti == 3) return go(std::integral_constant<int, 16>(), std::integral_constant<int, 16>(), std::integral_constant<int, 2>(), YM_DWV_LDS0 + 3);
+    return go(std::integral_constant<int, 8>(), std::integral_constant<int, 16>(), std::integral_constant<int, 4>(), YM_DWV_LDS0);
   }
   // column strips (dwconv3x3_strip): rows per thread where the grid keeps >= 256 workgroups (YM_DW_RT forces 2 / 4)
   static const int env_rt = [] { const char* e = getenv("YM_DW_RT"); return e ? atoi(e) : 0; }();
@@ -1758,6 +1760,7 @@ hipError_t ym_launch_dwconv(int dtype, const DwArgs& a, hipStream_t st) {
       if (is16) hipLaunchKernelGGL((dwconv3x3_strip<f16, 4, 4>), gs, dim3(256), 0, st, a);
       else if (x3) hipLaunchKernelGGL((dwconv3x3_strip<P2, 4, 4>), gs, dim3(256), 0, st, a);
       else hipLaunchKernelGGL((dwconv3x3_strip<float, 4, 4>), gs, dim3(256), 0, st, a);
+      ran(YM_DWV_STRIP4);
       return hipGetLastError();
     }
     if (px && rt == 2) {
@@ -1765,25 +1768,29 @@ hipError_t ym_launch_dwconv(int dtype, const DwArgs& a, hipStream_t st) {
       if (is16) hipLaunchKernelGGL((dwconv3x3_strip<f16, 2, 2>), gs, dim3(256), 0, st, a);
       else if (x3) hipLaunchKernelGGL((dwconv3x3_strip<P2, 2, 2>), gs, dim3(256), 0, st, a);
       else hipLaunchKernelGGL((dwconv3x3_strip<float, 2, 2>), gs, dim3(256), 0, st, a);
+      ran(YM_DWV_STRIP2);
       return hipGetLastError();
     }
   }
   const int pxt = env_pxt ? env_pxt : (total / 4 >= 128 * 256 ? 4 : 2);
-  if (dtype == YM_DT_F16 && pxt == 4 && a.W % 4 == 0)
+  if (dtype == YM_DT_F16 && pxt == 4 && a.W % 4 == 0) {
     hipLaunchKernelGGL((dwconv3x3_row<f16, 4>), dim3((total / 4 + 255) / 256), dim3(256), 0, st, a);
-  else if (pxt >= 2 && a.W % 2 == 0 && dtype == YM_DT_F16)
-    hipLaunchKernelGGL((dwconv3x3_row<f16, 2>), dim3((total / 2 + 255) / 256), dim3(256), 0, st, a);
-  else if (pxt >= 2 && a.W % 2 == 0 && dtype == YM_DT_X3)
-    hipLaunchKernelGGL((dwconv3x3_row<P2, 2>), dim3((total / 2 + 255) / 256), dim3(256), 0, st, a);
-  else if (pxt >= 2 && a.W % 2 == 0)
-    hipLaunchKernelGGL((dwconv3x3_row<float, 2>), dim3((total / 2 + 255) / 256), dim3(256), 0, st, a);
-  else if (dtype == YM_DT_F16) hipLaunchKernelGGL(dwconv3x3<f16>, g, dim3(256), 0, st, a);
-  else if (dtype == YM_DT_X3) hipLaunchKernelGGL(dwconv3x3<P2>, g, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(dwconv3x3<float>, g, dim3(256), 0, st, a);
+    ran(YM_DWV_ROW4);
+  } else if (pxt >= 2 && a.W % 2 == 0) {
+    if (dtype == YM_DT_F16) hipLaunchKernelGGL((dwconv3x3_row<f16, 2>), dim3((total / 2 + 255) / 256), dim3(256), 0, st, a);
+    else if (dtype == YM_DT_X3) hipLaunchKernelGGL((dwconv3x3_row<P2, 2>), dim3((total / 2 + 255) / 256), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((dwconv3x3_row<float, 2>), dim3((total / 2 + 255) / 256), dim3(256), 0, st, a);
+    ran(YM_DWV_ROW2);
+  } else {
+    if (dtype == YM_DT_F16) hipLaunchKernelGGL(dwconv3x3<f16>, g, dim3(256), 0, st, a);
+    else if (dtype == YM_DT_X3) hipLaunchKernelGGL(dwconv3x3<P2>, g, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(dwconv3x3<float>, g, dim3(256), 0, st, a);
+    ran(YM_DWV_PIXEL);
+  }
   return hipGetLastError();
 }
 
-hipError_t ym_launch_sppf(int dtype, const PoolArgs& a, hipStream_t st) {
+hipError_t ym_launch_sppf(int dtype, const PoolArgs& a, hipStream_t st, int* variant) {
   const size_t HW = (size_t)a.H * a.W;
   const size_t img = HW * 8 * (dtype == YM_DT_F16 ? 2 : (ym_dt_q8(dtype) ? 1 : 4));
   PoolArgs b = a;
@@ -1796,23 +1803,29 @@ hipError_t ym_launch_sppf(int dtype, const PoolArgs& a, hipStream_t st) {
   else if (dtype == YM_DT_F8) hipLaunchKernelGGL((sppf_pool<i8, true>), g, dim3(256), lds, st, b);
   else if (dtype == YM_DT_X3) hipLaunchKernelGGL(sppf_pool<P2>, g, dim3(256), lds, st, b);  // max of hi + lo values
   else hipLaunchKernelGGL(sppf_pool<float>, g, dim3(256), lds, st, b);
+  if (variant && !ym_dt_q8(dtype)) *variant = b.sep ? YM_SPPFV_SEP : YM_SPPFV_DIRECT;
   return hipGetLastError();
 }
 
 template <typename T>
-hipError_t launch_attn_t(const AttnArgs& a, hipStream_t st) {
+hipError_t launch_attn_t(const AttnArgs& a, hipStream_t st, int* variant) {
+  auto ran = [&](int qbi) { if (variant) *variant = YM_ATTNV_SCALAR_QB4 + qbi; };
   const size_t budget = 150 * 1024;
   auto lds = [&](int qb) { return ((size_t)qb * a.N + (size_t)qb * AKD + 64 * AHD) * sizeof(float); };
   // fewer queries per workgroup = more workgroups: with one wave per SIMD nothing hides this kernel's latencies
   auto wgs = [&](int qb) { return (long)a.B * a.nh * ((a.N + qb - 1) / qb); };
   if (lds(32) <= budget && wgs(32) >= 512) {
     hipLaunchKernelGGL((attn_psa<T, 32>), dim3(a.B * a.nh * ((a.N + 31) / 32)), dim3(256), lds(32), st, a);
+    ran(3);
   } else if (lds(16) <= budget && (wgs(16) >= 512 || lds(8) > budget)) {
     hipLaunchKernelGGL((attn_psa<T, 16>), dim3(a.B * a.nh * ((a.N + 15) / 16)), dim3(256), lds(16), st, a);
+    ran(2);
   } else if (lds(8) <= budget) {
     hipLaunchKernelGGL((attn_psa<T, 8>), dim3(a.B * a.nh * ((a.N + 7) / 8)), dim3(256), lds(8), st, a);
+    ran(1);
   } else if (lds(4) <= budget) {
     hipLaunchKernelGGL((attn_psa<T, 4>), dim3(a.B * a.nh * ((a.N + 3) / 4)), dim3(256), lds(4), st, a);
+    ran(0);
   } else {
     return hipErrorInvalidValue;  // N > ~9,600 tokens (input > 3136 px): not supported
   }
@@ -1846,31 +1859,32 @@ hipError_t launch_attn_x3(const AttnArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
-hipError_t ym_launch_attn(int dtype, const AttnArgs& a, hipStream_t st) {
+hipError_t ym_launch_attn(int dtype, const AttnArgs& a, hipStream_t st, int* variant) {
+  auto ran = [&](int code) { if (variant) *variant = code; };
   if (ym_dt_q8(dtype)) return ym_launch_attn_i8(a, st, dtype == YM_DT_F8);
   if (dtype == YM_DT_X3 && a.kd == 32 && a.hd == 64 && !a.raw && a.nh * 128 <= a.q_ctot && a.d_ctot % 4 == 0 &&
       a.d_coff % 4 == 0 && a.q_ctot % 8 == 0 && a.q_coff % 8 == 0) {
     const int nkt = (a.N + 15) / 16;
-    if (nkt <= 8) return launch_attn_x3<8>(a, st);
-    if (nkt <= 16) return launch_attn_x3<16>(a, st);
-    if (nkt <= 26) return launch_attn_x3<26>(a, st);
-    if (nkt <= 32) return launch_attn_x3<32>(a, st);
+    if (nkt <= 8) { ran(YM_ATTNV_X3_NKT8 + 0); return launch_attn_x3<8>(a, st); }
+    if (nkt <= 16) { ran(YM_ATTNV_X3_NKT8 + 1); return launch_attn_x3<16>(a, st); }
+    if (nkt <= 26) { ran(YM_ATTNV_X3_NKT8 + 2); return launch_attn_x3<26>(a, st); }
+    if (nkt <= 32) { ran(YM_ATTNV_X3_NKT8 + 3); return launch_attn_x3<32>(a, st); }
     const hipError_t e = launch_attn_flash<true>(a, st);
-    if (e != hipErrorInvalidValue) return e;
+    if (e != hipErrorInvalidValue) { ran(YM_ATTNV_FLASH_X3); return e; }
   }
   if (dtype == YM_DT_F16 && a.kd == 32 && a.hd == 64 && !a.raw && a.nh * 128 <= a.q_ctot && a.d_ctot % 4 == 0 &&
       a.d_coff % 4 == 0 && a.q_ctot % 8 == 0 && a.q_coff % 8 == 0) {
     const int nkt = (a.N + 15) / 16;
-    if (nkt <= 8) return launch_attn_mfma<8>(a, st);
-    if (nkt <= 16) return launch_attn_mfma<16>(a, st);
-    if (nkt <= 26) return launch_attn_mfma<26>(a, st);
-    if (nkt <= 32) return launch_attn_mfma<32>(a, st);
+    if (nkt <= 8) { ran(YM_ATTNV_MFMA_NKT8 + 0); return launch_attn_mfma<8>(a, st); }
+    if (nkt <= 16) { ran(YM_ATTNV_MFMA_NKT8 + 1); return launch_attn_mfma<16>(a, st); }
+    if (nkt <= 26) { ran(YM_ATTNV_MFMA_NKT8 + 2); return launch_attn_mfma<26>(a, st); }
+    if (nkt <= 32) { ran(YM_ATTNV_MFMA_NKT8 + 3); return launch_attn_mfma<32>(a, st); }
     const hipError_t e = launch_attn_flash<false>(a, st);  // N > 512 tokens (inputs above 724 px)
-    if (e != hipErrorInvalidValue) return e;  // (YM_ATTN_FLASH_OFF=1: the scalar kernel, tests)
+    if (e != hipErrorInvalidValue) { ran(YM_ATTNV_FLASH_F16); return e; }  // (YM_ATTN_FLASH_OFF=1: the scalar kernel, tests)
   }
   if (a.kd > AKD || a.hd > AHD) return hipErrorInvalidValue;
-  if (dtype == YM_DT_X3) return launch_attn_t<P2>(a, st);
-  return dtype == YM_DT_F16 ? launch_attn_t<f16>(a, st) : launch_attn_t<float>(a, st);
+  if (dtype == YM_DT_X3) return launch_attn_t<P2>(a, st, variant);
+  return dtype == YM_DT_F16 ? launch_attn_t<f16>(a, st, variant) : launch_attn_t<float>(a, st, variant);
 }
 
 hipError_t ym_launch_decode(const DecodeArgs& a, hipStream_t st) {

@@ -315,6 +315,9 @@ struct ym_ctx {
   // tests (ym_get_op_cfg_taken): per op of the last forward launched, whether its pinned cfg was the kernel that ran
   // ([2i]: the op, or the first conv of a split pair; [2i + 1]: the pair's second conv; ym_launch_conv's `taken`)
   std::vector<int> taken;
+  // tests (ym_get_op_variant): per op of that forward, the kernel instantiation a depthwise / SPPF / attention op
+  // launched (the launchers' `variant`; -1: another kind, not launched, int8 / fp8)
+  std::vector<int> variant;
   int tkB = 0, tkH = 0, tkW = 0;
   int op_cfg(long i, int B) const {  // for the current workspace height/width
     const std::vector<int>* v = find_cfg(B, cH, cW);
@@ -357,6 +360,7 @@ struct ym_ctx {
   template <typename T> const T* wptr(int32_t off) const {  // a record's *_off slot: unsigned bytes into the weights
     return reinterpret_cast<const T*>(d_weights + (size_t)(uint32_t)off);
   }
+  int* variant_of(const Op& op) { return variant.size() == ops.size() ? &variant[&op - ops.data()] : nullptr; }
   float* raw_of(const Launch& L, const Op& op) const { return L.calib_raw ? L.calib_raw[&op - ops.data()] : nullptr; }
   // buffer b from image img0 on: that slice of the whole-batch buffer (all buffers are image-major)
   void* bptr(int b, int img0) const { return d_arena + buf_off[b] + (size_t)img0 * buf_P(b) * bufs[b].C * elem(b); }
@@ -683,7 +687,7 @@ int launch_op(ym_ctx* c, const Launch& L, const Op& op, int B, const float* d_in
         a.sasw = c->wptr<float>(op.sasw_off);
       }
       a.raw = c->raw_of(L, op);
-      e = ym_launch_dwconv(dt, a, st);
+      e = ym_launch_dwconv(dt, a, st, c->variant_of(op));
       break;
     }
     case OP_SPPF: {
@@ -691,7 +695,7 @@ int launch_op(ym_ctx* c, const Launch& L, const Op& op, int B, const float* d_in
       const int bb = op.sppf_buf();
       a.buf = c->bptr(bb, L.img0); a.ctot = c->bufs[bb].C; a.coff = op.sppf_coff(); a.P = c->buf_P(bb);
       a.C = op.cin; a.H = c->buf_H(bb); a.W = c->buf_Wd(bb); a.B = B;
-      e = ym_launch_sppf(dt, a, st);
+      e = ym_launch_sppf(dt, a, st, c->variant_of(op));
       break;
     }
     case OP_ATTN: {
@@ -711,7 +715,7 @@ int launch_op(ym_ctx* c, const Launch& L, const Op& op, int B, const float* d_in
         a.pe_sasw = c->wptr<float>(op.sasw_off);
       }
       a.raw = c->raw_of(L, op);
-      e = ym_launch_attn(dt, a, st);
+      e = ym_launch_attn(dt, a, st, c->variant_of(op));
       break;
     }
     case OP_REQ: {
@@ -1282,6 +1286,7 @@ static int infer_impl(ym_ctx* c, const float* d_in, int B, int H, int W, const y
     L.pool = false;
   }
   c->taken.assign(2 * c->ops.size(), -1);
+  c->variant.assign(c->ops.size(), -1);
   c->tkB = B; c->tkH = H; c->tkW = W;
   if (!args->use_graph) {
     if ((rc = launch_forward(c, L, d_in, args, d_dets, d_counts, st))) return rc;
@@ -1726,6 +1731,23 @@ int ym_get_op_cfg_taken(ym_ctx* c, int B, int H, int W, int* out, int n) {
     return fail(YM_ESTATE, "ym_get_op_cfg_taken: the last forward was not a %d x %d x %d one", B, H, W);
   for (size_t i = 0; i < c->taken.size(); ++i) out[i] = c->taken[i];
   return YM_OK;
+}
+
+int ym_get_op_variant(ym_ctx* c, int B, int H, int W, int* out, int n) {
+  if (!c || !out || n < (int)c->ops.size()) return fail(YM_EINVAL, "variant array must hold %zu entries", c ? c->ops.size() : 0);
+  if (c->variant.size() != c->ops.size() || B != c->tkB || H != c->tkH || W != c->tkW)
+    return fail(YM_ESTATE, "ym_get_op_variant: the last forward was not a %d x %d x %d one", B, H, W);
+  for (size_t i = 0; i < c->variant.size(); ++i) out[i] = c->variant[i];
+  return YM_OK;
+}
+
+int ym_op_variant_count(int kind) {
+  switch (kind) {
+    case YM_OP_DWCONV: return YM_DWV_COUNT;
+    case YM_OP_SPPF: return YM_SPPFV_COUNT;
+    case YM_OP_ATTN: return YM_ATTNV_COUNT;
+    default: return fail(YM_EINVAL, "ym_op_variant_count: kind %d", kind);
+  }
 }
 
 int ym_num_ops(ym_ctx* c) { return c ? (int)c->ops.size() : fail(YM_EINVAL, "null context"); }

@@ -94,6 +94,8 @@ def load_library(path: os.PathLike = LIB_PATH):
         "ym_get_op_cfg": (I, [P, I, I, I, C.POINTER(I), I]),
         "ym_set_op_cfg": (I, [P, I, I, I, C.POINTER(I), I]),
         "ym_get_op_cfg_taken": (I, [P, I, I, I, C.POINTER(I), I]),
+        "ym_get_op_variant": (I, [P, I, I, I, C.POINTER(I), I]),
+        "ym_op_variant_count": (I, [I]),
         "ym_num_ops": (I, [P]),
         "ym_op_name": (C.c_char_p, [P, I]),
         "ym_num_buffers": (I, [P]),
@@ -137,7 +139,8 @@ def load_library(path: os.PathLike = LIB_PATH):
 
 EXPORTED = ("ym_create", "ym_load_weights", "ym_broadcast_weights", "ym_broadcast_weights_local", "ym_rccl_get_unique_id", "ym_rccl_comm_init",
             "ym_rccl_comm_destroy", "ym_infer", "ym_input_max", "ym_calibrate", "ym_masks", "ym_masks_slots", "ym_masks_native",
-            "ym_letterbox", "ym_profile", "ym_profile_replay", "ym_tune", "ym_get_op_cfg", "ym_set_op_cfg", "ym_get_op_cfg_taken", "ym_num_ops",
+            "ym_letterbox", "ym_profile", "ym_profile_replay", "ym_tune", "ym_get_op_cfg", "ym_set_op_cfg", "ym_get_op_cfg_taken", "ym_get_op_variant",
+            "ym_op_variant_count", "ym_num_ops",
             "ym_op_name",
             "ym_num_buffers", "ym_buffer_info", "ym_read_buffer", "ym_sync", "ym_last_error", "ym_destroy",
             "ym_version", "ym_num_conv_cfgs", "ym_set_debug", "ym_read_scratch", "ym_kpt_shape",
@@ -147,6 +150,12 @@ EXPORTED = ("ym_create", "ym_load_weights", "ym_broadcast_weights", "ym_broadcas
 
 DBG_NMS, DBG_DW_MODE, DBG_DW_TILE, DBG_CHAIN, DBG_CHAIN_LAUNCHES, DBG_STEMFUSE, DBG_ATTN_KB = 1, 2, 3, 4, 5, 6, 7
 DBG_PAIRST, DBG_CONV_CFG = 8, 9  # value + 1 (0: default)  # ym_set_debug keys (include/yolomi.h)
+# ym_get_op_variant codes (include/yolomi.h): op kinds, then per kind the code -> kernel instantiation
+OP_DWCONV, OP_SPPF, OP_ATTN = 1, 2, 3
+DW_VARIANTS = ("pixel", "row2", "row4", "strip2", "strip4", "lds0", "lds1", "lds2", "lds3")
+SPPF_VARIANTS = ("sep", "direct")
+ATTN_VARIANTS = ("scalar_qb4", "scalar_qb8", "scalar_qb16", "scalar_qb32", "mfma_nkt8", "mfma_nkt16", "mfma_nkt26",
+                 "mfma_nkt32", "x3_nkt8", "x3_nkt16", "x3_nkt26", "x3_nkt32", "flash_f16", "flash_x3")
 DBG_STOP = 10  # tests: 1 + the last op an eager forward launches (0: a whole forward); graph calls are refused
 
 
@@ -381,6 +390,14 @@ class Runtime:
         arr = (C.c_int * (2 * self.n_ops))()
         _check(self.lib.ym_get_op_cfg_taken(self.ctx, B, H, W, arr, 2 * self.n_ops))
         return [(arr[2 * i], arr[2 * i + 1]) for i in range(self.n_ops)]
+
+    def get_op_variant(self, B, H, W):
+        """Per op of the last (eager or captured) B x H x W forward, the kernel instantiation a depthwise / SPPF /
+        attention op launched (an index into DW_VARIANTS / SPPF_VARIANTS / ATTN_VARIANTS), -1 for every other op and
+        for int8 / fp8 plans (include/yolomi.h ym_get_op_variant)."""
+        arr = (C.c_int * self.n_ops)()
+        _check(self.lib.ym_get_op_variant(self.ctx, B, H, W, arr, self.n_ops))
+        return list(arr)
 
     def buffer_info(self, buf: int):
         p, c, h, w, e = C.c_void_p(), C.c_int(), C.c_int(), C.c_int(), C.c_int()

@@ -1,6 +1,6 @@
-"""Float64 references of the three compute ops of csrc/ym_misc.hip that are not convs — `attn` (C2PSA attention),
-`sppf` (the three max pools) and `dwconv` (depthwise 3x3) — each computed from the op's own stored input, with a
-per-element error bound: test infrastructure, CPU only (tests/test_misc_oracle_host.py checks it,
+"""Float64 references of the three compute ops that are not convs (csrc/ym_attn.hip, ym_sppf.hip, ym_dwconv.hip) —
+`attn` (C2PSA attention), `sppf` (the three max pools) and `dwconv` (depthwise 3x3) — each computed from the op's own
+stored input, with a per-element error bound: test infrastructure, CPU only (tests/test_misc_oracle_host.py checks it,
 tests/test_gpu_misc_ops.py uses it).  The style is tests/conv_oracle.py's: every constant below is derived here or
 measured against a CPU emulation of the plan's operand representation (tools/misc_op_bounds.py, figures in
 profiles/misc_op_bounds.txt), never against the kernels.

@@ -26,7 +26,7 @@ _models = {}
 @pytest.mark.parametrize("scale,B", [("s", 8), ("n", 8), ("s", 1)])
 @pytest.mark.parametrize("dtype", ["x3", "f16", "f32"])
 def test_dwconv_variants_match_float64(scale, B, dtype, mode):
-    """csrc/ym_misc.hip depthwise 3x3 (Detect cv3 DWConv) in each YM_DW_MODE: 0 the LDS-tile kernel
+    """csrc/ym_dwconv.hip depthwise 3x3 (Detect cv3 DWConv) in each YM_DW_MODE: 0 the LDS-tile kernel
     (default; partial tiles at 20² / 40²), 1 the row variant and one-pixel kernel, 2 the column strips (rows per
     thread 2 or 4 by grid size), on every dwconv of the Detect head at 640² (80², 40², 20² maps), eager forwards:
     output = SiLU(bias + Σ_taps w·x) of the stored input."""
@@ -327,7 +327,7 @@ def test_stem_fuse_matches_the_split_launches():
 
 
 def test_attention_k_batching_is_bitwise_neutral():
-    """YM_DBG_ATTN_KB (csrc/ym_misc.hip attn_psa_x3<NKT, KB>): the x3 C2PSA attention loads the K fragments of every
+    """YM_DBG_ATTN_KB (csrc/ym_attn.hip attn_psa_x3<NKT, KB>): the x3 C2PSA attention loads the K fragments of every
     key tile at once by default, 8 tiles per round trip with the switch at 1.  Only the load schedule differs, so
     every tensor of the forward and the detections are bitwise equal."""
     from core.model import YOLO11Model

@@ -1,8 +1,8 @@
-"""The attention, SPPF and depthwise kernels of csrc/ym_misc.hip op by op against float64 computed from the op's own
-stored input (tests/misc_oracle.py: the references, the per-element bound E, the mutations and where every number comes
-from) — and known to have run: after each forward the runtime says which instantiation each of these ops launched
-(ym_get_op_variant), the test restates the launch rule and demands that code, and over the whole set every code of
-ym_op_variant_count ran or stands on a reasoned never-run list.
+"""The attention, SPPF and depthwise kernels (csrc/ym_attn.hip, ym_sppf.hip, ym_dwconv.hip) op by op against float64
+computed from the op's own stored input (tests/misc_oracle.py: the references, the per-element bound E, the mutations
+and where every number comes from) — and known to have run: after each forward the runtime says which instantiation
+each of these ops launched (ym_get_op_variant), the test restates the launch rule and demands that code, and over the
+whole set every code of ym_op_variant_count ran or stands on a reasoned never-run list.
 
 Eager forwards, one lane, no autotune; inputs make_input("uniform", ...) cropped to H x W (misc_oracle.SHAPES).
 Shapes and what each reaches (N = (H / 32) (W / 32) tokens; yolo11n, 2 heads, unless stated):
@@ -52,7 +52,7 @@ ATTN_PLANS = ("f16", "x3", "f32")
 DW_PLANS = ("f16", "f32", "x3nodw")
 
 # (scale, shape, B, weights, plans, {plan: attention instantiation}) — the (plan, N, B * nh) -> code table, restated from
-# csrc/ym_misc.hip ym_launch_attn: f16 / x3 with kd 32, hd 64 take the MFMA kernels by ceil(N / 16) <= 8, 16, 26, 32,
+# csrc/ym_op_select.h ym_select_attn: f16 / x3 with kd 32, hd 64 take the MFMA kernels by ceil(N / 16) <= 8, 16, 26, 32,
 # above that flash; f32 takes attn_psa<QB>: 32 when B nh ceil(N / 32) >= 512, else 16 when B nh ceil(N / 16) >= 512, else
 # 8 (the LDS budget of 150 KiB holds QB 32 up to N = 1136 and QB 8 up to N = 4256)
 _MF = lambda n: {"f16": f"mfma_nkt{n}", "x3": f"x3_nkt{n}", "f32": "scalar_qb8"}
@@ -374,7 +374,7 @@ def test_second_forward_leaves_attention_and_pools_bit_equal(plan, shape, B):
 
 # ---------------------------------------------------------------------------------------------- depthwise
 def dw_expect(mode, tile, B, H, W, C, f16):
-    """csrc/ym_misc.hip ym_launch_dwconv restated: mode 0 the LDS tile; mode 2 a strip where the grid keeps >= 256
+    """csrc/ym_op_select.h ym_select_dwconv restated: mode 0 the LDS tile; mode 2 a strip where the grid keeps >= 256
     workgroups; else (and mode 1) 4 pixels per thread for f16 where that leaves >= 128 workgroups and W % 4 == 0, 2 where
     W is even, the one-pixel kernel at odd widths."""
     if mode == 0:

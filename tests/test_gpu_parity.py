@@ -112,7 +112,7 @@ def test_predict_kwargs_f32(kw):
 @pytest.mark.parametrize("conf", [0.5, 0.3, 0.15, 0.06, 0.02, 0.004, 0.001])
 def test_nms_paths_f32(conf):
     """Candidate counts from a few dozen to thousands per image: the one-wave (<= 64), bit-matrix (<= 512) and
-    blocked (> 512; the validator's conf 0.001) NMS paths of csrc/ym_misc.hip nms_image all reproduce torchvision's
+    blocked (> 512; the validator's conf 0.001) NMS paths of csrc/ym_nms.hip nms_image all reproduce torchvision's
     greedy order."""
     x = make_input("uniform", (31, 32), 640)
     ref = oracle().predict(x, conf=conf)
@@ -790,7 +790,7 @@ def test_decode_staged_variant_bitwise_equals_register_variant(tmp_path):
 # ------------------------------------------------------------------------------------------------ 1280² (N = 1600)
 def test_f16_1280_attention_and_layers(tmp_path):
     """benchmark_speed's 1280² size (core/validator.py:188): C2PSA attention over N = 1600 tokens runs the block-wise
-    MFMA attention (csrc/ym_misc.hip attn_psa_flash, online softmax) — equal to the scalar kernel within fp16
+    MFMA attention (csrc/ym_attn.hip attn_psa_flash, online softmax) — equal to the scalar kernel within fp16
     rounding, and every checked layer within the f16 plan's 1e-2 of the oracle."""
     import subprocess
     import sys
@@ -826,7 +826,7 @@ def test_f16_1280_attention_and_layers(tmp_path):
 @pytest.mark.parametrize("dtype", ["f32", "f16"])
 def test_max_nms_truncation_1280_conf0001(dtype):
     """The validation default conf 0.001 (core/validator.py:91) at 1280²: more than max_nms = 30000 candidates per
-    image, so nms_image takes the `n > max_nms` branch (top 30000 by score, csrc/ym_misc.hip) exactly as the oracle's
+    image, so nms_image takes the `n > max_nms` branch (top 30000 by score, csrc/ym_nms.hip) exactly as the oracle's
     argsort[:max_nms] does.  f32 plan: every detection within 1e-3; f16 plan: its own tolerance (1 px / 1e-2)."""
     x = make_input("uniform", (8101,), 1280)
     _, y, _ = oracle().raw(x)
@@ -847,7 +847,7 @@ NMS_VARIANTS = {"default": {}, "agnostic": {"agnostic": True}, "small_max_wh": {
 @pytest.mark.parametrize("variant", list(NMS_VARIANTS))
 @pytest.mark.parametrize("dtype,B", [("f32", 2), ("x3", 8)])
 def test_nms_blocked_path_equals_per_box_path(dtype, B, variant):
-    """csrc/ym_misc.hip nms_image's blocked path (NMS_BM = 512 < candidates <= NMS_BLK_MAX = 12,224 after max_nms:
+    """csrc/ym_nms.hip nms_image's blocked path (NMS_BM = 512 < candidates <= NMS_BLK_MAX = 12,224 after max_nms:
     keys sorted in LDS, then blocks of NMS_BLK = 256 candidates filtered against the kept list and scanned through
     their own IoU bit matrix) against the one-box-per-barrier path it replaced (ym_set_debug(YM_DBG_NMS, 9)), on the
     same forward's candidates at the validator's conf 0.001 and at 0.02 / 0.004: bit-identical rows and counts (greedy

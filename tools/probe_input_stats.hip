@@ -1,4 +1,4 @@
-// Probe: what bounds input_stats (csrc/ym_misc.hip), the forward's first kernel — 21.5 us for the 39 MB yolo11s
+// Probe: what bounds input_stats (csrc/ym_input.hip), the forward's first kernel — 21.5 us for the 39 MB yolo11s
 // B=8 batch (1.8 TB/s, profiles/r06a_s_b8_x3_kernel_stats.csv).  Variants of the same max reduction, each timed
 // alone with HIP events after a 1 GB memset flush (the batch is not L2/MALL-resident when a forward starts):
 //   grid x block x float4-loads-per-lane-and-round, with or without the last-block ticket.

@@ -1,4 +1,4 @@
-// Read-bandwidth probe for the forward's first kernel (csrc/ym_misc.hip input_stats): a max-reduce over the fp32
+// Read-bandwidth probe for the forward's first kernel (csrc/ym_input.hip input_stats): a max-reduce over the fp32
 // NCHW batch (8x3x640x640 = 39.3 MB), cold (a 512 MB write between launches evicts L2 and MALL), per layout of the
 // reads.  Prints the average kernel time (HIP events around each launch) and the achieved GB/s.
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 tools/read_probe.hip -o tools/probe_bin/read_probe

@@ -1,9 +1,9 @@
-// Stand-alone timing of the NMS key sort (csrc/ym_misc.hip bitonic_sort_desc) in one 1024-thread workgroup over
+// Stand-alone timing of the NMS key sort (csrc/ym_common.h bitonic_sort_desc) in one 1024-thread workgroup over
 // n2 keys in LDS, as nms_image's blocked path runs it; cycle stamps of thread 0 around the load and the sort.
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 tools/sort_probe.hip -o tools/ab/sort_probe -Lyolo-infer_amd/yolomi -lyolomi \
 //     -Wl,-rpath,'$ORIGIN/../../yolo-infer_amd/yolomi'   (the other kernels' launchers come from the library)
 //   tools/ab/sort_probe [n2] [variant: 0 bitonic_sort_desc, 1 register-tiled]
-#include "../yolo-infer_amd/csrc/ym_misc.hip"
+#include "../yolo-infer_amd/csrc/ym_common.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -69,6 +69,8 @@ __device__ __forceinline__ void sort_reg_desc(unsigned long long* k, int tid) {
   for (int r = 0; r < K; ++r) k[e0 + r] = v[r];
   __syncthreads();
 }
+
+constexpr int NMS_SORT = 16384;  // keys nms_image sorts in LDS (csrc/ym_nms.hip): 128 KB
 
 __global__ __launch_bounds__(NMS_T) void sort_probe(const unsigned long long* in, unsigned long long* out, int n2,
                                                   long long* stamps, int variant) {

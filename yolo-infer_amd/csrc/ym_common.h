@@ -92,6 +92,15 @@ template <> struct Vec8<P2> {
   }
   static __device__ __forceinline__ type zero() { return type{0, 0, 0, 0, 0, 0, 0, 0}; }
 };
+// The storage type of a plan dtype that is not int8 / fp8, as a tag: f(YmType<f16>), f(YmType<P2>) or f(YmType<float>)
+// — the launchers' one dtype ladder (`typename decltype(t)::type` inside a generic lambda)
+template <typename T> struct YmType { typedef T type; };
+template <typename F>
+inline auto ym_with_type(int dtype, F&& f) {
+  if (dtype == YM_DT_F16) return f(YmType<f16>());
+  if (dtype == YM_DT_X3) return f(YmType<P2>());
+  return f(YmType<float>());
+}
 __device__ __forceinline__ HL ym_load_hl(const P2* p) {
   return HL{*reinterpret_cast<const f16x8*>(p), *(reinterpret_cast<const f16x8*>(p) + 1)};
 }
@@ -443,7 +452,7 @@ struct NmsArgs {
   unsigned long long* keys2; int presorted;
 };
 
-// ---- shared by the NMS kernels (csrc/ym_misc.hip nms_image, csrc/ym_nms_ml.hip): one definition of the sort and of
+// ---- shared by the NMS kernels (csrc/ym_nms.hip nms_image, csrc/ym_nms_ml.hip): one definition of the sort and of
 // the IoU arithmetic, so the single-label and the multi-label path cannot drift apart
 constexpr int NMS_T = 1024;  // threads of an NMS / key-sort workgroup
 
@@ -566,7 +575,7 @@ hipError_t ym_launch_prep(int dtype, const PrepArgs& a, int* counts, int B, hipS
 hipError_t ym_launch_input_max(const float* x, long n, float* ctl, float* out, hipStream_t st);
 hipError_t ym_launch_decode(const DecodeArgs& a, hipStream_t st);
 hipError_t ym_launch_nms(const NmsArgs& a, hipStream_t st);
-hipError_t ym_launch_nms_presort(const NmsArgs& a, hipStream_t st);  // ym_misc.hip: keys sorted by 8 WGs per image
+hipError_t ym_launch_nms_presort(const NmsArgs& a, hipStream_t st);  // ym_nms.hip: keys sorted by 8 WGs per image
 // ym_nms_ml.hip: multi-label candidates -> top max_nms -> sort -> NMS (n: nms_image's arguments, keys / counts / kstride
 // those of the selected keys)
 hipError_t ym_launch_nms_ml(const MlArgs& m, const NmsArgs& n, hipStream_t st);
@@ -576,7 +585,7 @@ hipError_t ym_launch_conv_dma_i8(const ConvArgs& a, int dma_cfg, hipStream_t st)
 hipError_t ym_launch_conv_dma_chain(const ConvArgs& a0, const ConvArgs& a1, int dma_cfg, int* ctl, int cap,
                                     hipStream_t st);  // csrc/ym_conv_dma.hip: two dependent x3 convs, one launch
 hipError_t ym_launch_stem_down_x3(const ConvArgs& s, const ConvArgs& p, hipStream_t st);  // ym_stem_fused.hip
-int ym_debug_get(int key);  // ym_set_debug switches (ym_misc.hip)
+int ym_debug_get(int key);  // ym_set_debug switches (ym_runtime.cpp)
 int ym_debug_set(int key, int value);
 void ym_debug_add(int key, int d);
 const void* ym_nms_kernel();  // the NMS kernel's function (graph replays re-point its output rows: ym_infer)

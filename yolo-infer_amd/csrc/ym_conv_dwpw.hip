@@ -11,7 +11,7 @@
 //     window pixel is fetched once per workgroup instead of 9 times per output pixel;
 //   * depthwise: lane (g, col) of wave w computes pixel 16 w + col (tile row-major), channels 32 kb + 8 g .. + 7 —
 //     exactly its B operand of v_mfma_f32_16x16x32_f16 (k = 8 g .. 8 g + 7 of pixel col), in the arithmetic of
-//     csrc/ym_misc.hip dwconv3x3* (acc = bias, fmaf over taps 0..8 on the stored values — x3: hi + lo in fp32 —,
+//     csrc/ym_dwconv.hip dwconv3x3* (acc = bias, fmaf over taps 0..8 on the stored values — x3: hi + lo in fp32 —,
 //     SiLU (x3: ym_silu_x3, f16: ym_silu_fast), then x3: hi = fp16(v), lo = fp16(v - hi)): the same B operands the
 //     unfused 1x1 would read back from the stored depthwise tensor;
 //   * the 1x1: A fragments from the LDS weight rows (pitch 32·XS + 16 halves, conflict-free for the 16-row reads as

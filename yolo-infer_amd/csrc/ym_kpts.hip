@@ -1,6 +1,6 @@
 // Pose head: Ultralytics Pose.kpts_decode (non-export path) for the anchors NMS can emit.
 //
-// decode_anchors (ym_misc.hip) has appended, per image, one key per candidate (low 32 bits = ~anchor) and the
+// decode_anchors (ym_decode.hip) has appended, per image, one key per candidate (low 32 bits = ~anchor) and the
 // candidate count.  This kernel runs behind it and before the NMS: for every candidate it reads the anchor's K·ndim
 // raw keypoint values from the head rows and writes the decoded row
 //   x = (raw·2 + gx)·stride, y = (raw·2 + gy)·stride, v = sigmoid(raw) (ndim 3), pad columns 0

@@ -15,7 +15,7 @@
 //      holds exactly min(n, max_nms) keys by construction; every slot is still compared with `cap` before the store.
 //      Appends race, but the keys are unique and sorted next, so the output does not depend on their order.
 //   3. ml_sort_chunks / ml_sort_merge: 2,048-key chunks sorted in LDS, then every key ranked against the other chunks
-//      (the scheme of nms_presort_* in csrc/ym_misc.hip; 32,768 keys do not fit in LDS at once, so the other chunks
+//      (the scheme of nms_presort_* in csrc/ym_nms.hip; 32,768 keys do not fit in LDS at once, so the other chunks
 //      pass through it one at a time).
 //   4. nms_ml_image: nms_image's blocked greedy scan (blocks of 256 candidates in score order against the kept list,
 //      an intra-block bit matrix, one wave scanning it) with the class and the score taken from the key, the sorted

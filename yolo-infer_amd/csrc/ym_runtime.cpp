@@ -11,6 +11,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -28,6 +29,39 @@
 #include "ym_track.h"
 #include "ym_annot.h"
 #include "ym_contour.h"
+
+// process-wide debug switches (ym_set_debug; include/yolomi.h YM_DBG_*): set from the environment once, then only by
+// the setter — a launch reads an atomic instead of calling getenv (getenv per launch is not thread-safe
+// against setenv and costs time on every eager forward)
+namespace {
+constexpr int kDbgKeys = YM_DBG_STOP + 1;  // include/yolomi.h YM_DBG_* keys 1..10
+std::atomic<int>* dbg_slots() {
+  static std::atomic<int> v[kDbgKeys] = {};
+  static const bool init = [] {
+    const char* names[kDbgKeys] = {nullptr,       "YM_NMS_DBG", "YM_DW_MODE", "YM_DW_TILE", "YM_CHAIN",
+                                   nullptr,       "YM_STEMFUSE", "YM_ATTN_KB", "YM_PAIRST", "YM_CONV_CFG",
+                                   nullptr};  // (YM_DBG_STOP: set by a test only, never from the environment)
+    for (int k = 1; k < kDbgKeys; ++k) {
+      if (!names[k]) continue;
+      const char* e = getenv(names[k]);
+      // these two hold value + 1 (0: unset — the pair-store default mask, no forced tile configuration)
+      v[k].store(e && *e ? atoi(e) + (k == YM_DBG_PAIRST || k == YM_DBG_CONV_CFG ? 1 : 0) : 0);
+    }
+    return true;
+  }();
+  (void)init;
+  return v;
+}
+}  // namespace
+
+int ym_debug_get(int key) { return key > 0 && key < kDbgKeys ? dbg_slots()[key].load(std::memory_order_relaxed) : 0; }
+int ym_debug_set(int key, int value) {
+  if (key <= 0 || key >= kDbgKeys) return -1;
+  return dbg_slots()[key].exchange(value);
+}
+void ym_debug_add(int key, int d) {
+  if (key > 0 && key < kDbgKeys) dbg_slots()[key].fetch_add(d);
+}
 
 namespace {
 
@@ -81,7 +115,7 @@ int fail(int code, const char* fmt, ...) {
 
 constexpr int kSplitCounters = 16384;  // split-K tiles per conv launch (csrc/ym_conv_dma.hip)
 constexpr int kChainCtl = 4096;        // ready counters (+ done, give-up words) of the persistent chain kernel
-constexpr float kPresortConf = 0.1f;  // NMS keys presorted over several workgroups below this conf (ym_misc.hip)
+constexpr float kPresortConf = 0.1f;  // NMS keys presorted over several workgroups below this conf (ym_nms.hip)
 constexpr int kMaxLanes = 4;           // concurrent batch slices in one forward graph (<= GPU_MAX_HW_QUEUES)
 constexpr size_t kMaxGraphs = 16;      // captured forwards cached per context (the oldest is retired first)
 // ym_ctx::d_misc and its sub-regions: ym_input_max's statistics (slots, ticket, partials), the control words of

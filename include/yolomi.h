@@ -398,6 +398,26 @@ int ym_annotate(ym_ctx* ctx, const void* d_frames, int frames_are_f32_chw, int B
 int ym_mask_contours(ym_ctx* ctx, const unsigned char* d_masks, int n, int H, int W, long long plane_stride,
                      int* d_points, long long cap_points, long long* d_offsets, void* stream);
 
+/* COCO run-length encoding of mask planes (pycocotools' rleEncode / rleToString; Masks.rle), on the device
+ * (csrc/ym_rle.hip).  Pixel (x, y) has the column-major index x * H + y; the counts of a plane are the
+ * lengths of its runs of 0, 1, 0, ... in that order (the first is 0 when pixel 0 is set; a plane of one value gives
+ * [H * W] or [0, H * W]) and the string is their compressed form (count k minus count k - 2 for k > 2, 5 bits a byte).
+ * Works on any context, loaded or not.  d_masks, n, H, W, plane_stride: as ym_mask_contours takes them.
+ * d_run_offsets, d_byte_offsets: n + 1 int64 words each, plane i's counts are d_counts[run_offsets[i] ..
+ * run_offsets[i + 1]) and its string d_bytes[byte_offsets[i] .. byte_offsets[i + 1]) (no terminator);
+ * d_area: n int64 words, the set pixels of each plane.  The counts of plane i are written only when
+ * run_offsets[i + 1] <= cap_counts and its bytes only when byte_offsets[i + 1] <= cap_bytes (never cut), so a caller
+ * that reads a total above its capacity calls again with the totals; a null buffer with capacity 0 skips that output
+ * (both: a count-only call).  Reading a result: the two offset arrays, then exactly the counts and / or the bytes.
+ * YM_EINVAL: a null pointer, n < 0, H or W below 1 (or H * W above 2^27), plane_stride < H * W, a negative capacity;
+ * n = 0 is valid and writes both offsets[0] = 0.  Asynchronous on `stream`; the output is the same bit for bit on
+ * every call.  Scratch: about H * W / 8 bytes per plane (its bit words) plus 68 bytes per strip, a strip being up to
+ * 13,312 words of 32 rows of one column (640 x 640 is one strip); ONE buffer per context, grown like ym_annotate's
+ * (same rules: stream-ordered calls, no growth while capturing). */
+int ym_mask_rle(ym_ctx* ctx, const unsigned char* d_masks, int n, int H, int W, long long plane_stride,
+                unsigned int* d_counts, long long cap_counts, unsigned char* d_bytes, long long cap_bytes,
+                long long* d_run_offsets, long long* d_byte_offsets, long long* d_area, void* stream);
+
 int ym_sync(ym_ctx* ctx);
 const char* ym_last_error(void);
 void ym_destroy(ym_ctx* ctx);

@@ -112,28 +112,55 @@ class Masks(_TensorView):
     `xy` / `xyn`: the instances' polygons, upstream's `masks2segments` (strategy "largest") traced on the GPU by the
     engine that made the masks (Engine.mask_contours, csrc/ym_contour.hip; the contour definition is DESIGN.md §18's,
     not cv2's), then `scale_coords((H, W), points, orig_shape)`.  Computed on first access (one launch, two small
-    device->host reads for all n instances) and cached; a hand-built Masks needs `engine=`: there is no host tracer."""
+    device->host reads for all n instances) and cached; a hand-built Masks needs `engine=`: there is no host tracer.
+
+    `rle` / `area`: the planes' COCO run-length encoding and their set pixels, encoded on the GPU by the same engine
+    (Engine.mask_rle, csrc/ym_rle.hip), lossless where `xy` keeps one outline.  The planes are encoded
+    as they are: with `retina_masks=True` they have the original image's size and the RLE is what a COCO consumer
+    (pycocotools' `segm` evaluation, upstream's `pred_to_json`) takes; by default they are the letterboxed
+    network-input planes, exact for that frame but not COCO-ready for an image of another size."""
 
     def __init__(self, masks, orig_shape=None, engine=None):
         super().__init__(masks)
         self.orig_shape = orig_shape
         self._engine = engine
         self._xy = None
+        self._rle = None  # (list of {"size", "counts"}, int64 areas)
 
     def _extra(self):
         return (self.orig_shape, self._engine)
 
     def _carry(self, other, idx=None):
-        """Hand the computed polygons (all, or those `idx` selects) to `other`, a view of the same planes."""
+        """Hand the computed polygons and RLE (all, or those `idx` selects) to `other`, a view of the same planes."""
+        if isinstance(idx, torch.Tensor):
+            idx = idx.cpu().numpy()
         if self._xy is not None:
             if idx is None:
                 other._xy = self._xy
             else:
-                if isinstance(idx, torch.Tensor):
-                    idx = idx.cpu().numpy()
                 sel = np.arange(len(self._xy))[idx]
                 other._xy = [self._xy[i] for i in np.atleast_1d(sel).tolist()]
+        if self._rle is not None:
+            if idx is None:
+                other._rle = self._rle
+            else:
+                sel = np.atleast_1d(np.arange(len(self._rle[0]))[idx])
+                other._rle = ([self._rle[0][i] for i in sel.tolist()], self._rle[1][sel])
         return other
+
+    def _planes(self, what):
+        """The (n, H, W) uint8 / bool planes on the engine's device; `what`: the refusal's first words."""
+        if self._engine is None:
+            raise RuntimeError(f"{what} on the GPU: this Masks was built by hand without "
+                               "engine= (an Engine, e.g. model.model.engine); there is no host fallback")
+        planes = torch.as_tensor(self.data)
+        if planes.dim() == 2:
+            planes = planes[None]
+        if planes.dtype not in (torch.uint8, torch.bool):
+            planes = planes != 0
+        if planes.device != self._engine.device:  # after Results.cpu(): one upload
+            planes = planes.to(self._engine.device)
+        return planes
 
     def __getitem__(self, idx):
         return self._carry(super().__getitem__(idx), idx)
@@ -154,17 +181,8 @@ class Masks(_TensorView):
     def xy(self):
         """A list of n (k_i, 2) float32 numpy arrays: each instance's polygon, (x, y) in the original image's pixels."""
         if self._xy is None:
-            if self._engine is None:
-                raise RuntimeError("Masks.xy traces the polygons on the GPU: this Masks was built by hand without "
-                                   "engine= (an Engine, e.g. model.model.engine); there is no host fallback")
+            planes = self._planes("Masks.xy traces the polygons")
             from yolomi.preprocess import scale_coords
-            planes = torch.as_tensor(self.data)
-            if planes.dim() == 2:
-                planes = planes[None]
-            if planes.dtype not in (torch.uint8, torch.bool):
-                planes = planes != 0
-            if planes.device != self._engine.device:  # after Results.cpu(): one upload
-                planes = planes.to(self._engine.device)
             shape = tuple(planes.shape[-2:])
             orig = self.orig_shape if self.orig_shape is not None else shape
             self._xy = [scale_coords(shape, torch.from_numpy(p.astype(np.float32)), orig).numpy()
@@ -177,6 +195,26 @@ class Masks(_TensorView):
         shape = self.orig_shape if self.orig_shape is not None else tuple(self.data.shape[-2:])
         wh = np.array([shape[1], shape[0]], dtype=np.float32)
         return [p / wh for p in self.xy]
+
+    def _encode(self, what):
+        if self._rle is None:
+            planes = self._planes(f"Masks.{what} is encoded")
+            size = [int(planes.shape[-2]), int(planes.shape[-1])]
+            enc = self._engine.mask_rle(planes)
+            self._rle = ([{"size": size, "counts": s} for _, s, _ in enc],
+                         np.array([a for _, _, a in enc], dtype=np.int64))
+        return self._rle
+
+    @property
+    def rle(self):
+        """A list of n {"size": [H, W], "counts": bytes}: each plane's COCO RLE (pycocotools' compressed form), at the
+        planes' own size: COCO-ready with `retina_masks=True` (the image's size), the letterboxed frame otherwise."""
+        return self._encode("rle")[0]
+
+    @property
+    def area(self):
+        """(n,) int64: the set pixels of each plane (the sum of its RLE's odd-indexed counts), from the same call."""
+        return self._encode("area")[1]
 
 
 class Keypoints(_TensorView):
@@ -462,6 +500,23 @@ class Results:
             if segs is not None:
                 out[-1]["segments"] = {"x": (segs[i][:, 0].astype(np.float64) / w).round(decimals).tolist(),
                                        "y": (segs[i][:, 1].astype(np.float64) / h).round(decimals).tolist()}
+        return out
+
+    def to_coco(self, image_id=None, class_map=None):
+        """Upstream `pred_to_json`'s entries, one dict per detection: "image_id", "category_id" (the class, through
+        `class_map` when given), "bbox" [x, y, w, h] of the top-left corner rounded to 3 decimals, "score" rounded to 5
+        and, with masks, "segmentation": Masks.rle with "counts" as str (see Masks for which planes are COCO-ready)."""
+        if self.boxes is None:
+            return []
+        rles = self.masks.rle if self.masks is not None else None
+        out = []
+        for i, row in enumerate(torch.as_tensor(self.boxes.data).cpu().tolist()):
+            (x1, y1, x2, y2), conf, c = row[:4], row[-2], int(row[-1])
+            out.append({"image_id": image_id, "category_id": class_map[c] if class_map is not None else c,
+                        "bbox": [round(x1, 3), round(y1, 3), round(x2 - x1, 3), round(y2 - y1, 3)],
+                        "score": round(conf, 5)})
+            if rles is not None:
+                out[-1]["segmentation"] = {"size": list(rles[i]["size"]), "counts": rles[i]["counts"].decode("ascii")}
         return out
 
     def save_txt(self, txt_file, save_conf=False):

@@ -29,6 +29,7 @@
 #include "ym_track.h"
 #include "ym_annot.h"
 #include "ym_contour.h"
+#include "ym_rle.h"
 
 // process-wide debug switches (ym_set_debug; include/yolomi.h YM_DBG_*): set from the environment once, then only by
 // the setter — a launch reads an atomic instead of calling getenv (getenv per launch is not thread-safe
@@ -288,6 +289,10 @@ struct ym_ctx {
   // ym_ct_words(H, W) words; grown on demand
   char* d_contour = nullptr;
   size_t contour_bytes = 0;
+  // run-length encoding (ym_mask_rle): per (plane, strip) two RleAgg, the set pixels and the strip's bit words, per
+  // plane one RleAgg (ym_rle.h RleScratch); grown on demand
+  char* d_rle = nullptr;
+  size_t rle_bytes = 0;
   // test-time augmentation: ym_tta_forward launches the forward without its NMS stage; the merged candidate set and the
   // NMS scratch over it (ym_tta_nms) belong to the first pass's context and are rebuilt only when the shape changes
   struct TtaWs {
@@ -370,6 +375,7 @@ struct ym_ctx {
     if (d_embed) (void)hipFree(d_embed);
     if (d_annot) (void)hipFree(d_annot);
     if (d_contour) (void)hipFree(d_contour);
+    if (d_rle) (void)hipFree(d_rle);
     if (cap_stream) (void)hipStreamDestroy(cap_stream);
     for (int l = 0; l < kMaxLanes; ++l) {
       if (lane_streams[l]) (void)hipStreamDestroy(lane_streams[l]);
@@ -2364,6 +2370,55 @@ int ym_mask_contours(ym_ctx* c, const unsigned char* d_masks, int n, int H, int 
                                           in_lds ? nullptr : reinterpret_cast<uint32_t*>(c->d_contour + sel_bytes),
                                           reinterpret_cast<CtSel*>(c->d_contour), d_points, cap_points, d_offsets, st);
   if (e != hipSuccess) return fail(YM_EHIP, "contour kernels: %s", hipGetErrorString(e));
+  return YM_OK;
+}
+
+// ---------------------------------------------------------------------------------- run-length encoding
+int ym_mask_rle(ym_ctx* c, const unsigned char* d_masks, int n, int H, int W, long long plane_stride, unsigned int* d_counts,
+                long long cap_counts, unsigned char* d_bytes, long long cap_bytes, long long* d_run_offsets,
+                long long* d_byte_offsets, long long* d_area, void* stream) {
+  if (!c) return fail(YM_EINVAL, "null context");
+  if (!d_run_offsets || !d_byte_offsets || (n > 0 && (!d_masks || !d_area)) || (cap_counts > 0 && !d_counts) ||
+      (cap_bytes > 0 && !d_bytes))
+    return fail(YM_EINVAL, "ym_mask_rle: null pointer argument");
+  if (n < 0 || H < 1 || W < 1 || (long long)H * W > kRleMaxPixels || cap_counts < 0 || cap_bytes < 0)
+    return fail(YM_EINVAL, "ym_mask_rle: %d planes of %d x %d (1 x 1 .. 2^27 pixels), capacities %lld, %lld", n, H, W,
+                cap_counts, cap_bytes);
+  if (plane_stride < (long long)H * W)
+    return fail(YM_EINVAL, "ym_mask_rle: plane stride %lld below %d x %d", plane_stride, H, W);
+  const RleGeom g = ym_rle_geom(H, W);
+  const long long strips = (long long)n * g.strips;
+  if (strips > 0x7fffffffll) return fail(YM_EINVAL, "ym_mask_rle: %d planes of %d strips", n, g.strips);
+  HIPCK(hipSetDevice(c->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t agg_bytes = pad((size_t)strips * sizeof(RleAgg)), set_bytes = pad((size_t)strips * sizeof(int));
+  const size_t total_bytes = pad((size_t)n * sizeof(RleAgg));
+  const size_t need = 2 * agg_bytes + set_bytes + total_bytes + (size_t)strips * g.CS * g.JS * sizeof(uint32_t);
+  if (need > c->rle_bytes) {  // (an earlier call may still use the old scratch)
+    if (c->d_rle) {
+      HIPCK(hipDeviceSynchronize());
+      HIPCK(hipFree(c->d_rle));
+      c->d_rle = nullptr;
+      c->rle_bytes = 0;
+    }
+    const hipError_t e = hipMalloc(&c->d_rle, need);
+    if (e != hipSuccess) {
+      c->d_rle = nullptr;
+      return fail(YM_ENOMEM, "ym_mask_rle: %zu scratch bytes: %s", need, hipGetErrorString(e));
+    }
+    c->rle_bytes = need;
+  }
+  RleScratch ws;
+  char* at = c->d_rle;
+  ws.own = reinterpret_cast<RleAgg*>(at);
+  ws.prefix = reinterpret_cast<RleAgg*>(at += agg_bytes);
+  ws.set = reinterpret_cast<int*>(at += agg_bytes);
+  ws.total = reinterpret_cast<RleAgg*>(at += set_bytes);
+  ws.words = reinterpret_cast<uint32_t*>(at += total_bytes);
+  const hipError_t e = ym_launch_rle(d_masks, plane_stride, n, g, ws, cap_counts > 0 ? d_counts : nullptr, cap_counts,
+                                     cap_bytes > 0 ? d_bytes : nullptr, cap_bytes, d_run_offsets, d_byte_offsets, d_area, st);
+  if (e != hipSuccess) return fail(YM_EHIP, "rle kernels: %s", hipGetErrorString(e));
   return YM_OK;
 }
 

@@ -474,6 +474,50 @@ class Engine:
         self._ready(x, B, H, W, args, stream, dets, counts)
         return x.data_ptr(), B, H, W, args, dets.data_ptr(), counts.data_ptr(), stream
 
+    def mask_rle_device(self, masks: torch.Tensor, cap_counts: Optional[int] = None, cap_bytes: Optional[int] = None):
+        """COCO run-length encoding of n mask planes, left on the device (csrc/ym_rle.hip).  masks: as
+        mask_contours_device takes them.  Returns (counts, string bytes, run offsets, byte offsets, areas): (cap_counts,)
+        int32 holding uint32 run lengths, (cap_bytes,) uint8, two (n + 1,) int64 and (n,) int64; plane i's counts are
+        counts[run_offsets[i]:run_offsets[i + 1]], its string bytes[byte_offsets[i]:byte_offsets[i + 1]].  Defaults:
+        max(4096, 64 n) counts and four times as many bytes; a plane whose counts or bytes end beyond a capacity is
+        left unwritten in that buffer and the call is to be repeated with the totals (mask_rle does).  Enqueued on
+        the current stream; nothing is read."""
+        if masks.dim() != 3 or masks.dtype not in (torch.uint8, torch.bool) or masks.device != self.device:
+            raise ValueError("mask_rle: masks must be an (n, H, W) uint8 / bool tensor on the engine's device")
+        n, H, W = masks.shape
+        if H < 1 or W < 1:
+            raise ValueError(f"mask_rle: planes of {H} x {W}")
+        if n and (masks.stride(2) != 1 or masks.stride(1) != W or (n > 1 and masks.stride(0) < H * W)):
+            masks = masks.contiguous()
+        cap_counts = max(4096, 64 * n) if cap_counts is None else int(cap_counts)
+        cap_bytes = 4 * max(4096, 64 * n) if cap_bytes is None else int(cap_bytes)
+        counts = torch.empty((cap_counts,), dtype=torch.int32, device=self.device)
+        data = torch.empty((cap_bytes,), dtype=torch.uint8, device=self.device)
+        run_offs = torch.empty((n + 1,), dtype=torch.int64, device=self.device)
+        byte_offs = torch.empty((n + 1,), dtype=torch.int64, device=self.device)
+        area = torch.empty((n,), dtype=torch.int64, device=self.device)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        self.rt.mask_rle(masks.data_ptr() if n else 0, n, H, W, masks.stride(0) if n > 1 else H * W,
+                         counts.data_ptr() if cap_counts else 0, cap_counts, data.data_ptr() if cap_bytes else 0, cap_bytes,
+                         run_offs.data_ptr(), byte_offs.data_ptr(), area.data_ptr(), stream)
+        return counts, data, run_offs, byte_offs, area
+
+    def mask_rle(self, masks: torch.Tensor, cap_counts: Optional[int] = None, cap_bytes: Optional[int] = None):
+        """COCO run-length encoding of n mask planes: a list of n (counts: uint32 numpy array, string: bytes, area:
+        int), pycocotools' uncompressed and compressed forms of each plane (column-major runs of 0, 1, 0, ...).  One
+        small read of the offsets and areas, then exactly the counts and the bytes; a first capacity that proves too
+        small costs one more call."""
+        out = self.mask_rle_device(masks, cap_counts, cap_bytes)
+        meta = torch.cat(out[2:]).cpu().numpy()
+        n = masks.shape[0]
+        runs, nbytes = int(meta[n]), int(meta[2 * n + 1])
+        if runs > out[0].shape[0] or nbytes > out[1].shape[0]:
+            out = self.mask_rle_device(masks, runs, nbytes)
+        ro, bo, area = meta[:n + 1], meta[n + 1:2 * n + 2], meta[2 * n + 2:]
+        counts = out[0][:runs].cpu().numpy().view(np.uint32)
+        data = out[1][:nbytes].cpu().numpy().tobytes()
+        return [(counts[ro[i]:ro[i + 1]], data[bo[i]:bo[i + 1]], int(area[i])) for i in range(n)]
+
     def profile(self, x: torch.Tensor, **kw):
         return self.rt.profile(*self._profile_call(x, kw))
 

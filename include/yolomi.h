@@ -38,7 +38,7 @@ typedef struct {
   int max_h;
   int max_w;
   int scale;  /* 0 = any, else 'n', 's', 'm', 'l' or 'x' */
-  int task;   /* 0 = any, YM_TASK_DETECT, YM_TASK_SEGMENT, YM_TASK_POSE */
+  int task;   /* 0 = any, YM_TASK_DETECT, YM_TASK_SEGMENT, YM_TASK_POSE, YM_TASK_CLASSIFY */
   int dtype;  /* 0 = any, YM_DTYPE_F16, YM_DTYPE_F32, YM_DTYPE_I8, YM_DTYPE_F8, YM_DTYPE_X3 */
   int reserved[2];
 } ym_model_desc;
@@ -46,6 +46,7 @@ typedef struct {
 #define YM_TASK_DETECT 1
 #define YM_TASK_SEGMENT 2
 #define YM_TASK_POSE 3 /* Detect + keypoint branch; ym_infer rows carry the decoded keypoints (see ym_infer) */
+#define YM_TASK_CLASSIFY 4 /* the backbone without SPPF + the Classify head; run by ym_classify, not ym_infer */
 #define YM_DTYPE_F16 1 /* fp16 storage, fp32 MFMA accumulation (throughput plan) */
 #define YM_DTYPE_F32 2 /* exact-f32 MFMA (parity plan) */
 #define YM_DTYPE_I8 3  /* PTQ int8 (torch.ao qconfig of optimization/quantization/quantizers.py:124-131) */
@@ -185,10 +186,12 @@ int ym_kpt_shape(ym_ctx* ctx, int* K, int* ndim);
  * ~anchor, in no fixed order; YM_SCRATCH_COUNTS: the B candidate counts (int32); YM_SCRATCH_KPTS (pose plans): the
  * decoded keypoint rows (B, A, nm) fp32, written for the candidates' anchors only.
  * After a multi-label forward (ym_infer_args.multi_label = 1) YM_SCRATCH_COUNTS holds the per-image (anchor, class)
- * PAIR counts, before the max_nms cut, and YM_SCRATCH_KEYS the unused single-label keys. */
+ * PAIR counts, before the max_nms cut, and YM_SCRATCH_KEYS the unused single-label keys.
+ * YM_SCRATCH_POOLED (classify plans): the (B, 1280) fp32 pooled vectors of the last ym_classify, the Linear's input. */
 #define YM_SCRATCH_KEYS 0
 #define YM_SCRATCH_COUNTS 1
 #define YM_SCRATCH_KPTS 2
+#define YM_SCRATCH_POOLED 3
 int ym_read_scratch(ym_ctx* ctx, int which, void* dst, size_t bytes);
 
 /* Segment plans: instance masks of the detections of the last ym_infer (same B, H, W, stream order), i.e. Ultralytics
@@ -288,6 +291,18 @@ typedef struct {
 } ym_embed_view;
 int ym_embed(ym_ctx* ctx, const float* d_input, int B, int H, int W, const ym_infer_args* args,
              const ym_embed_view* views, int n_views, float* d_out, long long out_stride, void* stream);
+
+/* Classification (classify plans, YM_TASK_CLASSIFY): one forward of the yolo11-cls graph and its Classify head
+ * (csrc/ym_classify.hip).  d_input and the LoadTensor /255 rule as ym_infer (args: in_eps, d_batch_max, use_graph; the
+ * NMS fields are not read; one lane).  d_probs: (B, ld) fp32, ld >= nc, the softmax of image b in d_probs[b * ld ..];
+ * d_logits: (B, nc) fp32 Linear outputs, or NULL; d_topk / d_topk_conf: (B, k) with k = min(5, nc), the k most
+ * probable classes and their probabilities, best first, equal probabilities to the lower class.  Asynchronous on
+ * `stream`; with use_graph the forward is captured once per (shape, pointers) and replayed.  Results are bit-identical
+ * from call to call and between eager launches and replays.  YM_EINVAL: a null pointer (d_logits excepted), ld < nc,
+ * or a plan that is not a classify plan.  ym_infer on a classify plan returns YM_EINVAL; ym_embed, ym_read_buffer and
+ * ym_profile* serve it like any plan. */
+int ym_classify(ym_ctx* ctx, const float* d_input, int B, int H, int W, const ym_infer_args* args, float* d_probs,
+                int ld, float* d_logits, int* d_topk, float* d_topk_conf, void* stream);
 
 /* Object tracking (Ultralytics model.track(..., tracker="bytetrack.yaml"), trackers/byte_tracker.py BYTETracker.update):
  * a tracker holds the ByteTrack state of `streams` independent video streams in device memory; one ym_track_update

@@ -4,7 +4,9 @@ Same constructor, `predict`, `benchmark`, `get_model_info`, `.model` surface as 
 (`core/model.py:29-295`), but `predict` runs the hand-written gfx950 path (`yolomi.engine.Engine` → libyolomi.so →
 one HIP-graph replay per batch) instead of delegating to `ultralytics.YOLO.predict` (`core/model.py:133`).
 
-Scope: tasks detect/segment/pose, sizes n/s/m/l/x, `torch.Tensor` sources (BCHW or CHW, H,W % 32 == 0,
+Scope: tasks detect/segment/pose, and classify for models built from weights (a yolo11-cls checkpoint,
+state dict or packed blob decides the task, whatever `task=` says; there is no checkpoint to fetch offline, so a bare
+task="classify" raises NotImplementedError), sizes n/s/m/l/x, `torch.Tensor` sources (BCHW or CHW, H,W % 32 == 0,
 LoadTensor's /255 rule).  There is no CPU fallback: a CPU device or a missing libyolomi.so raises.
 """
 from __future__ import annotations
@@ -21,7 +23,7 @@ import torch
 from yolomi.engine import Engine
 from yolomi.synth import synth_weights
 
-from .results import LazyCounts, Results
+from .results import LazyCounts, Probs, Results
 
 logger = logging.getLogger(__name__)
 
@@ -192,7 +194,11 @@ class YOLO11Model:
         `state_dict` = weights already in memory, `weights_from` = (rccl comm, root): receive the root rank's model
         over RCCL, or a yolomi Runtime that already received it (yolomi.dist.rccl_broadcast_model), `kpt_shape` =
         (K, 2 | 3) of a pose model (default: (17, 3) for synthetic weights; for a checkpoint (nk // 3, 3) when its nk
-        keypoint channels divide by 3, else (nk // 2, 2))."""
+        keypoint channels divide by 3, else (nk // 2, 2)).
+        Classification: the weights decide the task.  `model_path`, `state_dict` or `weights_blob` holding a yolo11-cls
+        model give a classify model whatever `task=` says (as any checkpoint overrides size and task); task="classify"
+        with no weights raises NotImplementedError — there are no synthetic class names to serve and no checkpoint to
+        fetch offline, so pass weights.  predict() then returns Results with `probs` set."""
         self.task = task
         self.size = size
         self.device = device or self._get_default_device()
@@ -223,7 +229,12 @@ class YOLO11Model:
         if self.size not in self.SUPPORTED_SIZES:
             raise ValueError(f"Unsupported size: {self.size}. Supported: {self.SUPPORTED_SIZES}")
         if self.task not in self.HIP_TASKS:
-            raise NotImplementedError(f"task {self.task!r} has no MI355X plan (supported: {self.HIP_TASKS})")
+            has_weights = self.model_path or self._sd is not None or self._blob is not None
+            if self.task == "classify" and has_weights:
+                return  # the weights decide (they must hold a yolo11-cls model: _load_model)
+            hint = ("; a classify model is built from its weights: pass model_path=, state_dict= or weights_blob= of a "
+                    "yolo11-cls model (there is no checkpoint to fetch offline)") if self.task == "classify" else ""
+            raise NotImplementedError(f"task {self.task!r} has no MI355X plan (supported: {self.HIP_TASKS}){hint}")
 
     def _load_model(self) -> _ModelHandle:
         dev = torch.device(self.device)
@@ -243,6 +254,12 @@ class YOLO11Model:
                 sd = synth_weights(self.size, self.task, self.seed)
             nc = 1 if self.task == "pose" else 80
             kpt_shape = self._kpt_shape
+            if self._blob is not None:  # a packed model says what it is in its header
+                from yolomi.plan import TASK_IDS, unpack_blob
+                h = unpack_blob(self._blob)[0]
+                if h.task == TASK_IDS["classify"]:
+                    self.task, nc = "classify", h.nc
+                    self.size = chr(h.scale) if h.scale else self.size
             if sd and self._blob is None:  # the checkpoint decides the architecture, as YOLO(model_path) does
                 from yolomi.arch import infer_arch, infer_kpt_shape
                 scale, task, nc = infer_arch(sd, kpt_shape)
@@ -251,6 +268,8 @@ class YOLO11Model:
                     logger.warning(f"{self.model_path or 'state_dict'} holds a yolo11{scale} {task} model "
                                    f"(nc={nc}); using it instead of size={self.size!r} task={self.task!r}")
                     self.size, self.task = scale, task
+            if self.task == "classify" and not sd and self._blob is None:
+                raise NotImplementedError("task 'classify': pass the weights of a yolo11-cls model")
             engine = Engine(self.size, self.task, sd, dev, self.dtype, blob=self._blob, qparams=self._qparams, nc=nc,
                             receive=self._weights_from, kpt_shape=kpt_shape if self.task == "pose" else None)
             names = COCO_NAMES if nc == 80 else {i: f"class{i}" for i in range(nc)}
@@ -302,7 +321,51 @@ class YOLO11Model:
         bm = self.global_batch_max(im) if self.global_batch_max is not None and imsrc is None else None
         return im, eps, imsrc, bm, t0, t1
 
+    def _predict_classify(self, source, kwargs) -> List[Results]:
+        """predict() of a classify model: Results with `probs` (core.results.Probs) and no boxes, masks or keypoints.
+        Tensor sources (BCHW float, H and W multiples of 32, LoadTensor's /255 rule) stay asynchronous: the head's
+        kernels write fresh tensors and nothing is read on the host.  Image sources go through upstream's
+        classify_transforms on the host (yolomi.preprocess.classify_batch; imgsz default 224).  conf, iou, max_det,
+        augment and retina_masks do not apply."""
+        ignored = [k for k in ("conf", "iou", "max_det", "augment", "retina_masks") if k in kwargs]
+        if ignored:
+            logger.debug(f"classify: {', '.join(ignored)} ignored")
+        t0 = time.perf_counter()
+        eng = self.model.engine
+        imgs = paths = None
+        if isinstance(source, torch.Tensor) or (isinstance(source, (list, tuple)) and source
+                                                and all(isinstance(s, torch.Tensor) for s in source)):
+            im, eps, _ = self._as_batch(source)
+        else:
+            from yolomi.preprocess import classify_batch, expand_sources
+            imgs, paths = expand_sources(source)
+            im = classify_batch(imgs, int(kwargs.get("imgsz", 224))).to(self._dev)
+            eps = torch.finfo(torch.float32).eps
+        t1 = time.perf_counter()
+        bm = self.global_batch_max(im) if self.global_batch_max is not None and imgs is None else None
+        B, nc = im.shape[0], eng.graph.nc
+        k = min(5, nc)
+        out = (torch.empty((B, nc), dtype=torch.float32, device=im.device),
+               torch.empty((B, k), dtype=torch.int32, device=im.device),
+               torch.empty((B, k), dtype=torch.float32, device=im.device))
+        probs, topk, conf = eng.classify(im, out=out, in_eps=eps, batch_max=bm)
+        if kwargs.get("sync", False):
+            torch.cuda.current_stream(im.device).synchronize()
+        speed = _speed(t0, t1)
+        res = []
+        for b in range(B):
+            if imgs is None:
+                r = Results.from_batch(im, b, self.model.names, None, 0, path=f"image{b}.jpg", speed=speed)
+            else:
+                r = Results.from_image(imgs[b], paths[b], self.model.names, None, speed=speed)
+            r.boxes = None
+            r.probs = Probs(probs[b], topk[b], conf[b])
+            res.append(r)
+        return res
+
     def predict(self, source, **kwargs) -> List[Results]:
+        if self.task == "classify" and kwargs.get("embed", None) is None:
+            return self._predict_classify(source, kwargs)
         nms = _nms_kwargs(kwargs)
         augment = bool(kwargs.get("augment", False))
         if kwargs.get("embed", None) is not None:
@@ -390,6 +453,8 @@ class YOLO11Model:
         (yolomi.track.tracker_config); "botsort.yaml" and segment models raise NotImplementedError; a batch size other
         than the live tracker's under persist=True raises ValueError."""
         from yolomi.track import tracker_config
+        if self.task == "classify":
+            raise NotImplementedError("track() needs detections: a classify model has none")
         cfg = tracker_config(tracker)
         if self.task == "segment":
             raise NotImplementedError("track() is offered for detect and pose models: a segment model's masks would "
@@ -416,9 +481,9 @@ class YOLO11Model:
         predict's own (letterboxed image sources, LoadTensor's /255 rule for tensors).  augment and retina_masks do
         not apply (upstream returns before either is looked at).  Unlike upstream, which ignores an index no layer
         has and returns ordinary predictions, an index outside 0..22, a non-integer or an empty list raises."""
-        from yolomi.arch import normalize_embed
+        from yolomi.arch import EMBED_LAYERS, normalize_embed
         eng = self.model.engine
-        layers = normalize_embed(kwargs["embed"])
+        layers = normalize_embed(kwargs["embed"], 10 if self.task == "classify" else EMBED_LAYERS)
         eng._embed_table(layers)  # (raises for a layer the plan does not store, or a quantized plan)
         ignored = [k for k in ("augment", "retina_masks") if kwargs.get(k, False)]
         if ignored:
@@ -432,8 +497,8 @@ class YOLO11Model:
         """Ultralytics Model.embed: predict(source, embed=[len(model.model) - 2]) unless `embed` is given — layer 22,
         the last neck C3k2 (256 channels for yolo11n, 512 for yolo11s)."""
         from yolomi.arch import DEFAULT_EMBED
-        if kwargs.get("embed", None) is None:
-            kwargs["embed"] = list(DEFAULT_EMBED)
+        if kwargs.get("embed", None) is None:  # (a classify model: layer 9, 256 channels for yolo11n-cls)
+            kwargs["embed"] = [9] if self.task == "classify" else list(DEFAULT_EMBED)
         return self.predict(source, **kwargs)
 
     def _predict_retina(self, im, eps, imsrc, bm, t0, t1, nms) -> List[Results]:
@@ -512,6 +577,8 @@ class YOLO11Model:
         keypoint matches — with upstream PoseMetrics' `(B)` / `(P)` keys in `.results_dict`; augment=True warns and
         validates at a single scale.  Segment models raise NotImplementedError."""
         from yolomi.val import run_val
+        if self.task == "classify":
+            raise NotImplementedError("val() computes detection metrics: classification validation is not offered")
         if data is None:
             raise ValueError("val() needs data: a dataset YAML, a directory with images/ and labels/, or a list")
         if ignored:

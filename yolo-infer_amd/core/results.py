@@ -7,7 +7,7 @@ Tensors stay on the model's device, like upstream.
 """
 from __future__ import annotations
 
-from typing import Dict, Optional
+from typing import Dict, List, Optional
 
 import numpy as np
 import torch
@@ -251,6 +251,59 @@ class Keypoints(_TensorView):
         return self.data[..., 2] if self.has_visible else None
 
 
+class Probs(_TensorView):
+    """Upstream `Probs`: the class probabilities of one image.  `data` is the (nc,) softmax the head's kernel wrote;
+    top1 / top5 / top1conf / top5conf read that kernel's own top-k (csrc/ym_classify.hip: descending, equal
+    probabilities to the lower class) — nothing is sorted on the host.  top1 and top5 read the device (one small
+    copy, cached); data, top1conf and top5conf stay tensors, and move with cpu() / numpy() / cuda() / to() as data
+    does.  An index (probs[idx]) gives the Probs of data[idx], its top-k taken from those values."""
+
+    def __init__(self, probs, topk=None, topk_conf=None):
+        super().__init__(probs)
+        if topk is None:  # a hand-built or indexed Probs: the same order from a stable sort
+            topk_conf, topk = torch.sort(torch.as_tensor(probs).reshape(-1), descending=True, stable=True)
+            topk, topk_conf = topk[:5].to(torch.int32), topk_conf[:5]
+            if not isinstance(probs, torch.Tensor):
+                topk, topk_conf = topk.numpy(), topk_conf.numpy()
+        self._topk, self._conf, self._host = topk, topk_conf, None
+
+    def _moved(self, f):
+        return Probs(f(self.data), f(self._topk), f(self._conf))
+
+    def cpu(self):
+        return self._moved(lambda t: t.cpu() if isinstance(t, torch.Tensor) else t)
+
+    def numpy(self):
+        return self._moved(lambda t: t.cpu().numpy() if isinstance(t, torch.Tensor) else t)
+
+    def cuda(self):
+        return self._moved(lambda t: torch.as_tensor(t).cuda())
+
+    def to(self, *args, **kwargs):
+        return self._moved(lambda t: torch.as_tensor(t).to(*args, **kwargs))
+
+    def __getitem__(self, idx):
+        return Probs(self.data[idx])
+
+    @property
+    def top5(self) -> List[int]:
+        if self._host is None:
+            self._host = torch.as_tensor(self._topk).tolist()
+        return self._host
+
+    @property
+    def top1(self) -> int:
+        return self.top5[0]
+
+    @property
+    def top5conf(self):
+        return self._conf
+
+    @property
+    def top1conf(self):
+        return self._conf[0]
+
+
 class LazyCounts:
     """The B detection counts of one asynchronous predict() call, still on the device (the words the NMS kernel
     writes behind the call's rows): read to the host once, on the first access by any of the call's Results."""
@@ -284,7 +337,8 @@ class Results:
         self._orig_img = None
         self.orig_shape = tuple(orig_tensor.shape[-2:]) if orig_tensor is not None else None
         self.names = names
-        self.boxes = Boxes(boxes, self.orig_shape)
+        self._dets = None
+        self.boxes = Boxes(boxes, self.orig_shape) if boxes is not None else None  # (None: a classification result)
         self.masks = Masks(masks, self.orig_shape, engine=annotator) if masks is not None else None
         self.path = path
         self.speed = speed or {"preprocess": None, "inference": None, "postprocess": None}
@@ -337,7 +391,8 @@ class Results:
         r._mask_geo = tuple(int(v) for v in mask_geo) if mask_geo is not None else None
         r._orig_img = img_bgr
         r.orig_shape = tuple(img_bgr.shape[:2])
-        r.boxes.orig_shape = r.orig_shape
+        if r.boxes is not None:
+            r.boxes.orig_shape = r.orig_shape
         if r._kpts is not None:
             r._kpts.orig_shape = r.orig_shape
         if r.masks is not None:
@@ -361,7 +416,7 @@ class Results:
 
     @property
     def boxes(self) -> "Boxes":
-        if self._boxes is None:
+        if self._boxes is None and self._dets is not None:
             self._boxes = Boxes(self._dets[self._b, : self._count, :self._ncol], self.orig_shape)
         return self._boxes
 
@@ -413,8 +468,24 @@ class Results:
             self._orig_img = (t.permute(1, 2, 0).contiguous() * 255).clamp_(0, 255).to(torch.uint8).cpu().numpy()
         return self._orig_img
 
-    def __len__(self):
-        return len(self.boxes)
+    def __len__(self):  # (upstream: the length of the first field that is set; a classification result: its nc)
+        return len(self.boxes) if self.boxes is not None else (len(self.probs) if self.probs is not None else 0)
+
+    def _no_detections(self, what: str):
+        if self.boxes is None and self.probs is not None:
+            raise NotImplementedError(f"{what} needs detections: a classification result has probs only")
+
+    def verbose(self) -> str:
+        """Upstream `Results.verbose`: "name conf, " of a classification result's top-5; else "n name(s), " per detected
+        class in ascending class order, "(no detections), " for none."""
+        if self.probs is not None:
+            p = self.probs
+            return ", ".join(f"{self.names[j]} {c:.2f}"
+                             for j, c in zip(p.top5, torch.as_tensor(p.top5conf).tolist())) + ", "
+        if len(self) == 0:
+            return "(no detections), "
+        cls, n = torch.as_tensor(self.boxes.cls).unique(return_counts=True)
+        return "".join(f"{k} {self.names[int(c)]}{'s' * (k > 1)}, " for c, k in zip(cls.tolist(), n.tolist()))
 
     def _like(self, orig_tensor, boxes, masks, keypoints=None):
         r = Results(orig_tensor, self.names, boxes, masks, self.path, self.speed, keypoints=keypoints,
@@ -423,7 +494,8 @@ class Results:
         if orig_tensor is None:  # image-file / ndarray source: keep the loaded image and its shape
             r._orig_img = self._orig_img
             r.orig_shape = self.orig_shape
-            r.boxes.orig_shape = self.orig_shape
+            if r.boxes is not None:
+                r.boxes.orig_shape = self.orig_shape
             if r.masks is not None:
                 r.masks.orig_shape = self.orig_shape
             if r.keypoints is not None:
@@ -431,6 +503,10 @@ class Results:
         return r
 
     def __getitem__(self, idx):
+        if self.boxes is None:  # a classification result: its probs, indexed
+            r = self._like(self._orig_tensor, None, None)
+            r.probs = self.probs[idx] if self.probs is not None else None
+            return r
         k = self.keypoints
         r = self._like(self._orig_tensor, self.boxes.data[idx],
                        self.masks.data[idx] if self.masks is not None else None,
@@ -440,6 +516,10 @@ class Results:
         return r
 
     def cpu(self):
+        if self.boxes is None:  # a classification result: its probs on the host
+            r = self._like(self._orig_tensor.cpu() if self._orig_tensor is not None else None, None, None)
+            r.probs = self.probs.cpu() if self.probs is not None else None
+            return r
         k = self.keypoints
         r = self._like(self._orig_tensor.cpu() if self._orig_tensor is not None else None, self.boxes.data.cpu(),
                        self.masks.data.cpu() if self.masks is not None else None,
@@ -458,6 +538,7 @@ class Results:
         A hand-built Results needs `annotator=`: there is no host painter, so RuntimeError without one.
         `orig_img`, the rows and the masks are left as they are."""
         from yolomi.annotate import plot_results
+        self._no_detections("plot()")
         if ignored:
             import logging
             logging.getLogger(__name__).info(f"plot: ignoring {sorted(ignored)}")
@@ -486,6 +567,9 @@ class Results:
     def summary(self, normalize=False, decimals=5):
         """Upstream `Results.summary`: one dict per detection; with masks, its polygon as "segments": {"x": [...],
         "y": [...]} (Masks.xy, divided by the image's width / height when `normalize`), rounded to `decimals`."""
+        if self.probs is not None:  # classification: the top-1
+            p = self.probs
+            return [{"name": self.names[p.top1], "class": p.top1, "confidence": round(float(p.top1conf), decimals)}]
         out = []
         is_track = self.boxes.is_track
         segs = self.masks.xy if self.masks is not None else None
@@ -506,6 +590,7 @@ class Results:
         """Upstream `pred_to_json`'s entries, one dict per detection: "image_id", "category_id" (the class, through
         `class_map` when given), "bbox" [x, y, w, h] of the top-left corner rounded to 3 decimals, "score" rounded to 5
         and, with masks, "segmentation": Masks.rle with "counts" as str (see Masks for which planes are COCO-ready)."""
+        self._no_detections("to_coco()")
         if self.boxes is None:
             return []
         rles = self.masks.rle if self.masks is not None else None
@@ -525,6 +610,15 @@ class Results:
         (with their visibility when they have one) for pose; then the confidence when `save_conf`, then the track id of
         tracked rows.  Values are written with %g.  Nothing is written for an image without detections."""
         import os
+        if self.probs is not None:  # classification: upstream's "{conf:.2f} {name}" lines of the top-5
+            p = self.probs
+            texts = [f"{c:.2f} {self.names[j]}" for j, c in zip(p.top5, torch.as_tensor(p.top5conf).tolist())]
+            d = os.path.dirname(str(txt_file))
+            if d:
+                os.makedirs(d, exist_ok=True)
+            with open(txt_file, "a", encoding="utf-8") as f:
+                f.writelines(t + "\n" for t in texts)
+            return
         boxes, masks, kpts = self.boxes, self.masks, self.keypoints
         xywhn = torch.as_tensor(boxes.xywhn).cpu().tolist()
         rows = torch.as_tensor(boxes.data).cpu().tolist()
@@ -549,4 +643,6 @@ class Results:
                 f.writelines(t + "\n" for t in texts)
 
     def __repr__(self):
+        if self.boxes is None and self.probs is not None:
+            return f"Results(probs={tuple(self.probs.shape)}, orig_shape={self.orig_shape})"
         return f"Results(boxes={len(self.boxes)}, orig_shape={self.orig_shape})"

@@ -36,7 +36,10 @@ int validate_ops(const Plan& p, std::string& err) {
     };
     bool ok = true;
     switch (o.kind) {
-      case OP_INPUT: case OP_DECODE: case OP_NMS: break;  // no operands besides the header's input/anchor buffers
+      case OP_INPUT: break;
+      case OP_DECODE: case OP_NMS:  // no operands besides the header's input/anchor buffers
+        if (p.h.task == kTaskClassify) return bad(err, "op %s: a classify plan has no decode or NMS stage", o.name);
+        break;
       case OP_CONV: {
         const int N = o.n, Kpad = o.kpad;
         const int Nout = o.k2 ? o.n2 : N;            // the channels the launch writes (a fused pair: its second conv's)
@@ -74,6 +77,16 @@ int validate_ops(const Plan& p, std::string& err) {
         ok = o.cin > 0 && view_ok(o.src0, o.src0_coff, o.cin, false) && view_ok(o.dst, o.dst_coff, o.cin, false) &&
              w_ok(o.q_off, kQRecBytes);
         break;
+      case OP_CLASSIFY: {  // the head conv's operands, the Linear's; K a whole number of the kernel's 64-deep stages
+        const size_t xs = dtype == YM_DT_X3 ? 2 : 1, lw = dtype == YM_DT_F16 ? 2 : 4;
+        ok = p.h.task == kTaskClassify && !ym_dt_q8(dtype) && o.n == kClsWidth && o.c0 > 0 && o.c0 % 64 == 0 &&
+             o.cin == o.c0 && view_ok(o.src0, o.src0_coff, o.c0, false) && o.src0_coff % 8 == 0 &&
+             p.bufs[o.src0].C % 8 == 0 && p.bufs[o.src0].f > 0 && o.kpad % 8 == 0 && o.kpad <= (1 << 16) &&
+             (size_t)o.kpad >= xs * o.c0 && w_ok(o.w_off, (size_t)o.n * o.kpad * esz) && w_ok(o.b_off, (size_t)o.n * 4) &&
+             o.cls_nc() == p.h.nc && o.kpad2 == kClsWidth && w_ok(o.w2_off, (size_t)o.n2 * kClsWidth * lw) &&
+             w_ok(o.b2_off, (size_t)o.n2 * 4);
+        break;
+      }
       default: return bad(err, "op %s: unknown op kind %d", o.name, o.kind);
     }
     if (!ok) return bad(err, "op %s: buffer id, channel view or weight range out of bounds", o.name);
@@ -83,7 +96,9 @@ int validate_ops(const Plan& p, std::string& err) {
 
 }  // namespace
 
-const char* ym_task_name(int t) { return t == 0 ? "detect" : t == 1 ? "segment" : t == kTaskPose ? "pose" : "unknown"; }
+const char* ym_task_name(int t) {
+  return t == 0 ? "detect" : t == 1 ? "segment" : t == kTaskPose ? "pose" : t == kTaskClassify ? "classify" : "unknown";
+}
 
 int op_reads(const OpRec& o, int out[3]) {
   int n = 0;
@@ -93,7 +108,7 @@ int op_reads(const OpRec& o, int out[3]) {
       if (o.src1 >= 0) out[n++] = o.src1;
       if (o.res >= 0) out[n++] = o.res;
       break;
-    case OP_DW: case OP_ATTN: case OP_REQ: out[n++] = o.src0; break;
+    case OP_DW: case OP_ATTN: case OP_REQ: case OP_CLASSIFY: out[n++] = o.src0; break;
     case OP_SPPF: out[n++] = o.sppf_buf(); break;
     default: break;
   }
@@ -122,11 +137,13 @@ int ym_plan_parse(const void* blob, size_t bytes, const ym_model_desc* want, Pla
   const int dtype = h.dtype, task = h.task, nm = h.nm;
   if (dtype != YM_DT_F16 && !ym_dt_f32s(dtype) && !ym_dt_q8(dtype)) return bad(err, "unknown dtype %d", dtype);
   if (h.nl < 1 || h.nl > kMaxLevels) return bad(err, "bad level count");
-  if (h.nc < 1 || h.nc > 128 || nm < 0 || nm > 64 || h.reg_max < 1 || h.reg_max > 64)
+  const bool cls = task == kTaskClassify;  // (its nc is a Linear's rows, not a class bit mask's)
+  if (h.nc < 1 || h.nc > (cls ? 1 << 20 : 128) || nm < 0 || nm > 64 || h.reg_max < 1 || h.reg_max > 64)
     return bad(err, "bad head geometry (nc %d, nm %d, reg_max %d)", h.nc, nm, h.reg_max);
   for (int l = 0; l < h.nl; ++l)
     if (h.stride(l) < 1 || h.stride(l) > 64) return bad(err, "bad stride %d", h.stride(l));
-  if (task < 0 || task > kTaskPose) return bad(err, "unknown task %d (detect 0, segment 1, pose 2)", task);
+  if (task < 0 || task > kTaskClassify)
+    return bad(err, "unknown task %d (detect 0, segment 1, pose 2, classify 3)", task);
   if (want) {  // what the creator of the context expects (0 = any)
     if (want->task && want->task != task + 1)
       return bad(err, "blob task %s, context created for %s", ym_task_name(task), ym_task_name(want->task - 1));
@@ -135,7 +152,7 @@ int ym_plan_parse(const void* blob, size_t bytes, const ym_model_desc* want, Pla
     if (want->scale && h.scale && want->scale != h.scale)
       return bad(err, "blob scale '%c', context created for '%c'", (char)h.scale, (char)want->scale);
   }
-  if (h.input_buf < 0 || h.input_buf >= nbuf || h.anchor_buf < 0 || h.anchor_buf >= nbuf)
+  if (h.input_buf < 0 || h.input_buf >= nbuf || (cls ? h.anchor_buf != -1 : (h.anchor_buf < 0 || h.anchor_buf >= nbuf)))
     return bad(err, "bad input/anchor buffer ids");
   if (task == 1 && (h.proto_buf < 0 || h.proto_buf >= nbuf)) return bad(err, "segment plan without proto buffer");
   out.bufs.resize(nbuf);

@@ -30,17 +30,20 @@ constexpr int32_t kPlanMagic = 0x4C504D59;  // 'YMPL'
 constexpr int kBufRec = 8, kNameLen = 48;   // int32 words per buffer record, bytes per op name
 constexpr size_t kQRecBytes = 1088;         // sizeof(QRec) (ym_common.h)
 constexpr int kTaskPose = 2;
+constexpr int kTaskClassify = 3;  // (include/yolomi.h YM_TASK_CLASSIFY - 1)
+constexpr int kClsWidth = 1280;    // Classify's hidden width (csrc/ym_classify.h kClsHidden)
 constexpr int kMaxLevels = 3;  // the header has three stride slots
 
-enum OpKind { OP_INPUT = 1, OP_CONV = 2, OP_DW = 3, OP_SPPF = 4, OP_ATTN = 5, OP_DECODE = 6, OP_NMS = 7, OP_REQ = 8 };
+enum OpKind { OP_INPUT = 1, OP_CONV = 2, OP_DW = 3, OP_SPPF = 4, OP_ATTN = 5, OP_DECODE = 6, OP_NMS = 7, OP_REQ = 8,
+              OP_CLASSIFY = 9 };
 
 struct PlanHeader {
   // -- header fields begin
   int32_t magic;       // kPlanMagic
   int32_t version;     // 1
   int32_t dtype;       // YM_DT_*
-  int32_t task;        // 0 detect, 1 segment, 2 pose
-  int32_t nc;          // classes
+  int32_t task;        // 0 detect, 1 segment, 2 pose, 3 classify
+  int32_t nc;          // classes (classify plans: any count; others <= 128)
   int32_t nm;          // extras NMS carries per row (segment: 32 mask coefficients; pose: K * ndim padded to 4)
   int32_t reg_max;
   int32_t nl;          // head levels, <= kMaxLevels
@@ -52,7 +55,7 @@ struct PlanHeader {
   int32_t wbytes_lo;   // size of the weight section
   int32_t wbytes_hi;
   int32_t input_buf;
-  int32_t anchor_buf;
+  int32_t anchor_buf;  // (classify plans: -1)
   int32_t proto_buf;   // segment plans (-1 otherwise)
   int32_t no;          // offset of the nm extras in the anchor row
   int32_t scale;       // 'n', 's', ... (checked against ym_model_desc.scale; 0: unknown)
@@ -120,6 +123,9 @@ struct OpRec {
   int sppf_coff() const { return src0_coff; }
   int x3_wexp() const { return q_off; }
   int x3_wexp2() const { return sasw_off; }
+  // classify: the head conv in the conv slots (src0 view, n = kClsWidth, w_off / b_off / kpad, x3: q_off), the Linear
+  // in the fused-successor slots (w2_off [n2][kClsWidth] fp32, f16 plans fp16; b2_off fp32; n2 = nc, kpad2 = kClsWidth)
+  int cls_nc() const { return n2; }
   bool has_fused_dw() const { return biasi_off > 0; }  // (float plans)
   int32_t fused_dw_off() const { return biasi_off - 1; }
 };

@@ -30,6 +30,7 @@
 #include "ym_annot.h"
 #include "ym_contour.h"
 #include "ym_rle.h"
+#include "ym_classify.h"
 
 // process-wide debug switches (ym_set_debug; include/yolomi.h YM_DBG_*): set from the environment once, then only by
 // the setter — a launch reads an atomic instead of calling getenv (getenv per launch is not thread-safe
@@ -129,6 +130,15 @@ static_assert(sizeof(MlState) == kMlStateBytes, "ym_nms_ws.h sizes the multi-lab
 
 // What one launch_forward / launch_op call works on.  A value built per call (and per lane or branch stream inside
 // launch_forward), never context state: nothing is left to reset on an early return.
+// Where a ym_classify call's results go (null members: the context's own scratch, ym_ctx::cls_view)
+struct ClsOut {
+  float* probs = nullptr;
+  long long ld = 0;
+  float* logits = nullptr;
+  int* topk = nullptr;
+  float* topk_conf = nullptr;
+};
+
 struct Launch {
   int lane = 0;           // split-K slab / counter region of the stream the ops go to
   int img0 = 0;           // first image of the ops being launched (a lane's slice of the batch)
@@ -137,6 +147,7 @@ struct Launch {
   int stop = -1;          // ym_embed: the last op of the truncated forward (-1: a whole forward)
   bool pool = true;       // (stop >= 0) the embedding pooling stage follows; false: YM_DBG_STOP, a test's bare stop
   float* const* calib_raw = nullptr;  // ym_calibrate: per-op pre-activation output buffers (f32 plans)
+  ClsOut cls;             // ym_classify: the caller's outputs
 };
 
 struct GraphKey {
@@ -146,6 +157,7 @@ struct GraphKey {
   int embed_n;     // ... the views pooled behind it (GraphEntry::embed_views) ...
   const void* embed_out;  // ... and where their means go
   long long embed_ld;
+  ClsOut cls;  // ym_classify captures: the outputs the head's launches write
   const void* in;
   const void* dets;
   const void* counts;
@@ -262,6 +274,11 @@ struct ym_ctx {
   size_t arena_bytes = 0;
   std::vector<size_t> buf_off;
   size_t off_ctl = 0, off_slab = 0, off_cnt = 0, off_chain = 0, off_kpts = 0, slab_bytes = 0;
+  // classify plans: the head's op and its scratch in the arena — pooled (B, 1280), then logits, probs (B, nc each),
+  // top-k classes and probabilities (B, kClsTopK each), all fp32 / int32; a call's own outputs replace the last four
+  int cls_op = -1;
+  size_t off_cls = 0;
+  size_t cls_bytes(int nB) const { return (size_t)nB * (kClsHidden + 2 * (size_t)nc + 2 * kClsTopK) * 4; }
   int A = 0;
   // the NMS stage's scratch in the arena.  Multi-label mode (ym_infer_args.multi_label): its regions join at the first
   // workspace (re)build after a multi-label call was seen (check_call sets ml_want; nms.ml: they are there), so a
@@ -469,6 +486,8 @@ int ensure_workspace(ym_ctx* c, int B, int H, int W) {
   c->off_chain = off;  off = align_up(off + (size_t)kChainCtl * 4, 256);  // persistent chain kernel's counters
   c->off_kpts = off;  // pose plans: decoded keypoints (B, A, nm) fp32, the rows NMS takes its extras from
   if (c->task == kTaskPose) off = align_up(off + (size_t)nB * c->A * c->nm * 4, 256);
+  c->off_cls = off;
+  if (c->task == kTaskClassify) off = align_up(off + c->cls_bytes(nB), 256);
   c->arena_bytes = off;
   hipError_t e = hipMalloc(&c->d_arena, off);
   if (e != hipSuccess) {
@@ -817,6 +836,30 @@ int launch_op(ym_ctx* c, const Launch& L, const Op& op, int B, const float* d_in
       e = launch_nms_stage(v, src, args, B, c->nc, c->nm, c->cH, c->cW, d_dets, d_counts, counts2, st);
       break;
     }
+    case OP_CLASSIFY: {
+      ClsArgs a{};
+      const int bs = op.src0;
+      a.x = c->bptr(bs, L.img0); a.ctot = c->bufs[bs].C; a.coff = op.src0_coff; a.C1 = op.c0; a.P = c->buf_P(bs);
+      a.w = c->wptr<char>(op.w_off); a.bias = c->wptr<float>(op.b_off); a.kpad = op.kpad;
+      a.wsc = dt == YM_DT_X3 ? ldexpf(1.0f, -op.x3_wexp()) : 1.0f;
+      a.lw = c->wptr<char>(op.w2_off); a.lb = c->wptr<float>(op.b2_off);
+      a.nc = c->nc; a.B = B; a.k = c->nc < kClsTopK ? c->nc : kClsTopK;
+      // the scratch rows of the whole batch (cB images), this launch's images from img0 on
+      float* f = reinterpret_cast<float*>(c->d_arena + c->off_cls);
+      const size_t nB = (size_t)c->cB, i0 = (size_t)L.img0, nc = (size_t)c->nc;
+      a.pooled = f + i0 * kClsHidden;
+      f += nB * kClsHidden;
+      a.logits = L.cls.logits ? L.cls.logits + i0 * nc : f + i0 * nc;
+      f += nB * nc;
+      a.probs = L.cls.probs ? L.cls.probs + i0 * L.cls.ld : f + i0 * nc;
+      a.ld = L.cls.probs ? (long)L.cls.ld : (long)nc;
+      f += nB * nc;
+      a.topk = L.cls.topk ? L.cls.topk + i0 * a.k : reinterpret_cast<int*>(f) + i0 * a.k;
+      f += nB * kClsTopK;
+      a.topk_conf = L.cls.topk_conf ? L.cls.topk_conf + i0 * a.k : f + i0 * a.k;
+      e = ym_launch_classify(dt, a, st);
+      break;
+    }
     default:
       return fail(YM_EBLOB, "unknown op kind %d", op.kind);
   }
@@ -1044,6 +1087,13 @@ int ym_load_weights(ym_ctx* c, const void* blob, size_t bytes) {
   const int dtype = h.dtype;
   const bool pose = h.task == kTaskPose;
   const size_t woff = plan.woff, wbytes = plan.wbytes;
+  if (h.task == kTaskClassify) {  // exactly one head, behind every other op; its x3 weight exponent in ldexpf's range
+    int heads = 0;
+    for (const Op& o : plan.ops) heads += o.kind == OP_CLASSIFY;
+    const Op& last = plan.ops.back();
+    if (heads != 1 || last.kind != OP_CLASSIFY || (dtype == YM_DT_X3 && (last.x3_wexp() < -64 || last.x3_wexp() > 64)))
+      return fail(YM_EBLOB, "classify plan: one classify op, the last, with |x3 exponent| <= 64");
+  }
   // commit: a reload drops the previous plan's workspace, graphs and per-shape tile tables (they index its ops and
   // buffers); the weights are replaced below
   c->loaded = false;
@@ -1063,6 +1113,9 @@ int ym_load_weights(ym_ctx* c, const void* blob, size_t bytes) {
   c->kpt_off = pose ? h.kpt_off : 0;
   c->bufs = std::move(plan.bufs);
   c->ops = std::move(plan.ops);
+  c->cls_op = -1;
+  for (size_t i = 0; i < c->ops.size(); ++i)
+    if (c->ops[i].kind == OP_CLASSIFY) c->cls_op = (int)i;
   c->blob_host.assign(static_cast<const char*>(blob), static_cast<const char*>(blob) + bytes);  // ym_broadcast_weights
   build_schedule(c);
   while (c->op_ev.size() < c->ops.size()) {
@@ -1309,13 +1362,14 @@ static int begin_launch(ym_ctx* c, int B, int H, int W, hipStream_t st, Launch& 
 
 // ym_infer, (skip_nms) ym_tta_forward and (stop >= 0) ym_embed
 static int infer_impl(ym_ctx* c, const float* d_in, int B, int H, int W, const ym_infer_args* args, float* d_dets,
-                      int* d_counts, void* stream, bool skip_nms, int stop) {
+                      int* d_counts, void* stream, bool skip_nms, int stop, const ClsOut* cls = nullptr) {
   int rc = check_call(c, d_in, B, H, W, args, d_dets, d_counts);
   if (rc) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   Launch L;
   if ((rc = begin_launch(c, B, H, W, st, L))) return rc;
   L.skip_nms = skip_nms; L.stop = stop;
+  if (cls) L.cls = *cls;
   // YM_DBG_STOP (tests): an eager forward that ends behind op value - 1, every op its own launch as ym_embed's
   // truncated forward but with no pooling stage.  Never captured: a stopped forward must not be cached as, or
   // replayed for, a whole one
@@ -1336,6 +1390,7 @@ static int infer_impl(ym_ctx* c, const float* d_in, int B, int H, int W, const y
   memset(&key, 0, sizeof(key));
   key.B = B; key.H = H; key.W = W; key.in = d_in; key.dets = nullptr; key.counts = d_counts; key.args = *args;
   key.skip_nms = L.skip_nms ? 1 : 0;
+  key.cls = L.cls;
   const bool embed = L.stop >= 0;
   if (embed) {
     key.embed_stop = L.stop + 1;
@@ -1389,7 +1444,28 @@ static int infer_impl(ym_ctx* c, const float* d_in, int B, int H, int W, const y
 
 int ym_infer(ym_ctx* c, const float* d_in, int B, int H, int W, const ym_infer_args* args, float* d_dets,
              int* d_counts, void* stream) {
+  if (c && c->loaded && c->task == kTaskClassify)
+    return fail(YM_EINVAL, "ym_infer: a classify plan has no detections (ym_classify runs it)");
   return infer_impl(c, d_in, B, H, W, args, d_dets, d_counts, stream, false, -1);
+}
+
+// ---------------------------------------------------------------------------------- classification
+int ym_classify(ym_ctx* c, const float* d_in, int B, int H, int W, const ym_infer_args* args, float* d_probs, int ld,
+                float* d_logits, int* d_topk, float* d_topk_conf, void* stream) {
+  if (!c) return fail(YM_EINVAL, "null context");
+  if (!c->loaded) return fail(YM_ESTATE, "ym_classify before ym_load_weights");
+  if (c->task != kTaskClassify)
+    return fail(YM_EINVAL, "ym_classify: the loaded plan is a %s plan, not a classify plan", ym_task_name(c->task));
+  if (!d_in || !args || !d_probs || !d_topk || !d_topk_conf) return fail(YM_EINVAL, "null pointer argument");
+  if (ld < c->nc) return fail(YM_EINVAL, "ym_classify: row stride %d below the %d classes", ld, c->nc);
+  // what reaches the forward: the /255 rule's inputs and the launch mode; one lane; no detection output is written
+  ym_infer_args fa{};
+  fa.conf = 0.25f; fa.max_wh = 7680.f; fa.iou = 0.7; fa.max_det = 300; fa.max_nms = 30000;
+  fa.in_eps = args->in_eps; fa.use_graph = args->use_graph; fa.lanes = 1; fa.d_batch_max = args->d_batch_max;
+  ClsOut out;
+  out.probs = d_probs; out.ld = ld; out.logits = d_logits; out.topk = d_topk; out.topk_conf = d_topk_conf;
+  float* nodets = reinterpret_cast<float*>(c->d_misc + kMiscNoDets);
+  return infer_impl(c, d_in, B, H, W, &fa, nodets, reinterpret_cast<int*>(nodets), stream, false, -1, &out);
 }
 
 // ---------------------------------------------------------------------------------- test-time augmentation
@@ -1674,7 +1750,7 @@ int ym_profile_replay(ym_ctx* c, const float* d_in, int B, int H, int W, const y
     const int k = op.kind;
     op_ms[i] = -1.f;
     // input (resets counters), decode (appends candidates) and NMS (consumes them) are not idempotent: skipped
-    if (k != OP_CONV && k != OP_DW && k != OP_SPPF && k != OP_ATTN) continue;
+    if (k != OP_CONV && k != OP_DW && k != OP_SPPF && k != OP_ATTN && k != OP_CLASSIFY) continue;
     int lrc = YM_OK;
     float ms = 0.f;
     auto launch = [&](hipStream_t s) { return launch_op(c, L, op, B, d_in, args, d_dets, d_counts, s); };
@@ -1839,6 +1915,10 @@ int ym_read_scratch(ym_ctx* c, int which, void* dst, size_t bytes) {
     case YM_SCRATCH_KPTS:
       if (c->task != kTaskPose) return fail(YM_ESTATE, "YM_SCRATCH_KPTS needs a pose plan");
       off = c->off_kpts; cap = (size_t)c->cB * c->A * c->nm * 4;
+      break;
+    case YM_SCRATCH_POOLED:
+      if (c->task != kTaskClassify) return fail(YM_ESTATE, "YM_SCRATCH_POOLED needs a classify plan");
+      off = c->off_cls; cap = (size_t)c->cB * kClsHidden * 4;
       break;
     default: return fail(YM_EINVAL, "unknown scratch region %d", which);
   }

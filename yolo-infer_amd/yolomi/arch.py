@@ -34,6 +34,8 @@ SCALES = {
 }
 
 NC = 80
+NC_CLASSIFY = 1000  # yolo11-cls.yaml's nc (ImageNet)
+CLS_HIDDEN = 1280   # Classify's hidden width c_: fixed, not scaled by the model size (csrc/ym_classify.h kClsHidden)
 REG_MAX = 16
 STRIDES = (8, 16, 32)
 
@@ -102,10 +104,12 @@ class GraphBuilder:
         plan the GPU runs pads them (Detect)."""
         if scale not in SCALES:
             raise ValueError(f"Unsupported size: {scale}")
-        if task not in ("detect", "segment", "pose"):
-            raise ValueError(f"task {task!r} has no HIP plan (supported: detect, segment, pose)")
+        if task not in ("detect", "segment", "pose", "classify"):
+            raise ValueError(f"task {task!r} has no HIP plan (supported: detect, segment, pose, classify)")
         if nc is None:
-            nc = 1 if task == "pose" else NC
+            nc = 1 if task == "pose" else (NC_CLASSIFY if task == "classify" else NC)
+        if task == "classify" and (quant or nc < 1):
+            raise ValueError("classify plans are x3 / f16 / f32 with nc >= 1: there is no PTQ classify plan")
         self.scale, self.task, self.nc, self.quant = scale, task, nc, quant
         self.kpt_shape = (int(kpt_shape[0]), int(kpt_shape[1])) if task == "pose" else None
         if task == "pose" and (self.kpt_shape[0] < 1 or self.kpt_shape[1] not in (2, 3)
@@ -286,6 +290,20 @@ class GraphBuilder:
         self.conv(f"model.{i}.cv2", View(cv1, 0, c), c2, 1, 1, self.full(out), src1=b, catq=f"model.{i}.cat")
         return self.full(out)
 
+    def Classify(self, i: int, x: View):
+        """Ultralytics Classify: Conv(c1, 1280, 1) -> AdaptiveAvgPool2d(1) -> Linear(1280, nc) (-> softmax) as ONE op of
+        kind `classify` (csrc/ym_classify.hip): the 1280-channel map is never a buffer.  Its results leave the plan
+        (ym_classify's outputs), so the op has no dst."""
+        p = f"model.{i}"
+        self._conv_params(p + ".conv", x.C, CLS_HIDDEN, 1)
+        self.params.append(Param(p + ".linear.weight", (self.nc, CLS_HIDDEN), "linear_w"))
+        self.params.append(Param(p + ".linear.bias", (self.nc,), "linear_b"))
+        self.ops.append(Op("classify", dict(c1=x.C, c2=CLS_HIDDEN, nc=self.nc, src=x, wkey=p + ".conv", bn=True,
+                                            lkey=p + ".linear"), p))
+        self.flops_per_pixel.append((p + ".conv", x.buf.f, x.C * CLS_HIDDEN))
+        self.no, self.nm, self.kpt_off = 0, 0, -1
+        self.anchor_buf = None
+
     def Detect(self, i: int, xs: List[View]):
         nc = self.nc
         pose = self.task == "pose"
@@ -390,6 +408,11 @@ class GraphBuilder:
         L6 = self.C3k2(6, L5, ch(512), 2, True, 0.5)
         L7 = self.Conv(7, L6, ch(1024), 3, 2)
         L8 = self.C3k2(8, L7, ch(1024), 2, True, 0.5)
+        if self.task == "classify":  # yolo11-cls.yaml: the backbone without SPPF, C2PSA as layer 9, Classify as 10
+            L9 = self.C2PSA(9, L8, ch(1024), 2)
+            self.Classify(10, L9)
+            self.layers = {0: [L0], 1: [L1], 2: [L2], 3: [L3], 4: [L4], 5: [L5], 6: [L6], 7: [L7], 8: [L8], 9: [L9]}
+            return
         L9 = self.SPPF(9, L8, ch(1024))
         L10 = self.C2PSA(10, L9, ch(1024), 2)
         # 11 Upsample + 12 Concat[-1, 6] fold into layer 13's cv1 (two-source A loader, first source up-sampled)
@@ -447,7 +470,7 @@ class GraphBuilder:
         n = 0
         for op in self.ops:
             a = op.args
-            views = [a.get(k) for k in ("src0", "src1", "res", "src", "qkv")]
+            views = [a.get(k) for k in ("src0", "src1", "res", "src", "qkv")]  # (src: depthwise, SPPF, classify)
             n += sum(1 for v in views if isinstance(v, View) and v.buf is buf)
             if op.kind == "sppf" and a["dst"] is buf:
                 n += 1
@@ -624,6 +647,12 @@ class GraphBuilder:
             elif op.kind == "decode":
                 A = sum((H // s) * (W // s) for s in STRIDES)
                 by = B * A * (a["anchor"].C * 4 + 24)
+            elif op.kind == "classify":  # layer 9 read once, both weight matrices, the (B, nc) probabilities written
+                f = a["src"].buf.f
+                npx = B * (H // f) * (W // f)
+                fl = 2 * (npx * a["c1"] * a["c2"] + B * a["c2"] * a["nc"])
+                by = npx * a["c1"] * act_bytes + a["c1"] * a["c2"] * act_bytes + a["c2"] * 4 + a["c2"] * a["nc"] * 4 \
+                    + a["nc"] * 4 + B * a["nc"] * 4
             out.append((fl, by))
         return out
 
@@ -647,6 +676,9 @@ class GraphBuilder:
                 f = a["qkv"].buf.f
                 N = (H // f) * (W // f)
                 tot += N * N * a["nh"] * (a["kd"] + a["hd"]) + N * 9 * a["C"]
+            elif op.kind == "classify":
+                f = a["src"].buf.f
+                tot += (H // f) * (W // f) * a["c1"] * a["c2"] + a["c2"] * a["nc"]
         return tot
 
     def out_factor(self, op: Op) -> int:
@@ -661,10 +693,10 @@ EMBED_LAYERS = 23  # model.0 .. model.22; model.23 is the head
 DEFAULT_EMBED = (EMBED_LAYERS - 1,)  # Model.embed's default, len(model.model) - 2: the last neck C3k2
 
 
-def normalize_embed(layers) -> Tuple[int, ...]:
+def normalize_embed(layers, n_layers: int = EMBED_LAYERS) -> Tuple[int, ...]:
     """predict(embed=...) indices as _predict_once uses them: a set, ascending.  A bare int is one layer.  Unlike
-    upstream (which silently ignores an index no layer has), an index outside 0..22, a non-integer or an empty list
-    is a ValueError."""
+    upstream (which silently ignores an index no layer has), an index outside 0..22 (n_layers - 1: a classify graph
+    has layers 0..9), a non-integer or an empty list is a ValueError."""
     import operator
     if isinstance(layers, (str, bytes)) or isinstance(layers, bool):
         raise ValueError(f"embed: expected layer indices, got {layers!r}")
@@ -678,8 +710,8 @@ def normalize_embed(layers) -> Tuple[int, ...]:
             i = operator.index(v)
         except TypeError:
             raise ValueError(f"embed: layer index {v!r} is not an integer") from None
-        if not 0 <= i < EMBED_LAYERS:
-            raise ValueError(f"embed: layer index {i} is outside 0..{EMBED_LAYERS - 1}")
+        if not 0 <= i < n_layers:
+            raise ValueError(f"embed: layer index {i} is outside 0..{n_layers - 1}")
         out.add(i)
     if not out:
         raise ValueError("embed: no layer given")
@@ -715,6 +747,14 @@ def infer_arch(sd, kpt_shape: Optional[Tuple[int, int]] = None) -> Tuple[str, st
     task comes from the Proto keys (segment) or cv4 without Proto (pose; its kpt_shape: infer_kpt_shape), nc from the
     last cls conv, the scale from the graph whose every parameter shape matches."""
     import numpy as np
+    if "model.10.linear.weight" in sd:  # a yolo11-cls checkpoint: nc is the Linear's row count
+        nc = int(np.shape(sd["model.10.linear.weight"])[0])
+        for scale in SCALES:
+            g = GraphBuilder(scale, "classify", nc=nc)
+            if all(p.kind == "count" or (p.name in sd and tuple(np.shape(sd[p.name])) == tuple(p.shape))
+                   for p in g.params):
+                return scale, "classify", nc
+        raise ValueError(f"state dict matches no YOLO11 scale ({'/'.join(SCALES)}) for task classify, nc={nc}")
     task = "segment" if any(k.startswith("model.23.proto.") for k in sd) else "detect"
     if task == "detect" and any(k.startswith("model.23.cv4.") for k in sd):
         task = "pose"

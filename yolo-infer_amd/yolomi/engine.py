@@ -38,8 +38,8 @@ class Engine:
         self.scale, self.task, self.dtype = scale, task, dtype
         self.device = device
         self.qparams = qparams
-        if task == "pose" and dtype in QUANT_DTYPES:
-            raise ValueError(f"pose plans are x3 / f16 / f32: there is no PTQ pose plan (dtype {dtype!r})")
+        if task in ("pose", "classify") and dtype in QUANT_DTYPES:
+            raise ValueError(f"{task} plans are x3 / f16 / f32: there is no PTQ {task} plan (dtype {dtype!r})")
         self.graph = GraphBuilder(scale, task, nc=nc, quant=dtype in QUANT_DTYPES,
                                   fuse=fuse_default(dtype), **(dict(kpt_shape=kpt_shape) if kpt_shape else {}))
         dev_index = device.index if device.index is not None else torch.cuda.current_device()
@@ -75,6 +75,8 @@ class Engine:
         self._embed_tables = {}    # embed: layer tuple -> (ym_embed view table, total channels)
         self._embed_out = {}       # (B, layer tuple) -> the engine-owned (B, sum C) result
         self._embed_scratch = None  # rows / counts a tuning run of an embed-first shape may write
+        self._cls_out = {}         # classify: B -> the engine-owned (probs, topk, topk_conf)
+        self.logits = None         # classify: an optional (>= B, nc) fp32 tensor the Linear's outputs also go to (tests)
         self._trackers = {}        # track: (B, cfg items, capacity) -> yolomi.lib.Tracker
         self._live_tracker = None  # the key of the tracker the last track() call advanced
         self.tune_source: Dict[tuple, str] = {}
@@ -354,7 +356,7 @@ class Engine:
         return out
 
     def embed_layers(self):
-        """Layer indices (0..22) whose outputs this plan stores, i.e. the ones embed() can pool.  A plan with fused
+        """Layer indices (0..22; a classify plan: 0..9) whose outputs this plan stores, i.e. the ones embed() can pool.  A plan with fused
         conv pairs never writes the first conv's output (x3 / f16: model.1 runs inside model.2.cv1's launch)."""
         return self.graph.embed_layers()
 
@@ -380,9 +382,10 @@ class Engine:
         call).  Asynchronous on the current stream; in steady state nothing is allocated.
         ValueError: an index outside 0..22, a non-integer, an empty list, a layer this plan does not store, or a
         quantized plan."""
-        from .arch import DEFAULT_EMBED, normalize_embed
+        from .arch import normalize_embed
         in_eps, _, bm = self._check_input(x, in_eps, 1, batch_max)
-        layers = normalize_embed(DEFAULT_EMBED if layers is None else layers)
+        n_layers = len(self.graph.layers)  # 23, or a classify graph's 10; the default is upstream's len(model) - 2
+        layers = normalize_embed((n_layers - 1,) if layers is None else layers, n_layers)
         views, width = self._embed_table(layers)
         B, _, H, W = x.shape
         if out is None:
@@ -396,14 +399,64 @@ class Engine:
         args = self._args_cache.get(akey) or self._cache_args(akey, Runtime.make_args(
             in_eps=in_eps, use_graph=use_graph, lanes=1, batch_max_ptr=bm))
         stream = self._stream()
-        if (B, H, W) not in self._tuned:  # the conv tile table of the shape, as run() takes it (one lane)
+        self._ready_headless(x, B, H, W, args, stream)
+        self.rt.embed(x.data_ptr(), B, H, W, args, views, out.data_ptr(), out.stride(0), stream)
+        return out[:B, :width]
+
+    def _ready_headless(self, x, B, H, W, args, stream):
+        """_ready for the calls that write no detections (embed, classify): the conv tile table of the shape, as run()
+        takes it (one lane); a measuring run may write the scratch rows here, never outputs()'s buffers."""
+        if (B, H, W) not in self._tuned:
             if self._embed_scratch is None or self._embed_scratch[0].shape[0] < B:
                 self._embed_scratch = (torch.zeros((B, args.max_det, 6 + self.nm), dtype=torch.float32,
                                                    device=self.device),
                                        torch.zeros((B,), dtype=torch.int32, device=self.device))
-            self._ready(x, B, H, W, args, stream, *self._embed_scratch)  # (outputs()'s buffers are not touched)
-        self.rt.embed(x.data_ptr(), B, H, W, args, views, out.data_ptr(), out.stride(0), stream)
-        return out[:B, :width]
+            self._ready(x, B, H, W, args, stream, *self._embed_scratch)
+
+    def classify(self, x: torch.Tensor, out: Optional[tuple] = None, in_eps=None, use_graph=True,
+                 batch_max: Optional[torch.Tensor] = None):
+        """Classification (classify plans; csrc/ym_classify.hip): (probs (B, nc) fp32, topk (B, k) int32, topk_conf
+        (B, k) fp32) on the device, k = min(5, nc): the softmax of every image, its k most probable classes in
+        descending order (equal probabilities: the lower class first) and their probabilities.  x, in_eps, batch_max,
+        use_graph as run().  out: the caller's three tensors of those shapes and dtypes, contiguous (default:
+        engine-owned ones per B, overwritten by the next call).  When `self.logits` is set to a contiguous (>= B, nc)
+        fp32 device tensor the Linear's outputs are written there as well.  Asynchronous on the current stream: nothing
+        is read on the host, and in steady state nothing is allocated."""
+        if self.task != "classify":
+            raise ValueError(f"classify() needs a classify plan (this engine holds a {self.task} plan)")
+        in_eps, _, bm = self._check_input(x, in_eps, 1, batch_max)
+        B, _, H, W = x.shape
+        nc = self.graph.nc
+        k = min(5, nc)
+        if out is None:
+            out = self._cls_out.get(B)
+            if out is None:
+                out = self._cls_out[B] = (torch.empty((B, nc), dtype=torch.float32, device=self.device),
+                                          torch.empty((B, k), dtype=torch.int32, device=self.device),
+                                          torch.empty((B, k), dtype=torch.float32, device=self.device))
+        probs, topk, conf = out
+        for t, shape, dt in ((probs, (B, nc), torch.float32), (topk, (B, k), torch.int32), (conf, (B, k), torch.float32)):
+            assert t.is_cuda and t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous()
+        lg = self.logits
+        if lg is not None:
+            assert (lg.is_cuda and lg.dtype == torch.float32 and lg.is_contiguous() and lg.dim() == 2
+                    and lg.shape[0] >= B and lg.shape[1] == nc)
+        akey = ("classify", in_eps, use_graph, bm)
+        args = self._args_cache.get(akey) or self._cache_args(akey, Runtime.make_args(
+            in_eps=in_eps, use_graph=use_graph, lanes=1, batch_max_ptr=bm))
+        stream = self._stream()
+        self._ready_headless(x, B, H, W, args, stream)
+        self.rt.classify(x.data_ptr(), B, H, W, args, probs.data_ptr(), nc, lg.data_ptr() if lg is not None else 0,
+                         topk.data_ptr(), conf.data_ptr(), stream)
+        return probs, topk, conf
+
+    def pooled(self, B: int) -> torch.Tensor:
+        """Classify plans: the (B, 1280) pooled vectors of the last classify() — the Linear's input — as a CPU tensor
+        (tests); synchronous."""
+        from .lib import SCRATCH_POOLED
+        out = torch.empty((B, 1280), dtype=torch.float32)
+        self.rt.read_scratch(SCRATCH_POOLED, out.data_ptr(), out.numel() * 4)
+        return out
 
     def set_names(self, names: Dict[int, str]):
         """The class names annotate() writes into labels (YOLO11Model hands in its own)."""

@@ -24,8 +24,8 @@ class ModelDesc(C.Structure):
                 ("dtype", C.c_int), ("reserved", C.c_int * 2)]
 
 
-TASK_CODES = {"detect": 1, "segment": 2, "pose": 3}
-SCRATCH_KEYS, SCRATCH_COUNTS, SCRATCH_KPTS = 0, 1, 2  # ym_read_scratch regions (include/yolomi.h)
+TASK_CODES = {"detect": 1, "segment": 2, "pose": 3, "classify": 4}
+SCRATCH_KEYS, SCRATCH_COUNTS, SCRATCH_KPTS, SCRATCH_POOLED = 0, 1, 2, 3  # ym_read_scratch regions (include/yolomi.h)
 DTYPE_CODES = {"f16": 1, "f32": 2, "i8": 3, "f8": 4, "x3": 5}
 
 
@@ -110,6 +110,7 @@ def load_library(path: os.PathLike = LIB_PATH):
         "ym_tta_nms": (I, [C.POINTER(P), I, I, I, C.POINTER(InferArgs), P, P, P]),
         "ym_tta_counts": (I, [P, C.POINTER(I), I]),
         "ym_embed": (I, [P, P, I, I, I, C.POINTER(InferArgs), C.POINTER(EmbedView), I, P, C.c_longlong, P]),
+        "ym_classify": (I, [P, P, I, I, I, C.POINTER(InferArgs), P, I, P, P, P, P]),
         "ym_track_create": (I, [P, I, C.POINTER(TrackCfg), C.POINTER(P)]),
         "ym_track_destroy": (None, [P]),
         "ym_track_reset": (I, [P, P]),
@@ -145,7 +146,7 @@ EXPORTED = ("ym_create", "ym_load_weights", "ym_broadcast_weights", "ym_broadcas
             "ym_op_name",
             "ym_num_buffers", "ym_buffer_info", "ym_read_buffer", "ym_sync", "ym_last_error", "ym_destroy",
             "ym_version", "ym_num_conv_cfgs", "ym_set_debug", "ym_read_scratch", "ym_kpt_shape",
-            "ym_tta_shape", "ym_tta_scale", "ym_tta_forward", "ym_tta_nms", "ym_tta_counts", "ym_embed",
+            "ym_tta_shape", "ym_tta_scale", "ym_tta_forward", "ym_tta_nms", "ym_tta_counts", "ym_embed", "ym_classify",
             "ym_track_create", "ym_track_destroy", "ym_track_reset", "ym_track_update", "ym_track_read_state", "ym_annotate",
             "ym_mask_contours", "ym_mask_rle")
 
@@ -298,6 +299,14 @@ class Runtime:
         """ym_embed: the forward up to the last named buffer, then the pooled means into (B, out_stride) floats."""
         _check(self.lib.ym_embed(self.ctx, C.c_void_p(x_ptr), B, H, W, C.byref(args), views, len(views),
                                  C.c_void_p(out_ptr), out_stride, C.c_void_p(stream)))
+
+    def classify(self, x_ptr: int, B: int, H: int, W: int, args: InferArgs, probs_ptr: int, ld: int, logits_ptr: int,
+                 topk_ptr: int, conf_ptr: int, stream: int):
+        """ym_classify: the classify plan's forward and head; probabilities into (B, ld) floats, the min(5, nc) best
+        classes and their probabilities into (B, k) rows, the Linear's outputs into (B, nc) floats when logits_ptr."""
+        V = C.c_void_p
+        _check(self.lib.ym_classify(self.ctx, V(x_ptr), B, H, W, C.byref(args), V(probs_ptr), ld, V(logits_ptr or None),
+                                    V(topk_ptr), V(conf_ptr), V(stream)))
 
     @staticmethod
     def annotate_args(line_width, kpt_radius, flags, color_mode, tracked, det_stride, K, ndim, nc, mask_cap,

@@ -33,7 +33,9 @@ from .arch import REG_MAX, STRIDES, GraphBuilder
 
 MAGIC = 0x4C504D59
 VERSION = 1
-OP_IDS = {"input": 1, "conv": 2, "dwconv": 3, "sppf": 4, "attn": 5, "decode": 6, "nms": 7, "requant": 8}
+OP_IDS = {"input": 1, "conv": 2, "dwconv": 3, "sppf": 4, "attn": 5, "decode": 6, "nms": 7, "requant": 8,
+          "classify": 9}
+TASK_IDS = {"detect": 0, "segment": 1, "pose": 2, "classify": 3}
 DTYPES = {"f16": 0, "f32": 1, "i8": 2, "f8": 3, "x3": 4}
 QUANT_DTYPES = ("i8", "f8")  # one-byte PTQ plans: int8 affine (torch.ao qconfig) and fp8 e4m3 (yolomi/quant.py)
 BK = 64  # conv K is padded to the kernel K step (csrc/ym_conv.hip KSTEP)
@@ -189,6 +191,8 @@ def pack_graph(g: GraphBuilder, sd: Dict[str, np.ndarray], dtype: str = "f16", q
     if quant != bool(g.quant):
         raise ValueError("int8/fp8 blobs need GraphBuilder(quant=True), float blobs quant=False")
     pose = g.task == "pose"
+    if g.task == "classify" and quant:
+        raise ValueError(f"classify plans are x3 / f16 / f32: there is no PTQ classify plan (dtype {dtype!r})")
     if pose and quant:
         raise ValueError(f"pose plans are x3 / f16 / f32: there is no PTQ pose plan (dtype {dtype!r})")
     if pose and not g.pad_head:
@@ -347,6 +351,28 @@ def pack_graph(g: GraphBuilder, sd: Dict[str, np.ndarray], dtype: str = "f16", q
                 r["sasw_off"] = arena.add((np.float32(s_in) * sw).astype(np.float32))
             else:
                 r.update(w_off=arena.add(w9), b_off=arena.add(b))
+        elif op.kind == "classify":
+            # the head conv BN-folded in the plan's operand format, in the conv slots; the Linear in the fused-successor
+            # slots, fp32 (f16 plans: fp16 weights, fp32 bias).  No K padding beyond the kernel's 64-deep stages
+            w, b = _conv_weights(a, sd)  # (1280, 1, 1, c1)
+            N, K = w.shape[0], w.shape[3]
+            src = a["src"]
+            assert K == src.C and K % BK == 0, (K, src.C)
+            wp = w.reshape(N, K)
+            Kpad = K
+            if dtype == "x3":
+                ws = x3_weight_exp(wp)
+                wp, Kpad = x3_pair_rows(wp, ws), 2 * K
+                r["q_off"] = ws
+            r.update(k=1, s=1, cin=K, n=N, act=1, src0=src.buf.id, src0_coff=src.coff, c0=K, src1=-1, dst=-1, level=-1,
+                     res=-1)
+            r["w_off"] = arena.add(wp if wp.dtype == np.float16 else wp.astype(np_dt))
+            r["b_off"] = arena.add(b.astype(np.float32))
+            r["kpad"] = Kpad
+            lw = sd[a["lkey"] + ".weight"].astype(np.float32)
+            r["w2_off"] = arena.add(lw.astype(np.float16) if dtype == "f16" else lw)
+            r["b2_off"] = arena.add(sd[a["lkey"] + ".bias"].astype(np.float32))
+            r.update(n2=lw.shape[0], kpad2=lw.shape[1])
         elif op.kind == "requant":
             src, dst = a["src"], a["dst"]
             r.update(cin=dst.C, src0=src.buf.id, src0_coff=src.coff, up0=int(bool(a["up"])))
@@ -362,10 +388,10 @@ def pack_graph(g: GraphBuilder, sd: Dict[str, np.ndarray], dtype: str = "f16", q
     wbytes = arena.bytes()
     assert len(STRIDES) == 3  # the header's stride slots
     hdr = Header(
-        magic=MAGIC, version=VERSION, dtype=DTYPES[dtype], task={"detect": 0, "segment": 1, "pose": 2}[g.task],
+        magic=MAGIC, version=VERSION, dtype=DTYPES[dtype], task=TASK_IDS[g.task],
         nc=g.nc, nm=g.nm, reg_max=REG_MAX, nl=len(STRIDES), stride0=STRIDES[0], stride1=STRIDES[1], stride2=STRIDES[2],
         nbuf=len(g.buffers), nop=len(g.ops), wbytes_lo=len(wbytes) & 0xFFFFFFFF, wbytes_hi=len(wbytes) >> 32,
-        input_buf=g.input.id, anchor_buf=g.anchor_buf.id, proto_buf=g.proto_buf.id if g.task == "segment" else -1,
+        input_buf=g.input.id, anchor_buf=g.anchor_buf.id if g.anchor_buf is not None else -1, proto_buf=g.proto_buf.id if g.task == "segment" else -1,
         no=g.no, scale=ord(g.scale))  # (scale: checked against ym_model_desc.scale)
     if pose:  # nm = nk_pad, the extras NMS carries
         hdr = hdr._replace(kpt_k=g.kpt_shape[0], kpt_ndim=g.kpt_shape[1], kpt_off=g.kpt_off, cls_pad=g.no - 4 * REG_MAX)

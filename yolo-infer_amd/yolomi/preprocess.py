@@ -98,6 +98,34 @@ def letterbox_batch(rt, imgs: Sequence[np.ndarray], device: torch.device, imgsz:
     return out, [im.shape[:2] for im in imgs]
 
 
+def classify_geometry(h: int, w: int, imgsz: int = 224) -> Tuple[int, int, int, int]:
+    """Upstream classify_transforms' geometry for an h x w image: (rh, rw, top, left) — torchvision Resize(imgsz) puts
+    the shorter side at imgsz and the longer at int(imgsz * long / short); CenterCrop(imgsz) then starts at
+    int(round((rh - imgsz) / 2.0)) and likewise for the columns."""
+    if h <= w:
+        rh, rw = imgsz, int(imgsz * w / h)
+    else:
+        rh, rw = int(imgsz * h / w), imgsz
+    return rh, rw, int(round((rh - imgsz) / 2.0)), int(round((rw - imgsz) / 2.0))
+
+
+def classify_batch(imgs: Sequence[np.ndarray], imgsz: int = 224) -> torch.Tensor:
+    """Upstream classify_transforms on the host, with Pillow as upstream itself uses there: every HWC uint8 BGR image
+    to RGB, Resize(imgsz) with Image.BILINEAR, CenterCrop(imgsz), ToTensor (/255), Normalize(mean 0, std 1: the
+    identity).  Returns the (B, 3, imgsz, imgsz) fp32 CPU batch; imgsz must be a multiple of 32, as the plan's strides
+    ask."""
+    from PIL import Image
+    if imgsz < 32 or imgsz % 32:
+        raise ValueError(f"classify: imgsz {imgsz} must be a positive multiple of 32")
+    out = np.empty((len(imgs), 3, imgsz, imgsz), dtype=np.float32)
+    for i, im in enumerate(imgs):
+        rh, rw, top, left = classify_geometry(im.shape[0], im.shape[1], imgsz)
+        pil = Image.fromarray(np.ascontiguousarray(im[..., ::-1])).resize((rw, rh), Image.BILINEAR)
+        rgb = np.asarray(pil.crop((left, top, left + imgsz, top + imgsz)), dtype=np.uint8)
+        out[i] = rgb.transpose(2, 0, 1).astype(np.float32) / np.float32(255.0)
+    return torch.from_numpy(out)
+
+
 def scale_coords(img1_shape, coords: torch.Tensor, img0_shape) -> torch.Tensor:
     """ops.scale_coords(img1_shape, coords, img0_shape) (padding=True) + clip_coords, in place on a (..., >=2) tensor
     of x, y[, visibility] (Pose keypoints): the same gain / pad as scale_boxes, x clipped to [0, w0], y to [0, h0]."""

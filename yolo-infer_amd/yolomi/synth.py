@@ -61,6 +61,11 @@ def normal(seed: int, n: int) -> np.ndarray:
 # through the whole graph and roughly 20-60 anchors per image clear conf=0.25 on U[0,1) images.
 CLS_BIAS_SHIFT = {"n": 6.0, "s": 6.0, "m": 6.0, "l": 6.0, "x": 6.0}
 CONV_GAIN = 1.6
+# Classify's Linear(1280, nc): w ~ N(0, (LINEAR_GAIN / sqrt(1280))^2).  The pooled vector of a U[0,1) image has a root
+# mean square of ~0.22 (means of SiLU outputs), so the logits' standard deviation across classes is ~0.22 LINEAR_GAIN
+# = 0.7: the softmax is neither flat nor saturated.  3.25 is the value at which every test image also keeps its five
+# best float64 logits at least 1e-3 of the logit spread apart (4.0 left two of them 5e-6 apart)
+LINEAR_GAIN = 3.25
 
 
 def synth_param(name: str, shape: Tuple[int, ...], kind: str, seed: int, extra: dict) -> np.ndarray:
@@ -89,6 +94,10 @@ def synth_param(name: str, shape: Tuple[int, ...], kind: str, seed: int, extra: 
         w = np.full(n, math.log(5.0 / nc / (640.0 / stride) ** 2) + extra["shift"])
         w = w + 0.5 * normal(key, n)
     elif kind == "bias":
+        w = 0.1 * normal(key, n)
+    elif kind == "linear_w":  # Classify's Linear: class logits of U[0,1) images with a standard deviation of order 1
+        w = normal(key, n) * (LINEAR_GAIN / math.sqrt(shape[1]))
+    elif kind == "linear_b":
         w = 0.1 * normal(key, n)
     elif kind == "dfl":  # DFL conv weight is arange(reg_max), not trainable
         w = np.arange(n, dtype=np.float64)
@@ -208,6 +217,12 @@ def calibrate(graph, sd: Dict[str, np.ndarray], in_mean: float = 0.5, in_var: fl
                 mo, vo = mo + rm, vo + rv
             if a["anchor_level"] < 0:
                 put(a["dst"], mo, vo)
+        elif op.kind == "classify":  # the head conv's BN statistics, as any 1x1 conv's (nothing reads its output here)
+            m0, v0 = get(a["src"])
+            key = a["wkey"]
+            w = sd[key + ".conv.weight"].astype(np.float64)
+            sd[key + ".bn.running_mean"] = (w.sum((2, 3)) @ m0).astype(np.float32)
+            sd[key + ".bn.running_var"] = np.maximum((w * w).sum((2, 3)) @ v0 * VAR_INFLATE_1x1, 1e-3).astype(np.float32)
         elif op.kind == "dwconv":
             m0, v0 = get(a["src"])
             key = a["wkey"]
@@ -245,10 +260,11 @@ def calibrate(graph, sd: Dict[str, np.ndarray], in_mean: float = 0.5, in_var: fl
             put(a["dst"], vm + pm, ATTN_VAR * vv + pv)
 
 
-def synth_weights(scale: str = "n", task: str = "detect", seed: int = 0) -> Dict[str, np.ndarray]:
-    """Ultralytics-style state dict of synthetic weights with calibrated BN stats for yolo11{scale}[-seg]."""
+def synth_weights(scale: str = "n", task: str = "detect", seed: int = 0, nc: int = None) -> Dict[str, np.ndarray]:
+    """Ultralytics-style state dict of synthetic weights with calibrated BN stats for yolo11{scale}[-seg | -pose |
+    -cls].  nc: classes (default: the task's, 1000 for classify)."""
     from .arch import GraphBuilder
-    g = GraphBuilder(scale, task, pad_head=False)  # (pose: the head at its parameters' own channel counts)
+    g = GraphBuilder(scale, task, nc=nc, pad_head=False)  # (pose: the head at its parameters' own channel counts)
     sd = synth_state_dict([(p.name, p.shape, p.kind, p.extra) for p in g.params], seed)
     calibrate(g, sd)
     return sd

@@ -304,6 +304,24 @@ int ym_embed(ym_ctx* ctx, const float* d_input, int B, int H, int W, const ym_in
 int ym_classify(ym_ctx* ctx, const float* d_input, int B, int H, int W, const ym_infer_args* args, float* d_probs,
                 int ld, float* d_logits, int* d_topk, float* d_topk_conf, void* stream);
 
+/* Classify preprocessing (csrc/ym_cls_pre.hip): upstream's classify_transforms — Resize(imgsz) with Pillow's antialiased
+ * BILINEAR (ImagingResample, 8 bits per channel, bit for bit), CenterCrop(imgsz), ToTensor — for B HWC uint8 3-channel
+ * images packed in one device buffer, as one launch that writes the (B, 3, imgsz, imgsz) fp32 batch ym_classify reads.
+ * d_images: 16-byte aligned; image b's first byte at d_images + off (off a multiple of 16), rows row_bytes apart.  The
+ * geometry is the caller's (yolomi/preprocess.py classify_geometry): the image is resized to rh x rw, of which the
+ * imgsz x imgsz window at (top, left) is produced; bgr = 1 for cv2.imread order.  d_desc / h_desc: the B descriptors on
+ * the device and the same on the host, where they are validated.  YM_EINVAL: a null pointer, d_images not 16-byte
+ * aligned, B outside 1..65535, imgsz no positive multiple of 32, and per image off < 0 or off % 16, a size below 1,
+ * row_bytes < 3 * w, bgr outside 0..1, a window outside rh x rw, or h > 64 * rh or w > 64 * rw (the kernel's LDS
+ * tables are sized for at most 64-fold reduction per axis).  Asynchronous on `stream`. */
+typedef struct {
+  long long off;                 /* first byte of the image in d_images */
+  int h, w, row_bytes, bgr;      /* the source image */
+  int rh, rw, top, left;         /* resized size and the crop window's origin in it */
+} ym_cls_pre_desc;
+int ym_classify_pre(ym_ctx* ctx, const void* d_images, const ym_cls_pre_desc* d_desc, const ym_cls_pre_desc* h_desc,
+                    int B, int imgsz, float* d_dst, void* stream);
+
 /* Object tracking (Ultralytics model.track(..., tracker="bytetrack.yaml"), trackers/byte_tracker.py BYTETracker.update):
  * a tracker holds the ByteTrack state of `streams` independent video streams in device memory; one ym_track_update
  * call advances stream b by the detections of image b of a batch, as ONE kernel launch behind the NMS

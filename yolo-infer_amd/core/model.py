@@ -325,7 +325,8 @@ class YOLO11Model:
         """predict() of a classify model: Results with `probs` (core.results.Probs) and no boxes, masks or keypoints.
         Tensor sources (BCHW float, H and W multiples of 32, LoadTensor's /255 rule) stay asynchronous: the head's
         kernels write fresh tensors and nothing is read on the host.  Image sources go through upstream's
-        classify_transforms on the host (yolomi.preprocess.classify_batch; imgsz default 224).  conf, iou, max_det,
+        classify_transforms on the GPU (yolomi.preprocess.classify_batch_gpu, one copy and one launch per batch, bit-equal
+        to Pillow; imgsz default 224); YM_CLS_PRE=host keeps them on the host (classify_batch).  conf, iou, max_det,
         augment and retina_masks do not apply."""
         ignored = [k for k in ("conf", "iou", "max_det", "augment", "retina_masks") if k in kwargs]
         if ignored:
@@ -337,9 +338,14 @@ class YOLO11Model:
                                                 and all(isinstance(s, torch.Tensor) for s in source)):
             im, eps, _ = self._as_batch(source)
         else:
-            from yolomi.preprocess import classify_batch, expand_sources
+            from yolomi.preprocess import classify_batch, classify_batch_gpu, expand_sources
             imgs, paths = expand_sources(source)
-            im = classify_batch(imgs, int(kwargs.get("imgsz", 224))).to(self._dev)
+            imgsz = int(kwargs.get("imgsz", 224))
+            if os.environ.get("YM_CLS_PRE", "gpu") == "host":  # the Pillow path, for A/B and debugging
+                im = classify_batch(imgs, imgsz).to(self._dev)
+            else:
+                im = classify_batch_gpu(eng.rt, imgs, self._dev, imgsz,
+                                        torch.cuda.current_stream(self._dev).cuda_stream)
             eps = torch.finfo(torch.float32).eps
         t1 = time.perf_counter()
         bm = self.global_batch_max(im) if self.global_batch_max is not None and imgs is None else None

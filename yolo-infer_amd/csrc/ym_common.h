@@ -529,6 +529,14 @@ struct LetterboxArgs {
   float* dst; int Hn, Wn;                              // one image of the fp32 NCHW batch (3 planes of Hn x Wn)
 };
 
+constexpr int kClsPreMaxScale = 64;  // ym_cls_pre.hip: the largest source / resized ratio per axis (LDS tables, stage)
+struct ClsPreArgs {                  // csrc/ym_cls_pre.hip: classify_transforms for a batch, one launch
+  const unsigned char* images;       // the packed HWC uint8 images, 16-byte aligned
+  const ym_cls_pre_desc* desc;       // (B) on the device
+  float* dst; int B, imgsz;          // (B, 3, imgsz, imgsz) fp32
+  int KH, KV;                        // the batch's largest tap counts (ym_cls_pre_taps) along x and y
+};
+
 struct PrepArgs {
   const float* in; void* out;  // NCHW fp32 → NHWC act dtype, 8 channels (3 real + 5 zero)
   float* ctl;                  // ctl[0] = running max (ordered-int encoded) of the input
@@ -591,6 +599,8 @@ void ym_debug_add(int key, int d);
 const void* ym_nms_kernel();  // the NMS kernel's function (graph replays re-point its output rows: ym_infer)
 hipError_t ym_launch_stem(int dtype, const ConvArgs& a, hipStream_t st);
 hipError_t ym_launch_letterbox(const LetterboxArgs& a, hipStream_t st);
+hipError_t ym_launch_cls_pre(const ClsPreArgs& a, hipStream_t st);  // ym_cls_pre.hip
+int ym_cls_pre_taps(int in, int out);  // Pillow's ksize of one axis: 2 * ceil(max(in / out, 1)) + 1
 hipError_t ym_launch_spin(int usec, hipStream_t st);  // profiling: park the stream for usec (wall clock)
 hipError_t ym_launch_conv_dma(int out_f32, const ConvArgs& a, int i, hipStream_t st);  // f16 and x3 plans
 hipError_t ym_launch_conv_dma_fuse(int out_f32, const ConvArgs& a, int i, hipStream_t st);  // x3 conv -> 1x1 pairs

@@ -1949,6 +1949,40 @@ int ym_letterbox(ym_ctx* c, const void* d_src, int h, int w, int row_bytes, int 
   return YM_OK;
 }
 
+int ym_classify_pre(ym_ctx* c, const void* d_images, const ym_cls_pre_desc* d_desc, const ym_cls_pre_desc* h_desc,
+                    int B, int imgsz, float* d_dst, void* stream) {
+  if (!c) return fail(YM_EINVAL, "null context");
+  if (!d_images || !d_desc || !h_desc || !d_dst) return fail(YM_EINVAL, "ym_classify_pre: null pointer");
+  if (reinterpret_cast<uintptr_t>(d_images) & 15) return fail(YM_EINVAL, "ym_classify_pre: d_images not 16-byte aligned");
+  if (B < 1 || B > 65535) return fail(YM_EINVAL, "ym_classify_pre: B %d outside 1..65535", B);
+  if (imgsz < 32 || imgsz % 32) return fail(YM_EINVAL, "ym_classify_pre: imgsz %d is no positive multiple of 32", imgsz);
+  ClsPreArgs a{};
+  a.KH = a.KV = 3;
+  for (int b = 0; b < B; ++b) {
+    const ym_cls_pre_desc& d = h_desc[b];
+    if (d.off < 0 || d.off % 16 || d.h < 1 || d.w < 1 || d.rh < 1 || d.rw < 1 || (d.bgr != 0 && d.bgr != 1))
+      return fail(YM_EINVAL, "ym_classify_pre: image %d: bad descriptor (off %lld, %dx%d -> %dx%d, bgr %d)", b, d.off,
+                  d.h, d.w, d.rh, d.rw, d.bgr);
+    if (d.row_bytes < 3 * (long long)d.w)
+      return fail(YM_EINVAL, "ym_classify_pre: image %d: row_bytes %d below 3 * w = %lld", b, d.row_bytes,
+                  3 * (long long)d.w);
+    if (d.top < 0 || d.left < 0 || (long long)d.top + imgsz > d.rh || (long long)d.left + imgsz > d.rw)
+      return fail(YM_EINVAL, "ym_classify_pre: image %d: crop window %d at (%d, %d) outside %dx%d", b, imgsz, d.top,
+                  d.left, d.rh, d.rw);
+    if (d.h > (long long)kClsPreMaxScale * d.rh || d.w > (long long)kClsPreMaxScale * d.rw)
+      return fail(YM_EINVAL, "ym_classify_pre: image %d: %dx%d -> %dx%d reduces by more than %d", b, d.h, d.w, d.rh,
+                  d.rw, kClsPreMaxScale);
+    a.KH = std::max(a.KH, ym_cls_pre_taps(d.w, d.rw));
+    a.KV = std::max(a.KV, ym_cls_pre_taps(d.h, d.rh));
+  }
+  HIPCK(hipSetDevice(c->device));
+  a.images = static_cast<const unsigned char*>(d_images);
+  a.desc = d_desc; a.dst = d_dst; a.B = B; a.imgsz = imgsz;
+  hipError_t e = ym_launch_cls_pre(a, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail(YM_EHIP, "classify_pre launch: %s", hipGetErrorString(e));
+  return YM_OK;
+}
+
 static int launch_masks(ym_ctx* c, MaskArgs& a, int B, int H, int W, void* stream) {
   if (!c) return fail(YM_EINVAL, "null context");
   if (c->task != 1 || c->proto_buf < 0) return fail(YM_ESTATE, "ym_masks needs a segment plan");

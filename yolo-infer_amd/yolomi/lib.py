@@ -111,6 +111,7 @@ def load_library(path: os.PathLike = LIB_PATH):
         "ym_tta_counts": (I, [P, C.POINTER(I), I]),
         "ym_embed": (I, [P, P, I, I, I, C.POINTER(InferArgs), C.POINTER(EmbedView), I, P, C.c_longlong, P]),
         "ym_classify": (I, [P, P, I, I, I, C.POINTER(InferArgs), P, I, P, P, P, P]),
+        "ym_classify_pre": (I, [P, P, P, P, I, I, P, P]),
         "ym_track_create": (I, [P, I, C.POINTER(TrackCfg), C.POINTER(P)]),
         "ym_track_destroy": (None, [P]),
         "ym_track_reset": (I, [P, P]),
@@ -146,7 +147,7 @@ EXPORTED = ("ym_create", "ym_load_weights", "ym_broadcast_weights", "ym_broadcas
             "ym_op_name",
             "ym_num_buffers", "ym_buffer_info", "ym_read_buffer", "ym_sync", "ym_last_error", "ym_destroy",
             "ym_version", "ym_num_conv_cfgs", "ym_set_debug", "ym_read_scratch", "ym_kpt_shape",
-            "ym_tta_shape", "ym_tta_scale", "ym_tta_forward", "ym_tta_nms", "ym_tta_counts", "ym_embed", "ym_classify",
+            "ym_tta_shape", "ym_tta_scale", "ym_tta_forward", "ym_tta_nms", "ym_tta_counts", "ym_embed", "ym_classify", "ym_classify_pre",
             "ym_track_create", "ym_track_destroy", "ym_track_reset", "ym_track_update", "ym_track_read_state", "ym_annotate",
             "ym_mask_contours", "ym_mask_rle")
 
@@ -307,6 +308,14 @@ class Runtime:
         V = C.c_void_p
         _check(self.lib.ym_classify(self.ctx, V(x_ptr), B, H, W, C.byref(args), V(probs_ptr), ld, V(logits_ptr or None),
                                     V(topk_ptr), V(conf_ptr), V(stream)))
+
+    def classify_pre(self, images_ptr: int, desc_ptr: int, host_desc_ptr: int, B: int, imgsz: int, dst_ptr: int,
+                     stream: int):
+        """ym_classify_pre: B packed HWC uint8 images (descriptors on the device and, for validation, on the host) to
+        the (B, 3, imgsz, imgsz) fp32 classify batch; asynchronous on `stream`."""
+        V = C.c_void_p
+        _check(self.lib.ym_classify_pre(self.ctx, V(images_ptr or None), V(desc_ptr or None), V(host_desc_ptr or None),
+                                        B, imgsz, V(dst_ptr or None), V(stream)))
 
     @staticmethod
     def annotate_args(line_width, kpt_radius, flags, color_mode, tracked, det_stride, K, ndim, nc, mask_cap,

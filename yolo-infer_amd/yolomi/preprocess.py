@@ -6,6 +6,8 @@ has the same shape, else every image goes to imgsz x imgsz), stacks them, flips 
 divides by 255.  Here the geometry is computed on the host (`letterbox_geometry`, the same arithmetic as
 `LetterBox.__call__`), each image is copied to the device once, and `ym_letterbox` (csrc/ym_letterbox.hip) writes
 its slot of the fp32 NCHW batch.  Detections are mapped back with `scale_boxes` (upstream `ops.scale_boxes`).
+Classify models take upstream's `classify_transforms` instead: `classify_batch` (Pillow, on the host: the reference)
+and `classify_batch_gpu` (`ym_classify_pre`, csrc/ym_cls_pre.hip: one copy and one launch per batch, the same bits).
 Reference call sites: /root/reference/demos/detection_demo.py:87-93, 190-196 (path / ndarray sources).
 """
 from __future__ import annotations
@@ -124,6 +126,56 @@ def classify_batch(imgs: Sequence[np.ndarray], imgsz: int = 224) -> torch.Tensor
         rgb = np.asarray(pil.crop((left, top, left + imgsz, top + imgsz)), dtype=np.uint8)
         out[i] = rgb.transpose(2, 0, 1).astype(np.float32) / np.float32(255.0)
     return torch.from_numpy(out)
+
+
+# ym_cls_pre_desc (include/yolomi.h): one image of a ym_classify_pre batch
+CLS_DESC = np.dtype([("off", "<i8"), ("h", "<i4"), ("w", "<i4"), ("row_bytes", "<i4"), ("bgr", "<i4"), ("rh", "<i4"),
+                     ("rw", "<i4"), ("top", "<i4"), ("left", "<i4")])
+CLS_PRE_MAX_SCALE = 64  # csrc/ym_common.h kClsPreMaxScale: the kernel's largest reduction per axis
+_cls_stage = {"buf": None, "event": None}  # the pinned staging buffer and the event behind its last copy
+
+
+def classify_desc(shapes: Sequence[Tuple[int, int]], imgsz: int, bgr: bool = True) -> Tuple[np.ndarray, int]:
+    """(the CLS_DESC table of images of `shapes` = (h, w) packed back to back, every start 16-byte aligned, rows 3 * w
+    bytes apart; the 16-byte aligned size of the packed images)."""
+    desc = np.zeros(len(shapes), dtype=CLS_DESC)
+    off = 0
+    for i, (h, w) in enumerate(shapes):
+        desc[i] = (off, h, w, 3 * w, int(bgr)) + classify_geometry(h, w, imgsz)
+        off = (off + 3 * h * w + 15) // 16 * 16
+    return desc, off
+
+
+def classify_batch_gpu(rt, imgs: Sequence[np.ndarray], device: torch.device, imgsz: int = 224,
+                       stream: int = 0) -> torch.Tensor:
+    """classify_batch on the GPU, bit for bit (csrc/ym_cls_pre.hip): the HWC uint8 BGR images and their descriptor
+    table are packed into one pinned staging buffer (kept and grown from call to call), copied to `device` once, and
+    one ym_classify_pre launch writes the (B, 3, imgsz, imgsz) fp32 device batch.  A batch with an image the kernel does
+    not take (a side reduced more than CLS_PRE_MAX_SCALE-fold) goes through classify_batch whole."""
+    if imgsz < 32 or imgsz % 32:
+        raise ValueError(f"classify: imgsz {imgsz} must be a positive multiple of 32")
+    desc, nbytes = classify_desc([im.shape[:2] for im in imgs], imgsz)
+    if bool(np.any(desc["h"] > CLS_PRE_MAX_SCALE * desc["rh"]) or np.any(desc["w"] > CLS_PRE_MAX_SCALE * desc["rw"])):
+        return classify_batch(imgs, imgsz).to(device)
+    total = nbytes + desc.nbytes
+    st = _cls_stage
+    if st["event"] is not None:
+        st["event"].synchronize()  # the last call's copy has read the buffer
+    if st["buf"] is None or st["buf"].numel() < total:
+        st["buf"] = torch.empty(max(total, 1 << 22), dtype=torch.uint8, pin_memory=True)
+    host = st["buf"].numpy()
+    for d, im in zip(desc, imgs):
+        o, n = int(d["off"]), im.size
+        host[o:o + n] = np.ascontiguousarray(im).reshape(-1)
+    host[nbytes:total] = desc.view(np.uint8)
+    with torch.cuda.device(device):
+        dbuf = st["buf"][:total].to(device, non_blocking=True)
+        st["event"] = torch.cuda.Event()
+        st["event"].record()
+    out = torch.empty((len(imgs), 3, imgsz, imgsz), dtype=torch.float32, device=device)
+    rt.classify_pre(dbuf.data_ptr(), dbuf.data_ptr() + nbytes, st["buf"].data_ptr() + nbytes, len(imgs), imgsz,
+                    out.data_ptr(), stream)
+    return out
 
 
 def scale_coords(img1_shape, coords: torch.Tensor, img0_shape) -> torch.Tensor:

@@ -38,7 +38,7 @@ typedef struct {
   int max_h;
   int max_w;
   int scale;  /* 0 = any, else 'n', 's', 'm', 'l' or 'x' */
-  int task;   /* 0 = any, YM_TASK_DETECT, YM_TASK_SEGMENT, YM_TASK_POSE, YM_TASK_CLASSIFY */
+  int task;   /* 0 = any, YM_TASK_DETECT, YM_TASK_SEGMENT, YM_TASK_POSE, YM_TASK_CLASSIFY, YM_TASK_OBB */
   int dtype;  /* 0 = any, YM_DTYPE_F16, YM_DTYPE_F32, YM_DTYPE_I8, YM_DTYPE_F8, YM_DTYPE_X3 */
   int reserved[2];
 } ym_model_desc;
@@ -47,6 +47,7 @@ typedef struct {
 #define YM_TASK_SEGMENT 2
 #define YM_TASK_POSE 3 /* Detect + keypoint branch; ym_infer rows carry the decoded keypoints (see ym_infer) */
 #define YM_TASK_CLASSIFY 4 /* the backbone without SPPF + the Classify head; run by ym_classify, not ym_infer */
+#define YM_TASK_OBB 5 /* Detect + angle branch; ym_infer rows are [cx cy w h conf cls theta] (see ym_infer, ym_obb_nms) */
 #define YM_DTYPE_F16 1 /* fp16 storage, fp32 MFMA accumulation (throughput plan) */
 #define YM_DTYPE_F32 2 /* exact-f32 MFMA (parity plan) */
 #define YM_DTYPE_I8 3  /* PTQ int8 (torch.ao qconfig of optimization/quantization/quantizers.py:124-131) */
@@ -128,9 +129,21 @@ int ym_rccl_comm_destroy(void* comm);
  * multiple of 4 (COCO: 17*3 = 51 -> 52): [x1,y1,x2,y2,conf,cls, kpt_0 .. kpt_{K-1}, 0 pad] with kpt_k = (x, y[, v]) in
  * input pixels (Ultralytics Pose.kpts_decode: x = (raw*2 + grid_x)*stride, v = sigmoid(raw)); not clipped to the
  * image and not masked by visibility — scale_coords and the Keypoints view do that on the host side.
- * K and ndim: ym_kpt_shape. */
+ * K and ndim: ym_kpt_shape.
+ * OBB plans (YM_TASK_OBB): nm = 1 and a row is [cx, cy, w, h, conf, cls, theta] in input pixels and radians, as
+ * Ultralytics non_max_suppression(rotated=True) returns it: theta = (sigmoid(z) - 0.25) pi, not yet regularised, the
+ * box not clipped.  The NMS is upstream's Fast-NMS on ProbIoU (csrc/ym_obb.hip): candidate j is kept iff no
+ * higher-scored candidate i has probiou(i, j) >= iou.  multi_label = 1 is YM_EINVAL on an obb plan. */
 int ym_infer(ym_ctx* ctx, const float* d_input, int B, int H, int W, const ym_infer_args* args, float* d_dets,
              int* d_counts, void* stream);
+
+/* OBB plans: the rotated decode + NMS stage of ym_infer alone, on the caller's head rows instead of the forward's:
+ * d_rows is a (B, A, row) fp32 device tensor laid out as the plan's anchor buffer ([64 DFL | classes padded to 4 |
+ * angle logit, padded to 4]; row and A: ym_buffer_info of the anchor buffer after this call, A = anchors of H x W).
+ * Writes d_dets (B, max_det, 7) and d_counts (B) as ym_infer does; eager launches on `stream`, asynchronous.
+ * YM_EINVAL on another plan, multi_label = 1 or a null pointer. */
+int ym_obb_nms(ym_ctx* ctx, const float* d_rows, int B, int H, int W, const ym_infer_args* args, float* d_dets,
+               int* d_counts, void* stream);
 
 /* LoadTensor statistics of a device batch: *d_max = max over the n fp32 elements of d_input (asynchronous on
  * `stream`).  Each rank of a batch-sharded run computes its shard's max, the ranks all-reduce it (MAX), and pass the
@@ -192,6 +205,12 @@ int ym_kpt_shape(ym_ctx* ctx, int* K, int* ndim);
 #define YM_SCRATCH_COUNTS 1
 #define YM_SCRATCH_KPTS 2
 #define YM_SCRATCH_POOLED 3
+/* obb plans, after ym_infer / ym_obb_nms: what obb_decode wrote per anchor — (B, A) float4 (cx, cy, w, h),
+ * (B, A) float4 (theta, A, B, C: the ProbIoU covariance terms), (B, A) fp32 best scores, (B, A) int32 classes */
+#define YM_SCRATCH_OBB_BOXES 4
+#define YM_SCRATCH_OBB_COV 5
+#define YM_SCRATCH_OBB_SCORES 6
+#define YM_SCRATCH_OBB_CLS 7
 int ym_read_scratch(ym_ctx* ctx, int which, void* dst, size_t bytes);
 
 /* Segment plans: instance masks of the detections of the last ym_infer (same B, H, W, stream order), i.e. Ultralytics

@@ -23,7 +23,7 @@ import torch
 from yolomi.engine import Engine
 from yolomi.synth import synth_weights
 
-from .results import LazyCounts, Probs, Results
+from .results import OBB, LazyCounts, Probs, Results, obb_rows_to_results
 
 logger = logging.getLogger(__name__)
 
@@ -230,10 +230,11 @@ class YOLO11Model:
             raise ValueError(f"Unsupported size: {self.size}. Supported: {self.SUPPORTED_SIZES}")
         if self.task not in self.HIP_TASKS:
             has_weights = self.model_path or self._sd is not None or self._blob is not None
-            if self.task == "classify" and has_weights:
-                return  # the weights decide (they must hold a yolo11-cls model: _load_model)
+            if self.task in ("classify", "obb") and has_weights:
+                return  # the weights decide (they must hold a yolo11-cls / yolo11-obb model: _load_model)
             hint = ("; a classify model is built from its weights: pass model_path=, state_dict= or weights_blob= of a "
-                    "yolo11-cls model (there is no checkpoint to fetch offline)") if self.task == "classify" else ""
+                    f"yolo11-{'cls' if self.task == 'classify' else 'obb'} model (there is no checkpoint to fetch offline)"
+                    ) if self.task in ("classify", "obb") else ""
             raise NotImplementedError(f"task {self.task!r} has no MI355X plan (supported: {self.HIP_TASKS}){hint}")
 
     def _load_model(self) -> _ModelHandle:
@@ -257,8 +258,8 @@ class YOLO11Model:
             if self._blob is not None:  # a packed model says what it is in its header
                 from yolomi.plan import TASK_IDS, unpack_blob
                 h = unpack_blob(self._blob)[0]
-                if h.task == TASK_IDS["classify"]:
-                    self.task, nc = "classify", h.nc
+                if h.task in (TASK_IDS["classify"], TASK_IDS["obb"]):
+                    self.task, nc = ("classify" if h.task == TASK_IDS["classify"] else "obb"), h.nc
                     self.size = chr(h.scale) if h.scale else self.size
             if sd and self._blob is None:  # the checkpoint decides the architecture, as YOLO(model_path) does
                 from yolomi.arch import infer_arch, infer_kpt_shape
@@ -270,6 +271,8 @@ class YOLO11Model:
                     self.size, self.task = scale, task
             if self.task == "classify" and not sd and self._blob is None:
                 raise NotImplementedError("task 'classify': pass the weights of a yolo11-cls model")
+            if self.task == "obb" and not sd and self._blob is None:
+                raise NotImplementedError("task 'obb': pass the weights of a yolo11-obb model")
             engine = Engine(self.size, self.task, sd, dev, self.dtype, blob=self._blob, qparams=self._qparams, nc=nc,
                             receive=self._weights_from, kpt_shape=kpt_shape if self.task == "pose" else None)
             names = COCO_NAMES if nc == 80 else {i: f"class{i}" for i in range(nc)}
@@ -369,9 +372,38 @@ class YOLO11Model:
             res.append(r)
         return res
 
+    def _predict_obb(self, source, kwargs) -> List[Results]:
+        """predict() of an OBB model: Results with `obb` (core.results.OBB) and boxes None, as upstream.  The engine's
+        rows [cx, cy, w, h, conf, cls, theta] (csrc/ym_obb.hip) are regularised and, for image sources, mapped back to
+        each original image as scale_boxes(xywh=True) does.  augment, retina_masks and embed do not apply."""
+        if kwargs.get("embed", None) is not None:
+            raise NotImplementedError("embed is not offered for OBB models")
+        nms = _nms_kwargs(kwargs)
+        im, eps, imsrc, bm, t0, t1 = self._begin(source, kwargs)
+        eng = self.model.engine
+        B = im.shape[0]
+        out = torch.empty((B, nms["max_det"], 7), dtype=torch.float32, device=im.device)
+        _, counts = eng.run(im, in_eps=eps, batch_max=bm, dets_out=out, **nms)
+        n = counts[:B].tolist()  # the device→host sync of the call
+        speed = _speed(t0, t1)
+        res = []
+        for b in range(B):
+            if imsrc is None:
+                r = Results.from_batch(im, b, self.model.names, None, 0, path=f"image{b}.jpg", speed=speed, annotator=eng)
+                data = obb_rows_to_results(out[b, : n[b]])
+            else:
+                r = Results.from_image(imsrc[0][b], imsrc[1][b], self.model.names, None, speed=speed, annotator=eng)
+                data = obb_rows_to_results(out[b, : n[b]], im.shape[2:], imsrc[2][b])
+            r.boxes = None
+            r.obb = OBB(data, r.orig_shape)
+            res.append(r)
+        return res
+
     def predict(self, source, **kwargs) -> List[Results]:
         if self.task == "classify" and kwargs.get("embed", None) is None:
             return self._predict_classify(source, kwargs)
+        if self.task == "obb":
+            return self._predict_obb(source, kwargs)
         nms = _nms_kwargs(kwargs)
         augment = bool(kwargs.get("augment", False))
         if kwargs.get("embed", None) is not None:
@@ -461,6 +493,8 @@ class YOLO11Model:
         from yolomi.track import tracker_config
         if self.task == "classify":
             raise NotImplementedError("track() needs detections: a classify model has none")
+        if self.task == "obb":
+            raise NotImplementedError("track() is offered for detect and pose models: rotated boxes are not tracked")
         cfg = tracker_config(tracker)
         if self.task == "segment":
             raise NotImplementedError("track() is offered for detect and pose models: a segment model's masks would "
@@ -503,6 +537,8 @@ class YOLO11Model:
         """Ultralytics Model.embed: predict(source, embed=[len(model.model) - 2]) unless `embed` is given — layer 22,
         the last neck C3k2 (256 channels for yolo11n, 512 for yolo11s)."""
         from yolomi.arch import DEFAULT_EMBED
+        if self.task == "obb":
+            raise NotImplementedError("embed() is not offered for OBB models")
         if kwargs.get("embed", None) is None:  # (a classify model: layer 9, 256 channels for yolo11n-cls)
             kwargs["embed"] = [9] if self.task == "classify" else list(DEFAULT_EMBED)
         return self.predict(source, **kwargs)
@@ -585,6 +621,8 @@ class YOLO11Model:
         from yolomi.val import run_val
         if self.task == "classify":
             raise NotImplementedError("val() computes detection metrics: classification validation is not offered")
+        if self.task == "obb":
+            raise NotImplementedError("val() computes axis-aligned detection metrics: OBB validation is not offered")
         if data is None:
             raise ValueError("val() needs data: a dataset YAML, a directory with images/ and labels/, or a list")
         if ignored:

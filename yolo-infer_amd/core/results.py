@@ -251,6 +251,78 @@ class Keypoints(_TensorView):
         return self.data[..., 2] if self.has_visible else None
 
 
+class OBB(_TensorView):
+    """(n, 7) [cx, cy, w, h, theta, conf, cls] oriented boxes of one image (upstream `ultralytics.engine.results.OBB`):
+    centre and size in the original image's pixels, theta in radians, regularised (w >= h, theta in [0, pi))."""
+
+    def __init__(self, boxes, orig_shape):
+        if boxes.ndim == 1:
+            boxes = boxes[None, :]
+        super().__init__(boxes)
+        self.orig_shape = orig_shape
+
+    def _extra(self):
+        return (self.orig_shape,)
+
+    @property
+    def xywhr(self):
+        return self.data[:, :5]
+
+    @property
+    def conf(self):
+        return self.data[:, -2]
+
+    @property
+    def cls(self):
+        return self.data[:, -1]
+
+    @property
+    def xyxyxyxy(self):
+        """(n, 4, 2) corners ctr + v1 + v2, ctr + v1 - v2, ctr - v1 - v2, ctr - v1 + v2 (upstream's xywhr2xyxyxyxy), with
+        v1 = (w / 2)(cos, sin) and v2 = (h / 2)(-sin, cos)."""
+        d = self.data
+        xp = torch if isinstance(d, torch.Tensor) else np
+        c, s = xp.cos(d[:, 4]), xp.sin(d[:, 4])
+        ctr = d[:, :2]
+        v1 = xp.stack([d[:, 2] / 2 * c, d[:, 2] / 2 * s], -1)
+        v2 = xp.stack([-d[:, 3] / 2 * s, d[:, 3] / 2 * c], -1)
+        return xp.stack([ctr + v1 + v2, ctr + v1 - v2, ctr - v1 - v2, ctr - v1 + v2], -2)
+
+    @property
+    def xyxyxyxyn(self):
+        p = self.xyxyxyxy
+        p = p.clone() if isinstance(p, torch.Tensor) else np.copy(p)
+        p[..., 0] /= self.orig_shape[1]
+        p[..., 1] /= self.orig_shape[0]
+        return p
+
+    @property
+    def xyxy(self):
+        """(n, 4) the axis-aligned hull of the corners."""
+        p = self.xyxyxyxy
+        xp = torch if isinstance(p, torch.Tensor) else np
+        x, y = p[..., 0], p[..., 1]
+        return xp.stack([x.min(-1)[0] if xp is torch else x.min(-1), y.min(-1)[0] if xp is torch else y.min(-1),
+                         x.max(-1)[0] if xp is torch else x.max(-1), y.max(-1)[0] if xp is torch else y.max(-1)], -1)
+
+
+def obb_rows_to_results(rows, in_shape=None, orig_shape=None):
+    """NMS rows (n, 7) [cx, cy, w, h, conf, cls, theta] -> OBB data (n, 7) [cx, cy, w, h, theta, conf, cls] as
+    OBBPredictor builds it: regularize_rboxes (w <= h: swap and theta + pi / 2; theta mod pi), then, for a letterboxed
+    source, scale_boxes(xywh=True): the pad off the centre, all four by the gain, no clip."""
+    import math
+    x, y, w, h, conf, c, t = rows.unbind(-1)
+    swap = w <= h
+    w_, h_ = torch.where(swap, h, w), torch.where(swap, w, h)
+    t = torch.where(swap, t + math.pi / 2, t) % math.pi
+    if in_shape is not None and orig_shape is not None and tuple(in_shape) != tuple(orig_shape):
+        gain = min(in_shape[0] / orig_shape[0], in_shape[1] / orig_shape[1])
+        px = round((in_shape[1] - orig_shape[1] * gain) / 2 - 0.1)
+        py = round((in_shape[0] - orig_shape[0] * gain) / 2 - 0.1)
+        x, y, w_, h_ = (x - px) / gain, (y - py) / gain, w_ / gain, h_ / gain
+    return torch.stack([x, y, w_, h_, t, conf, c], -1)
+
+
 class Probs(_TensorView):
     """Upstream `Probs`: the class probabilities of one image.  `data` is the (nc,) softmax the head's kernel wrote;
     top1 / top5 / top1conf / top5conf read that kernel's own top-k (csrc/ym_classify.hip: descending, equal
@@ -469,11 +541,15 @@ class Results:
         return self._orig_img
 
     def __len__(self):  # (upstream: the length of the first field that is set; a classification result: its nc)
+        if self.boxes is None and self.obb is not None:
+            return len(self.obb)
         return len(self.boxes) if self.boxes is not None else (len(self.probs) if self.probs is not None else 0)
 
     def _no_detections(self, what: str):
         if self.boxes is None and self.probs is not None:
             raise NotImplementedError(f"{what} needs detections: a classification result has probs only")
+        if self.obb is not None:
+            raise NotImplementedError(f"{what} is not offered for oriented boxes (Results.obb)")
 
     def verbose(self) -> str:
         """Upstream `Results.verbose`: "name conf, " of a classification result's top-5; else "n name(s), " per detected
@@ -484,7 +560,7 @@ class Results:
                              for j, c in zip(p.top5, torch.as_tensor(p.top5conf).tolist())) + ", "
         if len(self) == 0:
             return "(no detections), "
-        cls, n = torch.as_tensor(self.boxes.cls).unique(return_counts=True)
+        cls, n = torch.as_tensor((self.boxes if self.boxes is not None else self.obb).cls).unique(return_counts=True)
         return "".join(f"{k} {self.names[int(c)]}{'s' * (k > 1)}, " for c, k in zip(cls.tolist(), n.tolist()))
 
     def _like(self, orig_tensor, boxes, masks, keypoints=None):
@@ -503,9 +579,10 @@ class Results:
         return r
 
     def __getitem__(self, idx):
-        if self.boxes is None:  # a classification result: its probs, indexed
+        if self.boxes is None:  # a classification result: its probs, indexed; an OBB result: its rows
             r = self._like(self._orig_tensor, None, None)
             r.probs = self.probs[idx] if self.probs is not None else None
+            r.obb = self.obb[idx] if self.obb is not None else None
             return r
         k = self.keypoints
         r = self._like(self._orig_tensor, self.boxes.data[idx],
@@ -519,6 +596,7 @@ class Results:
         if self.boxes is None:  # a classification result: its probs on the host
             r = self._like(self._orig_tensor.cpu() if self._orig_tensor is not None else None, None, None)
             r.probs = self.probs.cpu() if self.probs is not None else None
+            r.obb = self.obb.cpu() if self.obb is not None else None
             return r
         k = self.keypoints
         r = self._like(self._orig_tensor.cpu() if self._orig_tensor is not None else None, self.boxes.data.cpu(),
@@ -570,6 +648,13 @@ class Results:
         if self.probs is not None:  # classification: the top-1
             p = self.probs
             return [{"name": self.names[p.top1], "class": p.top1, "confidence": round(float(p.top1conf), decimals)}]
+        if self.obb is not None:  # upstream: the four corners as "box"
+            h, w = self.orig_shape if normalize and self.orig_shape is not None else (1, 1)
+            pts = torch.as_tensor(self.obb.xyxyxyxy).cpu().tolist()
+            return [{"name": self.names[int(row[-1])], "class": int(row[-1]), "confidence": round(row[-2], decimals),
+                     "box": {f"{a}{k + 1}": round(p[k][j] / d, decimals) for k in range(4)
+                             for j, (a, d) in enumerate((("x", w), ("y", h)))}}
+                    for row, p in zip(torch.as_tensor(self.obb.data).cpu().tolist(), pts)]
         out = []
         is_track = self.boxes.is_track
         segs = self.masks.xy if self.masks is not None else None
@@ -610,6 +695,7 @@ class Results:
         (with their visibility when they have one) for pose; then the confidence when `save_conf`, then the track id of
         tracked rows.  Values are written with %g.  Nothing is written for an image without detections."""
         import os
+        self._no_detections("save_txt()") if self.obb is not None else None
         if self.probs is not None:  # classification: upstream's "{conf:.2f} {name}" lines of the top-5
             p = self.probs
             texts = [f"{c:.2f} {self.names[j]}" for j, c in zip(p.top5, torch.as_tensor(p.top5conf).tolist())]
@@ -645,4 +731,6 @@ class Results:
     def __repr__(self):
         if self.boxes is None and self.probs is not None:
             return f"Results(probs={tuple(self.probs.shape)}, orig_shape={self.orig_shape})"
+        if self.boxes is None and self.obb is not None:
+            return f"Results(obb={len(self.obb)}, orig_shape={self.orig_shape})"
         return f"Results(boxes={len(self.boxes)}, orig_shape={self.orig_shape})"

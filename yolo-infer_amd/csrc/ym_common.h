@@ -455,6 +455,8 @@ struct NmsArgs {
 // ---- shared by the NMS kernels (csrc/ym_nms.hip nms_image, csrc/ym_nms_ml.hip): one definition of the sort and of
 // the IoU arithmetic, so the single-label and the multi-label path cannot drift apart
 constexpr int NMS_T = 1024;  // threads of an NMS / key-sort workgroup
+constexpr int NMS_BM = 512;      // nms_image's bit-matrix path; the presort skips images with no more candidates
+constexpr int NMS_SORT = 16384;  // keys sorted in LDS (128 KB: the whole LDS arena); the presort's upper limit
 
 // A step whose stride is <= 64 only pairs elements inside the 128-element run a wave's 64 consecutive i cover (i =
 // tid + NMS_T m), so consecutive such steps need no workgroup barrier: the wave's own LDS operations are in order.
@@ -520,6 +522,27 @@ struct KptArgs {  // Pose: keypoint decode of the NMS candidates (csrc/ym_kpts.h
   float* out; int nk_pad;                     // (B, A, nk_pad) decoded rows (only the candidates' rows are written)
   int A, kstride, K, ndim, B;
   int lvl_W[4], lvl_off[4], nl; float lvl_stride[4];
+};
+
+// OBB (csrc/ym_obb.hip): rotated decode, Fast-NMS on ProbIoU, rows [cx cy w h conf cls theta]
+struct ObbEntry {  // one sorted candidate as the NMS tiles hold it: 32 bytes, two float4
+  float x, y;      // centre, x with the class offset cls * max_wh added in fp32 (0 when agnostic)
+  float A, B;      // covariance terms a' cos² + b' sin², a' sin² + b' cos² (a' = w²/12, b' = h²/12)
+  float C, S;      // (a' - b') cos sin; S = w h / 12 = sqrt(A B - C²)
+  int cls; unsigned anc;
+};
+struct ObbArgs {
+  const float* anchors; int no_tot, ang_off;  // (B, A, no_tot) fp32 head rows; the angle logit at [ang_off]
+  float4* boxes; float4* cov; float* scores; int* cls;  // (B, A): (cx, cy, w, h), (theta, A, B, C), best score, class
+  unsigned long long* keys; unsigned long long* keys2; int* counts;  // as DecodeArgs / NmsArgs
+  ObbEntry* sorted; unsigned char* keep; int* nsel;  // (B, A) candidates in score order, their keep bytes; (B) their count
+  float* dets; int* out_counts; int* counts2;        // (B, max_det, 7), (B), as NmsArgs
+  int A, kstride, nc, reg_max, B, nl;
+  int lvl_W[4], lvl_off[4]; float lvl_stride[4];
+  float conf; int has_classes; unsigned int classes[4];
+  int max_det, max_nms, agnostic, presort;  // presort: the keys go through ym_launch_nms_presort first (low conf)
+  float max_wh, img_h, img_w;
+  double iou;
 };
 
 struct LetterboxArgs {
@@ -589,6 +612,8 @@ hipError_t ym_launch_nms_presort(const NmsArgs& a, hipStream_t st);  // ym_nms.h
 hipError_t ym_launch_nms_ml(const MlArgs& m, const NmsArgs& n, hipStream_t st);
 const void* ym_nms_ml_kernel();  // its NMS kernel (takes NmsArgs: graph replays re-point its rows as nms_image's)
 hipError_t ym_launch_kpts(const KptArgs& a, hipStream_t st);  // ym_kpts.hip: Pose keypoints of the candidates
+hipError_t ym_launch_obb_decode(const ObbArgs& a, hipStream_t st);  // ym_obb.hip: boxes, angles, covariances, keys
+hipError_t ym_launch_obb_nms(const ObbArgs& a, hipStream_t st);     // ym_obb.hip: sort -> keep flags -> rows
 hipError_t ym_launch_conv_dma_i8(const ConvArgs& a, int dma_cfg, hipStream_t st);  // ym_conv_dma.hip
 hipError_t ym_launch_conv_dma_chain(const ConvArgs& a0, const ConvArgs& a1, int dma_cfg, int* ctl, int cap,
                                     hipStream_t st);  // csrc/ym_conv_dma.hip: two dependent x3 convs, one launch

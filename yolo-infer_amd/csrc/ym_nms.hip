@@ -11,7 +11,7 @@ namespace {
 // everything (keys, boxes, areas, flags) lives in LDS, so the serial scan costs LDS latency per candidate;
 // larger candidate sets fall back to the same algorithm on global scratch.
 constexpr int NMS_LDS = 4096;
-constexpr int NMS_BM = 512;  // bit-matrix path: 512 x 8 words of 64 bits (32 KB) behind the first 512 boxes
+// (NMS_BM = 512, ym_common.h) bit-matrix path: 512 x 8 words of 64 bits (32 KB) behind the first 512 boxes
 // blocked path (NMS_BM < n, up to NMS_BLK_MAX candidates after max_nms, e.g. the validator's conf 0.001 at 640²: up to
 // A = 8,400): the keys sorted in LDS, then the greedy scan in blocks of NMS_BLK candidates in score order — a block's
 // candidates are first tested against every box kept by earlier blocks (the kept list in LDS), the survivors'
@@ -21,7 +21,7 @@ constexpr int NMS_BM = 512;  // bit-matrix path: 512 x 8 words of 64 bits (32 KB
 // NMS_NC): boxes of different classes are offset cls * max_wh apart and cannot intersect (IoU 0, never > iou), so a
 // candidate is tested only against kept boxes of its class (per-class lists) and a bit-matrix word only where the
 // word holds a box of row i's class (per-word class masks).
-constexpr int NMS_SORT = 16384;  // keys sorted in LDS (128 KB: the whole LDS arena)
+// (NMS_SORT = 16384, ym_common.h: keys sorted in LDS, 128 KB, the whole LDS arena)
 constexpr int NMS_BLK = 256;     // candidates per block (bit matrix 256 x 4 words)
 constexpr int NMS_KEEP = 512;    // kept boxes held in LDS: max_det up to this on the blocked path
 constexpr int NMS_NC = 128;      // classes of the class filter

@@ -97,7 +97,8 @@ int validate_ops(const Plan& p, std::string& err) {
 }  // namespace
 
 const char* ym_task_name(int t) {
-  return t == 0 ? "detect" : t == 1 ? "segment" : t == kTaskPose ? "pose" : t == kTaskClassify ? "classify" : "unknown";
+  return t == 0 ? "detect" : t == 1 ? "segment" : t == kTaskPose ? "pose" : t == kTaskClassify ? "classify"
+         : t == kTaskObb ? "obb" : "unknown";
 }
 
 int op_reads(const OpRec& o, int out[3]) {
@@ -142,8 +143,8 @@ int ym_plan_parse(const void* blob, size_t bytes, const ym_model_desc* want, Pla
     return bad(err, "bad head geometry (nc %d, nm %d, reg_max %d)", h.nc, nm, h.reg_max);
   for (int l = 0; l < h.nl; ++l)
     if (h.stride(l) < 1 || h.stride(l) > 64) return bad(err, "bad stride %d", h.stride(l));
-  if (task < 0 || task > kTaskClassify)
-    return bad(err, "unknown task %d (detect 0, segment 1, pose 2, classify 3)", task);
+  if (task < 0 || task > kTaskObb)
+    return bad(err, "unknown task %d (detect 0, segment 1, pose 2, classify 3, obb 4)", task);
   if (want) {  // what the creator of the context expects (0 = any)
     if (want->task && want->task != task + 1)
       return bad(err, "blob task %s, context created for %s", ym_task_name(task), ym_task_name(want->task - 1));
@@ -167,6 +168,12 @@ int ym_plan_parse(const void* blob, size_t bytes, const ym_model_desc* want, Pla
         h.kpt_off < 0 || (h.kpt_off & 3) || (arow & 3) || (long)h.kpt_off + nm > arow || h.no != h.kpt_off)
       return bad(err, "bad pose head geometry (K %d, ndim %d, nm %d, offset %d, row %d)", h.kpt_k, h.kpt_ndim, nm,
                  h.kpt_off, arow);
+  }
+  if (task == kTaskObb) {  // rows [reg_max * 4 DFL | cls_pad >= nc classes | angle logit at `no`], float4-aligned; float plans
+    const int arow = out.bufs[h.anchor_buf].C;
+    if (ym_dt_q8(dtype) || nm != 1 || h.reg_max != 16 || h.cls_pad < h.nc || (h.cls_pad & 3) ||
+        h.no != 4 * h.reg_max + h.cls_pad || (arow & 3) || arow > 192 || h.no + 1 > arow || !out.bufs[h.anchor_buf].f32)
+      return bad(err, "bad obb head geometry (nc %d, class slice %d, angle offset %d, row %d)", h.nc, h.cls_pad, h.no, arow);
   }
   out.ops.resize(nop);
   for (int i = 0; i < nop; ++i) {

@@ -31,6 +31,7 @@ constexpr int kBufRec = 8, kNameLen = 48;   // int32 words per buffer record, by
 constexpr size_t kQRecBytes = 1088;         // sizeof(QRec) (ym_common.h)
 constexpr int kTaskPose = 2;
 constexpr int kTaskClassify = 3;  // (include/yolomi.h YM_TASK_CLASSIFY - 1)
+constexpr int kTaskObb = 4;       // (YM_TASK_OBB - 1)
 constexpr int kClsWidth = 1280;    // Classify's hidden width (csrc/ym_classify.h kClsHidden)
 constexpr int kMaxLevels = 3;  // the header has three stride slots
 
@@ -42,9 +43,9 @@ struct PlanHeader {
   int32_t magic;       // kPlanMagic
   int32_t version;     // 1
   int32_t dtype;       // YM_DT_*
-  int32_t task;        // 0 detect, 1 segment, 2 pose, 3 classify
+  int32_t task;        // 0 detect, 1 segment, 2 pose, 3 classify, 4 obb
   int32_t nc;          // classes (classify plans: any count; others <= 128)
-  int32_t nm;          // extras NMS carries per row (segment: 32 mask coefficients; pose: K * ndim padded to 4)
+  int32_t nm;          // extras NMS carries per row (segment: 32 mask coefficients; pose: K * ndim padded to 4; obb: 1)
   int32_t reg_max;
   int32_t nl;          // head levels, <= kMaxLevels
   int32_t stride0;
@@ -57,12 +58,12 @@ struct PlanHeader {
   int32_t input_buf;
   int32_t anchor_buf;  // (classify plans: -1)
   int32_t proto_buf;   // segment plans (-1 otherwise)
-  int32_t no;          // offset of the nm extras in the anchor row
+  int32_t no;          // offset of the nm extras in the anchor row (obb: of the raw angle logit)
   int32_t scale;       // 'n', 's', ... (checked against ym_model_desc.scale; 0: unknown)
   int32_t kpt_k;       // pose plans: keypoints ...
   int32_t kpt_ndim;    // ... values of each (2 | 3) ...
   int32_t kpt_off;     // ... offset of the raw keypoints in the anchor row (= no) ...
-  int32_t cls_pad;     // ... and class channels of the anchor row (nc padded to 4); all four 0 in other plans
+  int32_t cls_pad;     // ... and class channels of the anchor row (nc padded to 4; obb plans too); 0 in other plans
   int32_t rsv24;
   int32_t rsv25;
   int32_t rsv26;

@@ -274,6 +274,9 @@ struct ym_ctx {
   size_t arena_bytes = 0;
   std::vector<size_t> buf_off;
   size_t off_ctl = 0, off_slab = 0, off_cnt = 0, off_chain = 0, off_kpts = 0, slab_bytes = 0;
+  // obb plans: per anchor the (theta, A, B, C) float4 of obb_decode, the sorted ObbEntry and the keep byte, per image
+  // the sorted count (csrc/ym_obb.hip); the regions hold cB images each
+  size_t off_obb_cov = 0, off_obb_sorted = 0, off_obb_keep = 0, off_obb_nsel = 0;
   // classify plans: the head's op and its scratch in the arena — pooled (B, 1280), then logits, probs (B, nc each),
   // top-k classes and probabilities (B, kClsTopK each), all fp32 / int32; a call's own outputs replace the last four
   int cls_op = -1;
@@ -488,6 +491,13 @@ int ensure_workspace(ym_ctx* c, int B, int H, int W) {
   if (c->task == kTaskPose) off = align_up(off + (size_t)nB * c->A * c->nm * 4, 256);
   c->off_cls = off;
   if (c->task == kTaskClassify) off = align_up(off + c->cls_bytes(nB), 256);
+  if (c->task == kTaskObb) {
+    const size_t na = (size_t)nB * c->A;
+    c->off_obb_cov = off;     off = align_up(off + na * sizeof(float4), 256);
+    c->off_obb_sorted = off;  off = align_up(off + na * sizeof(ObbEntry), 256);
+    c->off_obb_keep = off;    off = align_up(off + na, 256);
+    c->off_obb_nsel = off;    off = align_up(off + (size_t)nB * 4, 256);
+  }
   c->arena_bytes = off;
   hipError_t e = hipMalloc(&c->d_arena, off);
   if (e != hipSuccess) {
@@ -698,6 +708,31 @@ hipError_t launch_nms_stage(const NmsView& v, const NmsSource& src, const ym_inf
   return ym_launch_nms(a, st);
 }
 
+// The OBB stage's arguments over B images from image img0 on: `rows` their (B, A, no_tot) head rows
+ObbArgs obb_args(ym_ctx* c, const float* rows, int img0, int B, const ym_infer_args* args, float* dets, int* out_counts,
+                 int* counts2) {
+  const NmsView v = nms_view(c->d_arena, c->nms, img0);
+  ObbArgs a{};
+  a.anchors = rows; a.no_tot = c->bufs[c->anchor_buf].C; a.ang_off = c->no;
+  a.boxes = v.boxes; a.scores = v.scores; a.cls = v.cls; a.keys = v.keys; a.keys2 = v.keys2; a.counts = v.counts;
+  const size_t i0 = (size_t)img0 * c->A;
+  a.cov = reinterpret_cast<float4*>(c->d_arena + c->off_obb_cov) + i0;
+  a.sorted = reinterpret_cast<ObbEntry*>(c->d_arena + c->off_obb_sorted) + i0;
+  a.keep = reinterpret_cast<unsigned char*>(c->d_arena + c->off_obb_keep) + i0;
+  a.nsel = reinterpret_cast<int*>(c->d_arena + c->off_obb_nsel) + img0;
+  a.dets = dets; a.out_counts = out_counts; a.counts2 = counts2;
+  a.A = v.A; a.kstride = v.kstride; a.nc = c->nc; a.reg_max = c->reg_max; a.B = B; a.nl = c->nl;
+  for (int l = 0; l < c->nl; ++l) {
+    a.lvl_W[l] = c->lvl_W[l]; a.lvl_off[l] = c->lvl_off[l]; a.lvl_stride[l] = (float)c->strides[l];
+  }
+  a.conf = args->conf; a.has_classes = args->has_classes;
+  for (int i = 0; i < 4; ++i) a.classes[i] = args->classes[i];
+  a.max_det = args->max_det; a.max_nms = args->max_nms; a.agnostic = args->agnostic;
+  a.presort = args->conf < kPresortConf && v.kstride >= NMS_SORT;  // as launch_nms_stage
+  a.max_wh = args->max_wh; a.img_h = (float)c->cH; a.img_w = (float)c->cW; a.iou = args->iou;
+  return a;
+}
+
 int launch_op(ym_ctx* c, const Launch& L, const Op& op, int B, const float* d_in, const ym_infer_args* args,
               float* d_dets, int* d_counts, hipStream_t st) {
   const int dt = c->dtype;
@@ -793,6 +828,11 @@ int launch_op(ym_ctx* c, const Launch& L, const Op& op, int B, const float* d_in
       break;
     }
     case OP_DECODE: {
+      if (c->task == kTaskObb) {  // the rotated decode (csrc/ym_obb.hip); the rows and counts come with OP_NMS
+        e = ym_launch_obb_decode(obb_args(c, reinterpret_cast<const float*>(c->bptr(c->anchor_buf, L.img0)), L.img0, B,
+                                          args, nullptr, nullptr, nullptr), st);
+        break;
+      }
       const NmsView v = nms_view(c->d_arena, c->nms, L.img0);
       DecodeArgs a{};
       a.anchors = reinterpret_cast<const float*>(c->bptr(c->anchor_buf, L.img0));
@@ -814,6 +854,12 @@ int launch_op(ym_ctx* c, const Launch& L, const Op& op, int B, const float* d_in
       const float* rows = reinterpret_cast<const float*>(c->bptr(c->anchor_buf, L.img0));
       const int no_tot = c->bufs[c->anchor_buf].C;
       NmsSource src{rows, no_tot, c->no, rows, no_tot, 4 * c->reg_max};
+      if (c->task == kTaskObb) {  // sort -> Fast-NMS keep flags -> rows, in place of the greedy NMS
+        const size_t left = (size_t)(L.B - L.img0) * args->max_det * 7;
+        int* c2 = args->counts_after_dets ? reinterpret_cast<int*>(d_dets + left) + L.img0 : nullptr;
+        e = ym_launch_obb_nms(obb_args(c, rows, L.img0, B, args, d_dets, d_counts, c2), st);
+        break;
+      }
       if (c->task == kTaskPose) {
         // Pose: decode the candidates' keypoints (behind decode_anchors, before any NMS kernel) into their own
         // (B, A, nm) rows and let NMS carry its nm extras from there; the raw head rows stay as the convs wrote them
@@ -879,6 +925,8 @@ int check_nms_args(const ym_infer_args* args, int nc, int task) {
   if (args->max_det > 1024) return fail(YM_EINVAL, "max_det %d > 1024 is not supported", args->max_det);
   if (args->counts_after_dets != 0 && args->counts_after_dets != 1) return fail(YM_EINVAL, "counts_after_dets is 0 or 1");
   if (args->multi_label != 0 && args->multi_label != 1) return fail(YM_EINVAL, "multi_label is 0 or 1");
+  if (args->multi_label && task == kTaskObb)
+    return fail(YM_EINVAL, "multi_label: obb plans are not supported (validation mode is for detect plans)");
   if (args->multi_label && nc > 1) {  // (nc == 1: the single-label path, as upstream's multi_label &= nc > 1)
     if (task != 0)
       return fail(YM_EINVAL, "multi_label: %s plans are not supported (validation mode is for detect plans)",
@@ -1449,6 +1497,29 @@ int ym_infer(ym_ctx* c, const float* d_in, int B, int H, int W, const ym_infer_a
   return infer_impl(c, d_in, B, H, W, args, d_dets, d_counts, stream, false, -1);
 }
 
+// ---------------------------------------------------------------------------------- oriented boxes
+int ym_obb_nms(ym_ctx* c, const float* d_rows, int B, int H, int W, const ym_infer_args* args, float* d_dets,
+               int* d_counts, void* stream) {
+  if (!c) return fail(YM_EINVAL, "null context");
+  if (!c->loaded) return fail(YM_ESTATE, "ym_obb_nms before ym_load_weights");
+  if (c->task != kTaskObb)
+    return fail(YM_EINVAL, "ym_obb_nms: the loaded plan is a %s plan, not an obb plan", ym_task_name(c->task));
+  if (!d_rows || !args || !d_dets || !d_counts) return fail(YM_EINVAL, "null pointer argument");
+  if (int rc = check_shape(B, H, W, "ym_obb_nms: ")) return rc;
+  if (int rc = check_nms_args(args, c->nc, c->task)) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  Launch L;
+  if (int rc = begin_launch(c, B, H, W, st, L)) return rc;
+  // the candidate counts start at 0 (the forward's input op clears them; this entry point is never captured)
+  HIPCK(hipMemsetAsync(nms_view(c->d_arena, c->nms, 0).counts, 0, (size_t)B * 4, st));
+  int* c2 = args->counts_after_dets ? reinterpret_cast<int*>(d_dets + (size_t)B * args->max_det * 7) : nullptr;
+  const ObbArgs a = obb_args(c, d_rows, 0, B, args, d_dets, d_counts, c2);
+  hipError_t e = ym_launch_obb_decode(a, st);
+  if (e == hipSuccess) e = ym_launch_obb_nms(a, st);
+  if (e != hipSuccess) return fail(YM_EHIP, "ym_obb_nms launch: %s", hipGetErrorString(e));
+  return c->mark_last(st);
+}
+
 // ---------------------------------------------------------------------------------- classification
 int ym_classify(ym_ctx* c, const float* d_in, int B, int H, int W, const ym_infer_args* args, float* d_probs, int ld,
                 float* d_logits, int* d_topk, float* d_topk_conf, void* stream) {
@@ -1514,6 +1585,7 @@ int ym_embed(ym_ctx* c, const float* d_in, int B, int H, int W, const ym_infer_a
   if (!c) return fail(YM_EINVAL, "null context");
   if (!c->loaded) return fail(YM_ESTATE, "ym_embed before ym_load_weights");
   if (!d_in || !args || !views || !d_out) return fail(YM_EINVAL, "null pointer argument");
+  if (c->task == kTaskObb) return fail(YM_EINVAL, "ym_embed: obb plans are not supported");
   if (ym_dt_q8(c->dtype))
     return fail(YM_EINVAL, "ym_embed: the quantized plans are not supported (their stored codes need each buffer's "
                            "scale and zero point); use an x3, f16 or f32 plan");
@@ -1920,6 +1992,14 @@ int ym_read_scratch(ym_ctx* c, int which, void* dst, size_t bytes) {
       if (c->task != kTaskClassify) return fail(YM_ESTATE, "YM_SCRATCH_POOLED needs a classify plan");
       off = c->off_cls; cap = (size_t)c->cB * kClsHidden * 4;
       break;
+    case YM_SCRATCH_OBB_BOXES: case YM_SCRATCH_OBB_COV: case YM_SCRATCH_OBB_SCORES: case YM_SCRATCH_OBB_CLS: {
+      if (c->task != kTaskObb) return fail(YM_ESTATE, "the YM_SCRATCH_OBB_* regions need an obb plan");
+      const NmsRegion& r = which == YM_SCRATCH_OBB_BOXES ? c->nms.boxes : which == YM_SCRATCH_OBB_SCORES ? c->nms.scores
+                                                                                                         : c->nms.cls;
+      off = which == YM_SCRATCH_OBB_COV ? c->off_obb_cov : r.off;
+      cap = (size_t)c->cB * (which == YM_SCRATCH_OBB_COV ? (size_t)c->A * 16 : r.stride);
+      break;
+    }
     default: return fail(YM_EINVAL, "unknown scratch region %d", which);
   }
   if (bytes > cap) return fail(YM_EINVAL, "read of %zu bytes exceeds region size %zu", bytes, cap);

@@ -35,6 +35,7 @@ SCALES = {
 
 NC = 80
 NC_CLASSIFY = 1000  # yolo11-cls.yaml's nc (ImageNet)
+NC_OBB = 15         # yolo11-obb.yaml's nc (DOTAv1)
 CLS_HIDDEN = 1280   # Classify's hidden width c_: fixed, not scaled by the model size (csrc/ym_classify.h kClsHidden)
 REG_MAX = 16
 STRIDES = (8, 16, 32)
@@ -99,15 +100,18 @@ class GraphBuilder:
         weight matrices stacked along N: per output channel the same arithmetic as the two convs); fuse="x3" (x3
         plans) both, the conv → 1x1 pairs sized by the pair layout's doubled storage K (the streaming kernel's x3
         FUSE mode) and the Bottlenecks on conv_bneck's x3 mode.
-        nc: classes (default 80; 1 for pose plans).  kpt_shape (pose): (keypoints, 2 | 3).  pad_head=False (pose):
+        nc: classes (default 80; 1 for pose, 15 for obb plans).  kpt_shape (pose): (keypoints, 2 | 3).  pad_head=False
+        (pose, obb):
         the head at its Ultralytics channel counts, for walks over the parameters only (yolomi.synth.calibrate); the
         plan the GPU runs pads them (Detect)."""
         if scale not in SCALES:
             raise ValueError(f"Unsupported size: {scale}")
-        if task not in ("detect", "segment", "pose", "classify"):
-            raise ValueError(f"task {task!r} has no HIP plan (supported: detect, segment, pose, classify)")
+        if task not in ("detect", "segment", "pose", "classify", "obb"):
+            raise ValueError(f"task {task!r} has no HIP plan (supported: detect, segment, pose, classify, obb)")
         if nc is None:
-            nc = 1 if task == "pose" else (NC_CLASSIFY if task == "classify" else NC)
+            nc = {"pose": 1, "classify": NC_CLASSIFY, "obb": NC_OBB}.get(task, NC)
+        if task == "obb" and quant:
+            raise ValueError("obb plans are x3 / f16 / f32: there is no PTQ obb plan")
         if task == "classify" and (quant or nc < 1):
             raise ValueError("classify plans are x3 / f16 / f32 with nc >= 1: there is no PTQ classify plan")
         self.scale, self.task, self.nc, self.quant = scale, task, nc, quant
@@ -307,7 +311,13 @@ class GraphBuilder:
     def Detect(self, i: int, xs: List[View]):
         nc = self.nc
         pose = self.task == "pose"
+        obb = self.task == "obb"
         ncp = nc  # class channels of the anchor row
+        if obb:
+            # OBB head layout, padded as the pose head's: [64 box | nc -> 4k cls | 1 -> 4 angle] (DOTA: pitch 84); the
+            # row NMS emits carries one extra, the decoded angle (nm = 1: rows of 7)
+            pad = (lambda v, d: -(-v // d) * d) if self.pad_head else (lambda v, d: v)
+            ncp, self.ne, self.ne_pad = pad(nc, 4), 1, pad(1, 4)
         if pose:
             # Pose head layout: the class slice and the keypoint slice of the anchor row are padded to multiples of 4
             # (COCO pose: [64 box | 4 cls | 52 kpt], pitch 120) and cv4's hidden width to a multiple of 16 (51 -> 64),
@@ -317,12 +327,12 @@ class GraphBuilder:
             pad = (lambda v, d: -(-v // d) * d) if self.pad_head else (lambda v, d: v)
             ncp, self.nk_pad = pad(nc, 4), pad(self.nk, 4)
         no = ncp + 4 * REG_MAX
-        nm = self.nk_pad if pose else (32 if self.task == "segment" else 0)
+        nm = self.nk_pad if pose else (32 if self.task == "segment" else (1 if obb else 0))
         # no: offset of the nm extras NMS carries in the anchor row (pose: the raw keypoints; the decoded ones NMS
-        # reads live in the runtime's own (B, A, nm) buffer, csrc/ym_kpts.hip)
+        # reads live in the runtime's own (B, A, nm) buffer, csrc/ym_kpts.hip; obb: the raw angle logit)
         self.no, self.nm = no, nm
         self.kpt_off = no if pose else -1
-        anchor = self.buf(no + nm, 0, "anchors", f32=True)
+        anchor = self.buf(no + (self.ne_pad if obb else nm), 0, "anchors", f32=True)
         self.anchor_buf = anchor
         ch0 = xs[0].C
         c2 = max(16, ch0 // 4, REG_MAX * 4)
@@ -389,6 +399,17 @@ class GraphBuilder:
                 self.conv(f"{p}.cv4.{l}.2", self.full(k2), self.nk_pad, 1, 1, View(anchor, no, self.nk_pad),
                           act=False, bn=False, anchor_level=l, pc1=pc4,
                           pc2=self.nk if self.nk_pad != self.nk else None)
+            if obb:  # angle branch cv4: Conv(x,c4,3) → Conv(c4,c4,3) → Conv2d(c4,ne,1), c4 = max(ch0 // 4, ne)
+                c4 = max(ch0 // 4, self.ne)
+                c4p = -(-c4 // 16) * 16 if self.pad_head else c4
+                pc4 = c4 if c4p != c4 else None
+                k1 = self.buf(c4p, f, f"cv4.{l}.0", q=f"{p}.cv4.{l}.0")
+                self.conv(f"{p}.cv4.{l}.0", x, c4p, 3, 1, self.full(k1), pc2=pc4)
+                k2 = self.buf(c4p, f, f"cv4.{l}.1", q=f"{p}.cv4.{l}.1")
+                self.conv(f"{p}.cv4.{l}.1", self.full(k1), c4p, 3, 1, self.full(k2), pc1=pc4, pc2=pc4)
+                self.conv(f"{p}.cv4.{l}.2", self.full(k2), self.ne_pad, 1, 1, View(anchor, no, self.ne_pad),
+                          act=False, bn=False, bias_kind="angle_b", anchor_level=l, pc1=pc4,
+                          pc2=self.ne if self.ne_pad != self.ne else None)
         self.params.append(Param(f"{p}.dfl.conv.weight", (1, REG_MAX, 1, 1), "dfl"))
         self.ops.append(Op("decode", dict(anchor=anchor, nc=nc, nm=nm), f"{p}.decode"))
         self.ops.append(Op("nms", dict(nc=nc, nm=nm), f"{p}.nms"))
@@ -744,7 +765,8 @@ def infer_kpt_shape(sd, kpt_shape: Optional[Tuple[int, int]] = None) -> Optional
 def infer_arch(sd, kpt_shape: Optional[Tuple[int, int]] = None) -> Tuple[str, str, int]:
     """(scale, task, nc) of an Ultralytics-key state dict: the reference takes the architecture from the checkpoint
     (`YOLO(model_path)`, core/model.py:100-110), so a loaded file decides the plan, not the `size` argument.  The
-    task comes from the Proto keys (segment) or cv4 without Proto (pose; its kpt_shape: infer_kpt_shape), nc from the
+    task comes from the Proto keys (segment) or cv4 without Proto (one output row: obb; more: pose, its kpt_shape from
+    infer_kpt_shape), nc from the
     last cls conv, the scale from the graph whose every parameter shape matches."""
     import numpy as np
     if "model.10.linear.weight" in sd:  # a yolo11-cls checkpoint: nc is the Linear's row count
@@ -757,7 +779,8 @@ def infer_arch(sd, kpt_shape: Optional[Tuple[int, int]] = None) -> Tuple[str, st
         raise ValueError(f"state dict matches no YOLO11 scale ({'/'.join(SCALES)}) for task classify, nc={nc}")
     task = "segment" if any(k.startswith("model.23.proto.") for k in sd) else "detect"
     if task == "detect" and any(k.startswith("model.23.cv4.") for k in sd):
-        task = "pose"
+        # cv4 without Proto: one output row is the OBB angle; a pose head has K * ndim >= 2 rows
+        task = "obb" if int(np.shape(sd["model.23.cv4.0.2.bias"])[0]) == 1 else "pose"
     kpt_shape = infer_kpt_shape(sd, kpt_shape) if task == "pose" else None
     key = "model.23.cv3.0.2.bias"
     if key not in sd:

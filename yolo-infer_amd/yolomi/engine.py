@@ -38,7 +38,7 @@ class Engine:
         self.scale, self.task, self.dtype = scale, task, dtype
         self.device = device
         self.qparams = qparams
-        if task in ("pose", "classify") and dtype in QUANT_DTYPES:
+        if task in ("pose", "classify", "obb") and dtype in QUANT_DTYPES:
             raise ValueError(f"{task} plans are x3 / f16 / f32: there is no PTQ {task} plan (dtype {dtype!r})")
         self.graph = GraphBuilder(scale, task, nc=nc, quant=dtype in QUANT_DTYPES,
                                   fuse=fuse_default(dtype), **(dict(kpt_shape=kpt_shape) if kpt_shape else {}))
@@ -55,7 +55,8 @@ class Engine:
         else:
             self.blob = blob if blob is not None else pack_graph(self.graph, state_dict, dtype, qparams)
             self.rt = Runtime(dev_index, self.blob, scale=scale, task=task, dtype=dtype)
-        self.nm = self.graph.nm  # extras per device row (segment: mask coefficients; pose: K·ndim padded to 4)
+        # extras per device row (segment: mask coefficients; pose: K·ndim padded to 4; obb: the angle, rows of 7)
+        self.nm = self.graph.nm
         self.kpt_shape = self.graph.kpt_shape  # pose: (K, ndim); the first nk = K·ndim extras are the keypoints
         self.nk = self.graph.nk if task == "pose" else 0
         self._out: Dict[int, tuple] = {}
@@ -235,6 +236,33 @@ class Engine:
         self.rt.infer(x.data_ptr(), B, H, W, args, dets.data_ptr(), counts.data_ptr(), stream)
         return dets, counts
 
+    def obb_nms(self, rows: torch.Tensor, H: int, W: int, conf=0.25, iou=0.7, max_det=300,
+                classes: Optional[Sequence[int]] = None, agnostic=False, max_nms=30000, max_wh=7680.0):
+        """OBB plans: the rotated decode and Fast-NMS stage of run() alone (csrc/ym_obb.hip) on the caller's head rows:
+        rows (B, A, row) fp32 on the device, laid out as the plan's anchor buffer for an H x W input ([64 DFL | classes
+        padded to 4 | angle logit padded to 4]).  Returns the engine-owned (dets (B, max_det, 7), counts) as run()."""
+        if self.task != "obb":
+            raise ValueError(f"obb_nms() needs an obb plan (this engine holds a {self.task} plan)")
+        from .arch import num_anchors
+        B = rows.shape[0]
+        assert (rows.is_cuda and rows.dtype == torch.float32 and rows.is_contiguous()
+                and tuple(rows.shape[1:]) == (num_anchors(H, W), self.graph.anchor_buf.C))
+        args = Runtime.make_args(conf, iou, max_det, max_nms, agnostic, max_wh, classes=classes, use_graph=False)
+        dets, counts = self.outputs(B, max_det)
+        self.rt.obb_nms(rows.data_ptr(), B, H, W, args, dets.data_ptr(), counts.data_ptr(), self._stream())
+        return dets, counts
+
+    def obb_decoded(self, B: int, H: int, W: int):
+        """OBB plans: what obb_decode wrote for the last run() / obb_nms() (tests), as CPU tensors: boxes (B, A, 4)
+        (cx, cy, w, h), cov (B, A, 4) (theta, A, B, C), scores (B, A), cls (B, A) int32.  Synchronous."""
+        from .arch import num_anchors
+        from .lib import SCRATCH_OBB_BOXES, SCRATCH_OBB_CLS, SCRATCH_OBB_COV, SCRATCH_OBB_SCORES
+        A = num_anchors(H, W)
+        out = (torch.empty((B, A, 4)), torch.empty((B, A, 4)), torch.empty((B, A)), torch.empty((B, A), dtype=torch.int32))
+        for t, which in zip(out, (SCRATCH_OBB_BOXES, SCRATCH_OBB_COV, SCRATCH_OBB_SCORES, SCRATCH_OBB_CLS)):
+            self.rt.read_scratch(which, t.data_ptr(), t.numel() * 4)
+        return out
+
     def track(self, x: torch.Tensor, cfg: Optional[Dict] = None, persist: bool = True, capacity: int = 0, **kw):
         """run() followed by the tracker launch (csrc/ym_track.hip) on the same stream, with no host sync in between:
         image b of the batch is video stream b of a ByteTrack state that lives in device memory.  cfg: the ByteTrack
@@ -250,6 +278,8 @@ class Engine:
         from .lib import TRACK_DEFAULTS, TRACK_MAX_DET
         if self.task == "segment":
             raise NotImplementedError("tracking is offered for detect and pose plans; segment masks are not re-gathered")
+        if self.task == "obb":
+            raise NotImplementedError("tracking is offered for detect and pose plans; rotated boxes are not tracked")
         full = dict(TRACK_DEFAULTS, **(cfg or {}))
         max_det = int(kw.get("max_det", 300))
         if not 1 <= max_det <= TRACK_MAX_DET:
@@ -383,6 +413,8 @@ class Engine:
         ValueError: an index outside 0..22, a non-integer, an empty list, a layer this plan does not store, or a
         quantized plan."""
         from .arch import normalize_embed
+        if self.task == "obb":
+            raise NotImplementedError("embeddings are not offered for obb plans")
         in_eps, _, bm = self._check_input(x, in_eps, 1, batch_max)
         n_layers = len(self.graph.layers)  # 23, or a classify graph's 10; the default is upstream's len(model) - 2
         layers = normalize_embed((n_layers - 1,) if layers is None else layers, n_layers)

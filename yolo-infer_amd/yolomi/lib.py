@@ -24,8 +24,9 @@ class ModelDesc(C.Structure):
                 ("dtype", C.c_int), ("reserved", C.c_int * 2)]
 
 
-TASK_CODES = {"detect": 1, "segment": 2, "pose": 3, "classify": 4}
+TASK_CODES = {"detect": 1, "segment": 2, "pose": 3, "classify": 4, "obb": 5}
 SCRATCH_KEYS, SCRATCH_COUNTS, SCRATCH_KPTS, SCRATCH_POOLED = 0, 1, 2, 3  # ym_read_scratch regions (include/yolomi.h)
+SCRATCH_OBB_BOXES, SCRATCH_OBB_COV, SCRATCH_OBB_SCORES, SCRATCH_OBB_CLS = 4, 5, 6, 7  # obb plans: obb_decode's outputs
 DTYPE_CODES = {"f16": 1, "f32": 2, "i8": 3, "f8": 4, "x3": 5}
 
 
@@ -83,6 +84,7 @@ def load_library(path: os.PathLike = LIB_PATH):
         "ym_create": (I, [I, C.POINTER(ModelDesc), C.POINTER(P)]),
         "ym_load_weights": (I, [P, P, C.c_size_t]),
         "ym_infer": (I, [P, P, I, I, I, C.POINTER(InferArgs), P, P, P]),
+        "ym_obb_nms": (I, [P, P, I, I, I, C.POINTER(InferArgs), P, P, P]),
         "ym_profile": (I, [P, P, I, I, I, C.POINTER(InferArgs), P, P, P, F, I]),
         "ym_calibrate": (I, [P, P, I, I, I, C.POINTER(InferArgs), P, P, C.POINTER(C.c_void_p), I, P]),
         "ym_profile_replay": (I, [P, P, I, I, I, C.POINTER(InferArgs), P, P, P, I, F, I]),
@@ -141,7 +143,7 @@ def load_library(path: os.PathLike = LIB_PATH):
 
 
 EXPORTED = ("ym_create", "ym_load_weights", "ym_broadcast_weights", "ym_broadcast_weights_local", "ym_rccl_get_unique_id", "ym_rccl_comm_init",
-            "ym_rccl_comm_destroy", "ym_infer", "ym_input_max", "ym_calibrate", "ym_masks", "ym_masks_slots", "ym_masks_native",
+            "ym_rccl_comm_destroy", "ym_infer", "ym_obb_nms", "ym_input_max", "ym_calibrate", "ym_masks", "ym_masks_slots", "ym_masks_native",
             "ym_letterbox", "ym_profile", "ym_profile_replay", "ym_tune", "ym_get_op_cfg", "ym_set_op_cfg", "ym_get_op_cfg_taken", "ym_get_op_variant",
             "ym_op_variant_count", "ym_num_ops",
             "ym_op_name",
@@ -434,6 +436,12 @@ class Runtime:
 
     def read_buffer(self, buf: int, dst_ptr: int, nbytes: int):
         _check(self.lib.ym_read_buffer(self.ctx, buf, C.c_void_p(dst_ptr), nbytes))
+
+    def obb_nms(self, rows_ptr: int, B: int, H: int, W: int, args: InferArgs, dets_ptr: int, counts_ptr: int,
+                stream: int):
+        """ym_obb_nms: an obb plan's rotated decode + NMS stage on the caller's (B, A, row) head rows."""
+        _check(self.lib.ym_obb_nms(self.ctx, C.c_void_p(rows_ptr), B, H, W, C.byref(args), C.c_void_p(dets_ptr),
+                                   C.c_void_p(counts_ptr), C.c_void_p(stream)))
 
     def read_scratch(self, which: int, dst_ptr: int, nbytes: int):
         _check(self.lib.ym_read_scratch(self.ctx, which, C.c_void_p(dst_ptr), nbytes))

@@ -35,7 +35,7 @@ MAGIC = 0x4C504D59
 VERSION = 1
 OP_IDS = {"input": 1, "conv": 2, "dwconv": 3, "sppf": 4, "attn": 5, "decode": 6, "nms": 7, "requant": 8,
           "classify": 9}
-TASK_IDS = {"detect": 0, "segment": 1, "pose": 2, "classify": 3}
+TASK_IDS = {"detect": 0, "segment": 1, "pose": 2, "classify": 3, "obb": 4}
 DTYPES = {"f16": 0, "f32": 1, "i8": 2, "f8": 3, "x3": 4}
 QUANT_DTYPES = ("i8", "f8")  # one-byte PTQ plans: int8 affine (torch.ao qconfig) and fp8 e4m3 (yolomi/quant.py)
 BK = 64  # conv K is padded to the kernel K step (csrc/ym_conv.hip KSTEP)
@@ -193,9 +193,10 @@ def pack_graph(g: GraphBuilder, sd: Dict[str, np.ndarray], dtype: str = "f16", q
     pose = g.task == "pose"
     if g.task == "classify" and quant:
         raise ValueError(f"classify plans are x3 / f16 / f32: there is no PTQ classify plan (dtype {dtype!r})")
-    if pose and quant:
-        raise ValueError(f"pose plans are x3 / f16 / f32: there is no PTQ pose plan (dtype {dtype!r})")
-    if pose and not g.pad_head:
+    obb = g.task == "obb"
+    if (pose or obb) and quant:
+        raise ValueError(f"{g.task} plans are x3 / f16 / f32: there is no PTQ {g.task} plan (dtype {dtype!r})")
+    if (pose or obb) and not g.pad_head:
         raise ValueError("GraphBuilder(pad_head=False) is not a plan the GPU runs")
     check_state_dict(g, sd)
     if quant:
@@ -232,7 +233,7 @@ def pack_graph(g: GraphBuilder, sd: Dict[str, np.ndarray], dtype: str = "f16", q
         r = {"kind": OP_IDS[op.kind]}  # OP_FIELDS slots of this op
         if op.kind == "conv":
             w, b = _conv_weights(a, sd)  # (N, k, k, cin)
-            if pose:
+            if pose or obb:
                 w, b = _pad_channels(w, b, a["c2"], a["c1"])
             src0 = a["src0"]
             C0 = src0.C
@@ -283,7 +284,7 @@ def pack_graph(g: GraphBuilder, sd: Dict[str, np.ndarray], dtype: str = "f16", q
                 if dtype not in ("f16", "x3"):
                     raise ValueError(f"op {op.name}: fused conv pairs are f16 / x3 only")
                 w2, b2 = _conv_weights(pair, sd)  # (N2, k2, k2, N)
-                if pose:
+                if pose or obb:
                     w2, b2 = _pad_channels(w2, b2, pair["c2"], pair["c1"])
                 N2, k2 = w2.shape[0], pair["k"]
                 assert w2.shape[1:] == (k2, k2, N)
@@ -395,6 +396,8 @@ def pack_graph(g: GraphBuilder, sd: Dict[str, np.ndarray], dtype: str = "f16", q
         no=g.no, scale=ord(g.scale))  # (scale: checked against ym_model_desc.scale)
     if pose:  # nm = nk_pad, the extras NMS carries
         hdr = hdr._replace(kpt_k=g.kpt_shape[0], kpt_ndim=g.kpt_shape[1], kpt_off=g.kpt_off, cls_pad=g.no - 4 * REG_MAX)
+    if obb:  # nm = 1 (the decoded angle of a row); the raw angle logit at anchor-row offset no, behind cls_pad classes
+        hdr = hdr._replace(cls_pad=g.no - 4 * REG_MAX)
     head = struct.pack("<32i", *hdr)
     bufs = b"".join(struct.pack("<8i", b.Cs or b.C, b.f, int(b.f32), 0, 0, 0, 0, 0) for b in g.buffers)
     ops = b"".join(struct.pack("<32i", *rr) for rr in op_recs)

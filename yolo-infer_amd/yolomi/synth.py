@@ -95,6 +95,8 @@ def synth_param(name: str, shape: Tuple[int, ...], kind: str, seed: int, extra: 
         w = w + 0.5 * normal(key, n)
     elif kind == "bias":
         w = 0.1 * normal(key, n)
+    elif kind == "angle_b":  # OBB angle logit bias 0: theta = (sigmoid(z) - 0.25) pi spreads around pi / 4
+        w = np.zeros(n)
     elif kind == "linear_w":  # Classify's Linear: class logits of U[0,1) images with a standard deviation of order 1
         w = normal(key, n) * (LINEAR_GAIN / math.sqrt(shape[1]))
     elif kind == "linear_b":
@@ -153,6 +155,8 @@ DETECT_Z = 5.5
 # pose plans (one class): DETECT_Z counts on the max over 80 class scores; with a single class it leaves no anchor
 # above conf 0.25 (max score ~0.06 on yolo11n).  1.5 sigma gives tens of candidates per U[0,1) image
 POSE_DETECT_Z = 1.5
+# obb plans (15 classes): between the two, for the same reason
+OBB_DETECT_Z = 3.0
 SPPF_SHIFT = (2.7, 3.7, 4.2)
 SPPF_VAR = (1.45, 1.27, 1.12)
 ATTN_VAR = 0.6
@@ -207,7 +211,7 @@ def calibrate(graph, sd: Dict[str, np.ndarray], in_mean: float = 0.5, in_var: fl
                 bias_name = key + ".bias"
                 if ".cv3." in key:  # class logits: place the bias DETECT_Z std below the conf=0.25 logit
                     thr = math.log(0.25 / 0.75)
-                    z = POSE_DETECT_Z if graph.task == "pose" else DETECT_Z
+                    z = {"pose": POSE_DETECT_Z, "obb": OBB_DETECT_Z}.get(graph.task, DETECT_Z)
                     sd[bias_name] = (thr - z * np.sqrt(vo) - mo).astype(np.float32)
                 mo = mo + sd[bias_name].astype(np.float64)
             if a["act"]:
@@ -262,7 +266,7 @@ def calibrate(graph, sd: Dict[str, np.ndarray], in_mean: float = 0.5, in_var: fl
 
 def synth_weights(scale: str = "n", task: str = "detect", seed: int = 0, nc: int = None) -> Dict[str, np.ndarray]:
     """Ultralytics-style state dict of synthetic weights with calibrated BN stats for yolo11{scale}[-seg | -pose |
-    -cls].  nc: classes (default: the task's, 1000 for classify)."""
+    -cls | -obb].  nc: classes (default: the task's, 1000 for classify, 15 for obb)."""
     from .arch import GraphBuilder
     g = GraphBuilder(scale, task, nc=nc, pad_head=False)  # (pose: the head at its parameters' own channel counts)
     sd = synth_state_dict([(p.name, p.shape, p.kind, p.extra) for p in g.params], seed)

@@ -1,7 +1,7 @@
 """The receive path of the init-time weight broadcast on one GPU (SURVEY §4.4's fake backend).
 
 `ym_broadcast_weights_local` runs the per-rank steps of `ym_broadcast_weights` — staging buffer, the root's upload,
-a receiver's copy-out, `ym_load_weights`, the verdict every rank agrees on (csrc/ym_runtime.cpp BcastRank) — with
+a receiver's copy-out, `ym_load_weights`, the verdict every rank agrees on (csrc/ym_rt_dist.cpp BcastRank) — with
 the ranks as contexts of this process and device-to-device copies where RCCL would move the chunks.  So the code
 that the RCCL transport's non-root ranks run executes here on a one-GPU box."""
 import pytest

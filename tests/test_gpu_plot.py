@@ -165,6 +165,19 @@ def test_segment_batch_annotate_equals_oracle():
     out = torch.empty((2, 12, 6 + eng.nm), dtype=torch.float32, device=DEV)
     dets, counts = eng.run(x, conf=0.01, max_det=12, dets_out=out)
     slots, _ = eng.masks_slots(out, counts[:2], 8, 128, 160)  # 8 mask slots for up to 12 rows: rows 8.. have no mask
+    # the two-kernel mask path's scratch on this one context: 16 slots, then 80 (more than any call before: it is
+    # replaced), then 16 again in the larger buffer — the same masks each time, and the ones painted below
+    first = slots.clone()
+    out40 = torch.empty((2, 40, 6 + eng.nm), dtype=torch.float32, device=DEV)
+    _, counts40 = eng.run(x, conf=0.01, max_det=40, dets_out=out40)
+    big, _ = eng.masks_slots(out40, counts40[:2], 40, 128, 160)
+    big = big.clone()
+    dets, counts = eng.run(x, conf=0.01, max_det=12, dets_out=out)
+    slots, _ = eng.masks_slots(out, counts[:2], 8, 128, 160)
+    for b in range(2):  # (NMS rows come best first: the 12-row call's are the 40-row call's first 12)
+        k = min(int(counts[b]), 8)
+        assert torch.equal(slots[b, :k], first[b, :k])
+        assert torch.equal(out40[b, :k], out[b, :k]) and torch.equal(big[b, :k], slots[b, :k])
     img = eng.annotate(x, out, counts[:2].contiguous(), masks=slots).cpu().numpy()
     n = counts[:2].tolist()
     assert max(n) > 0

@@ -1,4 +1,4 @@
-// Annotated frames (csrc/ym_annot.hip; driven by ym_annotate in ym_runtime.cpp): Results.plot()'s boxes, labels,
+// Annotated frames (csrc/ym_annot.hip; driven by ym_annotate in ym_rt_post.cpp): Results.plot()'s boxes, labels,
 // masks, keypoints, skeletons and track ids, composited per pixel on the device.  DESIGN.md §17 states the rules.
 //
 // This header holds everything that decides a pixel and is shared by the kernels and a stand-alone host program

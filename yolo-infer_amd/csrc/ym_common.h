@@ -222,7 +222,7 @@ constexpr int YM_CTL_SLOTS = 16, YM_CTL_STRIDE = 16;  // ints
 // YM_STATS_GROUPS group tickets 128 B apart
 constexpr int YM_STATS_GROUPS = 16;
 constexpr int YM_CTL_BYTES = (YM_CTL_SLOTS * YM_CTL_STRIDE + 64 + 1024 + 32 * YM_STATS_GROUPS) * 4;
-static_assert(YM_CTL_BYTES <= 8192, "ym_input_max's region of the context scratch (ym_runtime.cpp d_misc)");
+static_assert(YM_CTL_BYTES <= 8192, "ym_input_max's region of the context scratch (ym_runtime.h kMiscBcast)");
 __device__ __forceinline__ float ym_input_max(const float* ctl) {
   const int* c = reinterpret_cast<const int*>(ctl);
   int m = c[0];

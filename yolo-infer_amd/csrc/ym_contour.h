@@ -1,4 +1,4 @@
-// Instance polygons behind the mask stages (csrc/ym_contour.hip; driven by ym_mask_contours in ym_runtime.cpp): per
+// Instance polygons behind the mask stages (csrc/ym_contour.hip; driven by ym_mask_contours in ym_rt_post.cpp): per
 // 0/1 byte plane, the outer border of one top-level 8-connected component, traced by Suzuki-Abe border following and
 // compressed like OpenCV's CHAIN_APPROX_SIMPLE (the definition is DESIGN.md §18's; tests/contour_oracle.py is its
 // sequential restatement).

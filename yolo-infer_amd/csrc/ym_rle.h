@@ -1,4 +1,4 @@
-// COCO run-length encoding of mask planes (csrc/ym_rle.hip; driven by ym_mask_rle in ym_runtime.cpp):
+// COCO run-length encoding of mask planes (csrc/ym_rle.hip; driven by ym_mask_rle in ym_rt_post.cpp):
 // pycocotools' rleEncode / rleToString.  Pixel (x, y) of an H x W plane has the column-major index x * H + y, a
 // transition is an index whose pixel differs from the one before it (pixel -1 is 0), the counts are the distances
 // between transitions (the last one reaches H * W), and count k is written to the string as count[k] - count[k - 2]

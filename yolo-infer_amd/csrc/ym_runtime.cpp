@@ -3,9 +3,6 @@
 // This is the native replacement for the Ultralytics predictor loop that `YOLO11Model.predict` delegates to
 // (/root/reference/core/model.py:118-133): per batch it replays ONE captured HIP graph of the whole forward
 // (input /255 rule → 80+ fused conv launches → attention → decode → NMS), so the Python host issues one call.
-#include <hip/hip_runtime.h>
-
-#include <dlfcn.h>
 #include <execinfo.h>
 #include <signal.h>
 #include <unistd.h>
@@ -15,22 +12,11 @@
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
-#include <cstring>
 #include <string>
-#include <type_traits>
-#include <vector>
 
-#include "../../include/yolomi.h"
-#include "ym_common.h"
-#include "ym_plan.h"
-#include "ym_nms_ws.h"
+#include "ym_runtime.h"
 #include "ym_embed.h"
 #include "ym_tta.h"
-#include "ym_track.h"
-#include "ym_annot.h"
-#include "ym_contour.h"
-#include "ym_rle.h"
-#include "ym_classify.h"
 
 // process-wide debug switches (ym_set_debug; include/yolomi.h YM_DBG_*): set from the environment once, then only by
 // the setter — a launch reads an atomic instead of calling getenv (getenv per launch is not thread-safe
@@ -99,6 +85,8 @@ __attribute__((constructor)) void install_segv_trace() {
   sigaction(SIGBUS, &sa, &g_prev_sig[1]);
 }
 
+}  // namespace
+
 int fail(int code, const char* fmt, ...) {
   char buf[512];
   va_list ap;
@@ -109,80 +97,20 @@ int fail(int code, const char* fmt, ...) {
   return code;
 }
 
-#define HIPCK(x)                                                                              \
-  do {                                                                                        \
-    hipError_t e_ = (x);                                                                      \
-    if (e_ != hipSuccess) return fail(YM_EHIP, "%s: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-  } while (0)
-
-constexpr int kSplitCounters = 16384;  // split-K tiles per conv launch (csrc/ym_conv_dma.hip)
-constexpr int kChainCtl = 4096;        // ready counters (+ done, give-up words) of the persistent chain kernel
-constexpr float kPresortConf = 0.1f;  // NMS keys presorted over several workgroups below this conf (ym_nms.hip)
-constexpr int kMaxLanes = 4;           // concurrent batch slices in one forward graph (<= GPU_MAX_HW_QUEUES)
-constexpr size_t kMaxGraphs = 16;      // captured forwards cached per context (the oldest is retired first)
-// ym_ctx::d_misc and its sub-regions: ym_input_max's statistics (slots, ticket, partials), the control words of
-// ym_broadcast_weights, and the words that stand in for the outputs of a forward that writes none (never written)
-constexpr size_t kMiscBytes = 16384;
-constexpr size_t kMiscStats = 0, kMiscBcast = 8192, kMiscNoDets = 12288;
-static_assert(kMiscStats + YM_CTL_BYTES <= kMiscBcast && kMiscBcast + 2 * sizeof(unsigned long long) <= kMiscNoDets &&
-                  kMiscNoDets < kMiscBytes, "the d_misc sub-regions fit in kMiscBytes and do not overlap");
 static_assert(sizeof(MlState) == kMlStateBytes, "ym_nms_ws.h sizes the multi-label state rows");
 
-// What one launch_forward / launch_op call works on.  A value built per call (and per lane or branch stream inside
-// launch_forward), never context state: nothing is left to reset on an early return.
-// Where a ym_classify call's results go (null members: the context's own scratch, ym_ctx::cls_view)
-struct ClsOut {
-  float* probs = nullptr;
-  long long ld = 0;
-  float* logits = nullptr;
-  int* topk = nullptr;
-  float* topk_conf = nullptr;
-};
-
-struct Launch {
-  int lane = 0;           // split-K slab / counter region of the stream the ops go to
-  int img0 = 0;           // first image of the ops being launched (a lane's slice of the batch)
-  int B = 0;              // images of the whole call (all lanes)
-  bool skip_nms = false;  // ym_tta_forward: the passes' candidates are merged first (ym_tta_nms)
-  int stop = -1;          // ym_embed: the last op of the truncated forward (-1: a whole forward)
-  bool pool = true;       // (stop >= 0) the embedding pooling stage follows; false: YM_DBG_STOP, a test's bare stop
-  float* const* calib_raw = nullptr;  // ym_calibrate: per-op pre-activation output buffers (f32 plans)
-  ClsOut cls;             // ym_classify: the caller's outputs
-};
-
-struct GraphKey {
-  int B, H, W;
-  int skip_nms;  // 1: a ym_tta_forward capture (no NMS stage)
-  int embed_stop;  // ym_embed captures: 1 + the last op of the truncated forward (0: a whole forward) ...
-  int embed_n;     // ... the views pooled behind it (GraphEntry::embed_views) ...
-  const void* embed_out;  // ... and where their means go
-  long long embed_ld;
-  ClsOut cls;  // ym_classify captures: the outputs the head's launches write
-  const void* in;
-  const void* dets;
-  const void* counts;
-  const void* stream_unused;
-  ym_infer_args args;
-  bool operator==(const GraphKey& o) const { return memcmp(this, &o, sizeof(GraphKey)) == 0; }
-};
-
-// A captured forward.  The detection rows are the caller's (a fresh tensor per predict() call, so the Results of
-// earlier calls stay valid without a copy): the key leaves `dets` out when the graph's NMS nodes were found, and a
-// replay for other rows re-points those nodes (hipGraphExecKernelNodeSetParams; the lanes' row offsets kept).
-struct GraphEntry {
-  GraphKey key;
-  hipGraph_t graph;
-  hipGraphExec_t exec;
-  float* dets = nullptr;                 // the rows the exec's NMS nodes write now
-  hipEvent_t done = nullptr;             // recorded behind every launch of `exec` (retire_graph waits on it)
-  std::vector<hipGraphNode_t> nms_nodes;  // empty: dets is part of the key
-  std::vector<NmsArgs> nms_args;
-  std::vector<ym_embed_view> embed_views;  // a ym_embed capture: the pooled views (compared with the key)
-};
+// The device under DevBuf (ym_devbuf.h)
+int ym_dev_alloc(void** p, size_t bytes, const char* what, size_t n) {
+  const hipError_t e = hipMalloc(p, bytes);
+  if (e == hipSuccess) return YM_OK;
+  return fail(YM_ENOMEM, (std::string(what) + ": %s").c_str(), n, hipGetErrorString(e));  // (what: one %zu, for n)
+}
+int ym_dev_free(void* p) { HIPCK(hipFree(p)); return YM_OK; }
+int ym_dev_sync() { HIPCK(hipDeviceSynchronize()); return YM_OK; }
 
 // The NMS kernel nodes of a captured forward and their arguments (false when none is found: the caller keys the
 // graph on the output pointer instead)
-bool find_nms_nodes(GraphEntry& ge) {
+static bool find_nms_nodes(GraphEntry& ge) {
   size_t nn = 0;
   if (hipGraphGetNodes(ge.graph, nullptr, &nn) != hipSuccess || nn == 0) return false;
   std::vector<hipGraphNode_t> nodes(nn);
@@ -207,7 +135,7 @@ bool find_nms_nodes(GraphEntry& ge) {
   return true;
 }
 
-int repoint_dets(GraphEntry& ge, float* d_dets) {
+static int repoint_dets(GraphEntry& ge, float* d_dets) {
   for (size_t j = 0; j < ge.nms_nodes.size(); ++j) {
     NmsArgs na = ge.nms_args[j];
     na.dets = d_dets + (na.dets - ge.dets);
@@ -226,8 +154,6 @@ int repoint_dets(GraphEntry& ge, float* d_dets) {
   return YM_OK;
 }
 
-// Destroy a captured forward only after its last launch has finished on whatever stream it was replayed on: the
-// HIP runtime may still hold the exec's launch state (kernel arguments, the packet chain) while it is in flight.
 void retire_graph(GraphEntry& g) {
   if (g.done) {
     (void)hipEventSynchronize(g.done);
@@ -238,221 +164,6 @@ void retire_graph(GraphEntry& g) {
   if (g.graph) (void)hipGraphDestroy(g.graph);
   g.exec = nullptr;
   g.graph = nullptr;
-}
-
-}  // namespace
-
-struct ym_ctx {
-  int device = 0;
-  ym_model_desc desc{};
-  bool loaded = false;
-  // plan
-  int dtype = YM_DT_F16, task = 0, nc = 80, nm = 0, reg_max = 16, nl = 3;
-  int strides[4] = {8, 16, 32, 0};
-  int input_buf = -1, anchor_buf = -1, proto_buf = -1, no = 0;
-  int kpt_K = 0, kpt_ndim = 0, kpt_off = 0;  // pose plans: keypoints, 2 | 3 values each, raw offset in the anchor row
-  float* d_lowres = nullptr;  // Segment mask assembly scratch (ym_masks)
-  char* d_misc = nullptr;     // 16 KB: ym_input_max statistics region, ym_broadcast_weights control words
-  size_t lowres_bytes = 0;
-  std::vector<BufDesc> bufs;
-  std::vector<Op> ops;
-  char* d_weights = nullptr;
-  std::vector<char> blob_host;  // the loaded blob as received (what ym_broadcast_weights sends from the root)
-  size_t off_wstem = 0;  // stem weights re-laid out as fp32 [27][N] behind the blob's weights (ym_stem.hip)
-  size_t off_wtap0 = 0;            // int8 plans: the 3x3 convs' [9][N] int32 tap sums, behind the stem weights
-  std::vector<size_t> off_wtap;    // per op: 1 + byte offset from off_wtap0 (0: none)
-  // branch schedule of a one-lane forward (ops of independent DAG branches on up to kMaxLanes streams)
-  int nbr = 1;
-  std::vector<int> br_of;                // per op: branch stream
-  std::vector<std::vector<int>> br_wait; // per op: earlier ops (other streams) whose events it waits for
-  std::vector<char> br_rec;              // per op: record its event after it
-  std::vector<hipEvent_t> op_ev;
-  size_t wbytes = 0;
-  // workspace for the current (B, H, W)
-  int cB = 0, cH = 0, cW = 0;
-  char* d_arena = nullptr;
-  size_t arena_bytes = 0;
-  std::vector<size_t> buf_off;
-  size_t off_ctl = 0, off_slab = 0, off_cnt = 0, off_chain = 0, off_kpts = 0, slab_bytes = 0;
-  // obb plans: per anchor the (theta, A, B, C) float4 of obb_decode, the sorted ObbEntry and the keep byte, per image
-  // the sorted count (csrc/ym_obb.hip); the regions hold cB images each
-  size_t off_obb_cov = 0, off_obb_sorted = 0, off_obb_keep = 0, off_obb_nsel = 0;
-  // classify plans: the head's op and its scratch in the arena — pooled (B, 1280), then logits, probs (B, nc each),
-  // top-k classes and probabilities (B, kClsTopK each), all fp32 / int32; a call's own outputs replace the last four
-  int cls_op = -1;
-  size_t off_cls = 0;
-  size_t cls_bytes(int nB) const { return (size_t)nB * (kClsHidden + 2 * (size_t)nc + 2 * kClsTopK) * 4; }
-  int A = 0;
-  // the NMS stage's scratch in the arena.  Multi-label mode (ym_infer_args.multi_label): its regions join at the first
-  // workspace (re)build after a multi-label call was seen (check_call sets ml_want; nms.ml: they are there), so a
-  // context that never validates pays nothing
-  NmsScratch nms;
-  bool ml_want = false;
-  int lvl_W[4] = {0}, lvl_off[4] = {0};
-  hipStream_t cap_stream = nullptr;
-  // lanes: the batch is cut into image slices whose op chains are captured as parallel branches of one graph, so
-  // the fixed per-launch latency of one slice's small kernels overlaps the other slices' work
-  hipStream_t lane_streams[kMaxLanes] = {};
-  hipEvent_t fork_ev = nullptr, join_ev[kMaxLanes] = {};
-  std::vector<GraphEntry> graphs;
-  // feature embeddings (ym_embed): the forward stops early (Launch::stop) and the pooling stage (csrc/ym_embed.hip)
-  // reads embed_views into embed_out; d_embed holds the chunk partials of large maps
-  std::vector<ym_embed_view> embed_views;
-  float* embed_out = nullptr;
-  long long embed_ld = 0;
-  float* d_embed = nullptr;
-  size_t embed_floats = 0;
-  // annotated frames (ym_annotate): the records of the B x max_det detection slots, grown on demand
-  AnnotRec* d_annot = nullptr;
-  size_t annot_recs = 0;
-  // instance polygons (ym_mask_contours): n CtSel records, then (planes too large for LDS only) n bit planes of
-  // ym_ct_words(H, W) words; grown on demand
-  char* d_contour = nullptr;
-  size_t contour_bytes = 0;
-  // run-length encoding (ym_mask_rle): per (plane, strip) two RleAgg, the set pixels and the strip's bit words, per
-  // plane one RleAgg (ym_rle.h RleScratch); grown on demand
-  char* d_rle = nullptr;
-  size_t rle_bytes = 0;
-  // test-time augmentation: ym_tta_forward launches the forward without its NMS stage; the merged candidate set and the
-  // NMS scratch over it (ym_tta_nms) belong to the first pass's context and are rebuilt only when the shape changes
-  struct TtaWs {
-    int B = 0, H = 0, W = 0, nc = 0;
-    char* d = nullptr;
-    NmsScratch ws;  // over ws.A merged anchors; multi-label regions and class rows on demand (ws.ml)
-  } tta;
-  // the previous forward: every forward of a context uses the same arena, NMS scratch, split-K slabs /
-  // counters and input_stats ticket, so a forward launched on another stream than the previous one first waits for
-  // it (ym_infer: hipStreamWaitEvent); last_ev is the replayed graph's `done` event or fwd_ev (eager forwards)
-  hipStream_t last_st = nullptr;
-  hipEvent_t last_ev = nullptr, fwd_ev = nullptr;
-  int order_after_last(hipStream_t st) {
-    if (last_ev && last_st != st) {
-      const hipError_t e = hipStreamWaitEvent(st, last_ev, 0);
-      if (e != hipSuccess) return fail(YM_EHIP, "stream order: %s", hipGetErrorString(e));
-    }
-    return YM_OK;
-  }
-  int record_last(hipEvent_t ev, hipStream_t st) {
-    HIPCK(hipEventRecord(ev, st));
-    last_ev = ev;
-    last_st = st;
-    return YM_OK;
-  }
-  int mark_last(hipStream_t st) {  // behind an eager forward (or any other use of the shared scratch) on `st`
-    if (!fwd_ev) HIPCK(hipEventCreateWithFlags(&fwd_ev, hipEventDisableTiming));
-    return record_last(fwd_ev, st);
-  }
-  int launch_graph(GraphEntry& g, hipStream_t st) {
-    HIPCK(hipGraphLaunch(g.exec, st));
-    return record_last(g.done, st);
-  }
-  void retire(GraphEntry& g) {  // retire_graph, forgetting last_ev when it is that graph's event (now complete)
-    if (g.done && g.done == last_ev) last_ev = nullptr;
-    retire_graph(g);
-  }
-  std::vector<hipEvent_t> prof_events;
-  // per-shape, per-op conv tile configuration (-1 = heuristic); set by ym_tune / ym_set_op_cfg
-  struct ShapeCfg {
-    int B, H, W;
-    std::vector<int> cfg;
-  };
-  std::vector<ShapeCfg> cfgs;
-  const std::vector<int>* find_cfg(int B, int H, int W) const {
-    for (const auto& e : cfgs)
-      if (e.B == B && e.H == H && e.W == W) return &e.cfg;
-    return nullptr;
-  }
-  void put_cfg(int B, int H, int W, std::vector<int> v) {
-    for (auto& e : cfgs)
-      if (e.B == B && e.H == H && e.W == W) { e.cfg = std::move(v); return; }
-    cfgs.push_back({B, H, W, std::move(v)});
-  }
-  void drop_cfg(int B, int H, int W) {
-    for (size_t i = 0; i < cfgs.size(); ++i)
-      if (cfgs[i].B == B && cfgs[i].H == H && cfgs[i].W == W) { cfgs.erase(cfgs.begin() + i); return; }
-  }
-  // tests (ym_get_op_cfg_taken): per op of the last forward launched, whether its pinned cfg was the kernel that ran
-  // ([2i]: the op, or the first conv of a split pair; [2i + 1]: the pair's second conv; ym_launch_conv's `taken`)
-  std::vector<int> taken;
-  // tests (ym_get_op_variant): per op of that forward, the kernel instantiation a depthwise / SPPF / attention op
-  // launched (the launchers' `variant`; -1: another kind, not launched, int8 / fp8)
-  std::vector<int> variant;
-  int tkB = 0, tkH = 0, tkW = 0;
-  int op_cfg(long i, int B) const {  // for the current workspace height/width
-    const std::vector<int>* v = find_cfg(B, cH, cW);
-    return (v && i >= 0 && i < (long)v->size()) ? (*v)[i] : -1;
-  }
-
-  ~ym_ctx() {
-    (void)hipSetDevice(device);
-    clear_graphs();
-    for (auto e : prof_events) (void)hipEventDestroy(e);
-    if (d_arena) (void)hipFree(d_arena);
-    if (d_weights) (void)hipFree(d_weights);
-    if (d_lowres) (void)hipFree(d_lowres);
-    if (d_misc) (void)hipFree(d_misc);
-    if (tta.d) (void)hipFree(tta.d);
-    if (d_embed) (void)hipFree(d_embed);
-    if (d_annot) (void)hipFree(d_annot);
-    if (d_contour) (void)hipFree(d_contour);
-    if (d_rle) (void)hipFree(d_rle);
-    if (cap_stream) (void)hipStreamDestroy(cap_stream);
-    for (int l = 0; l < kMaxLanes; ++l) {
-      if (lane_streams[l]) (void)hipStreamDestroy(lane_streams[l]);
-      if (join_ev[l]) (void)hipEventDestroy(join_ev[l]);
-    }
-    if (fork_ev) (void)hipEventDestroy(fork_ev);
-    if (fwd_ev) (void)hipEventDestroy(fwd_ev);
-    for (hipEvent_t e : op_ev) (void)hipEventDestroy(e);
-  }
-  void clear_graphs() {
-    for (auto& g : graphs) retire(g);
-    graphs.clear();
-  }
-  int buf_P(int b) const {
-    const BufDesc& d = bufs[b];
-    if (d.f == 0) return A;
-    return (cH / d.f) * (cW / d.f);
-  }
-  int buf_H(int b) const { return bufs[b].f == 0 ? 1 : cH / bufs[b].f; }
-  int buf_Wd(int b) const { return bufs[b].f == 0 ? A : cW / bufs[b].f; }
-  int elem(int b) const { return (bufs[b].f32 || ym_dt_f32s(dtype)) ? 4 : (ym_dt_q8(dtype) ? 1 : 2); }
-  template <typename T> const T* wptr(int32_t off) const {  // a record's *_off slot: unsigned bytes into the weights
-    return reinterpret_cast<const T*>(d_weights + (size_t)(uint32_t)off);
-  }
-  int* variant_of(const Op& op) { return variant.size() == ops.size() ? &variant[&op - ops.data()] : nullptr; }
-  float* raw_of(const Launch& L, const Op& op) const { return L.calib_raw ? L.calib_raw[&op - ops.data()] : nullptr; }
-  // buffer b from image img0 on: that slice of the whole-batch buffer (all buffers are image-major)
-  void* bptr(int b, int img0) const { return d_arena + buf_off[b] + (size_t)img0 * buf_P(b) * bufs[b].C * elem(b); }
-};
-
-namespace {
-
-size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
-// Typed pointers into an NmsScratch at `base`, from image img0 on (absent regions: null)
-struct NmsView {
-  float4 *boxes, *sboxes;
-  float *scores, *sareas, *rows;
-  int *cls, *counts, *seln;
-  unsigned long long *keys, *keys2, *sel, *sel2;
-  unsigned char* sup;
-  unsigned int* hist;
-  MlState* state;
-  int A, kstride;
-};
-NmsView nms_view(char* base, const NmsScratch& s, int img0) {
-  NmsView v{};
-  auto set = [&](auto*& p, const NmsRegion& r) {
-    p = r.stride ? reinterpret_cast<std::remove_reference_t<decltype(p)>>(base + r.at(img0)) : nullptr;
-  };
-  set(v.boxes, s.boxes); set(v.scores, s.scores); set(v.cls, s.cls);
-  set(v.keys, s.keys); set(v.keys2, s.keys2); set(v.counts, s.counts);
-  set(v.sboxes, s.sboxes); set(v.sareas, s.sareas); set(v.sup, s.sup);
-  set(v.rows, s.rows);
-  set(v.sel, s.sel); set(v.sel2, s.sel2); set(v.hist, s.hist); set(v.state, s.state); set(v.seln, s.seln);
-  v.A = s.A; v.kstride = s.kstride;
-  return v;
 }
 
 int ensure_workspace(ym_ctx* c, int B, int H, int W) {
@@ -510,8 +221,8 @@ int ensure_workspace(ym_ctx* c, int B, int H, int W) {
 }
 
 // Kernel arguments of a conv op for batch B at the current workspace shape.
-int conv_args(ym_ctx* c, const Launch& L, const Op& op, int B, const float* d_in, float in_eps, ConvArgs& a,
-              int& out_f32) {
+static int conv_args(ym_ctx* c, const Launch& L, const Op& op, int B, const float* d_in, float in_eps, ConvArgs& a,
+                     int& out_f32) {
   a = ConvArgs{};
   a.wsc = a.wsc2 = 1.0f;
   const int pst = ym_debug_get(YM_DBG_PAIRST);  // (value + 1; 0: the default family mask 21)
@@ -625,7 +336,7 @@ int conv_args(ym_ctx* c, const Launch& L, const Op& op, int B, const float* d_in
 
 // A fused pair (ConvArgs::w2) run as its two convs: A writes the intermediate buffer (the record's `mid`), B reads it.
 // The tuner picks this when the two tuned single launches beat every fused variant (op cfg ymc::split_encode).
-void split_args(ym_ctx* c, const Launch& L, const Op& op, const ConvArgs& a, ConvArgs& A, ConvArgs& Bc) {
+static void split_args(ym_ctx* c, const Launch& L, const Op& op, const ConvArgs& a, ConvArgs& A, ConvArgs& Bc) {
   const int mid = op.mid;
   A = a;
   A.w2 = nullptr; A.bias2 = nullptr; A.res = nullptr;
@@ -645,8 +356,8 @@ void split_args(ym_ctx* c, const Launch& L, const Op& op, const ConvArgs& a, Con
 
 // taken[2]: ym_launch_conv's `taken` of the fused launch, or of the two convs of a split cfg (a "heuristic" half:
 // -1); a fused cfg that fell back to the split pair is {0, -1}
-hipError_t launch_fused(ym_ctx* c, const Launch& L, const Op& op, const ConvArgs& a, int out_f32, int cfg,
-                        hipStream_t st, int* taken) {
+static hipError_t launch_fused(ym_ctx* c, const Launch& L, const Op& op, const ConvArgs& a, int out_f32, int cfg,
+                               hipStream_t st, int* taken) {
   const bool tagged = ymc::is_split(cfg);
   if (!tagged) {
     const hipError_t e = ym_launch_conv(c->dtype, out_f32, a, cfg, st, false, &taken[0]);
@@ -663,15 +374,6 @@ hipError_t launch_fused(ym_ctx* c, const Launch& L, const Op& op, const ConvArgs
   return ym_launch_conv(c->dtype, out_f32, Bc, ymc::split_cfg(ymc::split_second(cfg)), st, false, tb);
 }
 
-// Where an NMS stage reads per-candidate rows: the nm extras the NMS kernel copies behind each kept box, and the
-// class scores the multi-label candidate stage thresholds (both (B, A, *_ld) fp32; null: none)
-struct NmsSource {
-  const float* extras; int extras_ld, mask_off;
-  const float* cls; int cls_ld, cls_off;
-};
-
-// The NMS stage over B images of the candidates in `v` (decode_anchors' or the TTA merge's): single-label, with the
-// keys presorted at low conf, or multi-label.  The forward's OP_NMS and ym_tta_nms both end here.
 hipError_t launch_nms_stage(const NmsView& v, const NmsSource& src, const ym_infer_args* args, int B, int nc, int nm,
                             int H, int W, float* dets, int* out_counts, int* counts2, hipStream_t st) {
   NmsArgs a{};
@@ -689,8 +391,7 @@ hipError_t launch_nms_stage(const NmsView& v, const NmsSource& src, const ym_inf
     MlArgs m{};
     m.anchors = src.cls; m.no_tot = src.cls_ld; m.cls_off = src.cls_off;
     m.A = v.A; m.nc = nc; m.B = B;
-    m.conf = args->conf; m.has_classes = args->has_classes;
-    for (int i = 0; i < 4; ++i) m.classes[i] = args->classes[i];
+    set_filter(m, args);
     m.max_nms = args->max_nms; m.cap = kMlCap;
     m.counts = v.counts; m.hist = v.hist; m.state = v.state; m.sel = v.sel; m.sel2 = v.sel2; m.seln = v.seln;
     a.keys = m.sel; a.kstride = kMlCap; a.counts = m.seln;
@@ -709,8 +410,8 @@ hipError_t launch_nms_stage(const NmsView& v, const NmsSource& src, const ym_inf
 }
 
 // The OBB stage's arguments over B images from image img0 on: `rows` their (B, A, no_tot) head rows
-ObbArgs obb_args(ym_ctx* c, const float* rows, int img0, int B, const ym_infer_args* args, float* dets, int* out_counts,
-                 int* counts2) {
+static ObbArgs obb_args(ym_ctx* c, const float* rows, int img0, int B, const ym_infer_args* args, float* dets,
+                        int* out_counts, int* counts2) {
   const NmsView v = nms_view(c->d_arena, c->nms, img0);
   ObbArgs a{};
   a.anchors = rows; a.no_tot = c->bufs[c->anchor_buf].C; a.ang_off = c->no;
@@ -721,20 +422,17 @@ ObbArgs obb_args(ym_ctx* c, const float* rows, int img0, int B, const ym_infer_a
   a.keep = reinterpret_cast<unsigned char*>(c->d_arena + c->off_obb_keep) + i0;
   a.nsel = reinterpret_cast<int*>(c->d_arena + c->off_obb_nsel) + img0;
   a.dets = dets; a.out_counts = out_counts; a.counts2 = counts2;
-  a.A = v.A; a.kstride = v.kstride; a.nc = c->nc; a.reg_max = c->reg_max; a.B = B; a.nl = c->nl;
-  for (int l = 0; l < c->nl; ++l) {
-    a.lvl_W[l] = c->lvl_W[l]; a.lvl_off[l] = c->lvl_off[l]; a.lvl_stride[l] = (float)c->strides[l];
-  }
-  a.conf = args->conf; a.has_classes = args->has_classes;
-  for (int i = 0; i < 4; ++i) a.classes[i] = args->classes[i];
+  a.A = v.A; a.kstride = v.kstride; a.nc = c->nc; a.reg_max = c->reg_max; a.B = B;
+  set_levels(a, c);
+  set_filter(a, args);
   a.max_det = args->max_det; a.max_nms = args->max_nms; a.agnostic = args->agnostic;
   a.presort = args->conf < kPresortConf && v.kstride >= NMS_SORT;  // as launch_nms_stage
   a.max_wh = args->max_wh; a.img_h = (float)c->cH; a.img_w = (float)c->cW; a.iou = args->iou;
   return a;
 }
 
-int launch_op(ym_ctx* c, const Launch& L, const Op& op, int B, const float* d_in, const ym_infer_args* args,
-              float* d_dets, int* d_counts, hipStream_t st) {
+static int launch_op(ym_ctx* c, const Launch& L, const Op& op, int B, const float* d_in, const ym_infer_args* args,
+                     float* d_dets, int* d_counts, hipStream_t st) {
   const int dt = c->dtype;
   hipError_t e = hipSuccess;
   switch (op.kind) {
@@ -838,13 +536,9 @@ int launch_op(ym_ctx* c, const Launch& L, const Op& op, int B, const float* d_in
       a.anchors = reinterpret_cast<const float*>(c->bptr(c->anchor_buf, L.img0));
       a.no_tot = c->bufs[c->anchor_buf].C;
       a.boxes = v.boxes; a.scores = v.scores; a.cls = v.cls; a.keys = v.keys; a.counts = v.counts;
-      a.A = v.A; a.kstride = v.kstride; a.nc = c->nc; a.reg_max = c->reg_max; a.B = B; a.nl = c->nl;
-      for (int l = 0; l < c->nl; ++l) {
-        a.lvl_W[l] = c->lvl_W[l]; a.lvl_off[l] = c->lvl_off[l]; a.lvl_stride[l] = (float)c->strides[l];
-      }
-      a.conf = args->conf;
-      a.has_classes = args->has_classes;
-      for (int i = 0; i < 4; ++i) a.classes[i] = args->classes[i];
+      a.A = v.A; a.kstride = v.kstride; a.nc = c->nc; a.reg_max = c->reg_max; a.B = B;
+      set_levels(a, c);
+      set_filter(a, args);
       e = ym_launch_decode(a, st);
       break;
     }
@@ -854,9 +548,10 @@ int launch_op(ym_ctx* c, const Launch& L, const Op& op, int B, const float* d_in
       const float* rows = reinterpret_cast<const float*>(c->bptr(c->anchor_buf, L.img0));
       const int no_tot = c->bufs[c->anchor_buf].C;
       NmsSource src{rows, no_tot, c->no, rows, no_tot, 4 * c->reg_max};
+      // counts_after_dets: this lane's images' words behind the WHOLE batch's rows (d_dets is the lane's)
+      const int left = L.B - L.img0, cad = args->counts_after_dets;
       if (c->task == kTaskObb) {  // sort -> Fast-NMS keep flags -> rows, in place of the greedy NMS
-        const size_t left = (size_t)(L.B - L.img0) * args->max_det * 7;
-        int* c2 = args->counts_after_dets ? reinterpret_cast<int*>(d_dets + left) + L.img0 : nullptr;
+        int* c2 = cad ? counts_behind(d_dets, left, args->max_det, 7, L.img0) : nullptr;
         e = ym_launch_obb_nms(obb_args(c, rows, L.img0, B, args, d_dets, d_counts, c2), st);
         break;
       }
@@ -868,17 +563,12 @@ int launch_op(ym_ctx* c, const Launch& L, const Op& op, int B, const float* d_in
         k.keys = v.keys; k.counts = v.counts;
         k.out = reinterpret_cast<float*>(c->d_arena + c->off_kpts) + (size_t)L.img0 * c->A * c->nm;
         k.nk_pad = c->nm; k.A = v.A; k.kstride = v.kstride; k.K = c->kpt_K; k.ndim = c->kpt_ndim; k.B = B;
-        k.nl = c->nl;
-        for (int l = 0; l < c->nl; ++l) {
-          k.lvl_W[l] = c->lvl_W[l]; k.lvl_off[l] = c->lvl_off[l]; k.lvl_stride[l] = (float)c->strides[l];
-        }
+        set_levels(k, c);
         e = ym_launch_kpts(k, st);
         if (e != hipSuccess) break;
         src.extras = k.out; src.extras_ld = c->nm; src.mask_off = 0;
       }
-      // counts_after_dets: this lane's images' words behind the WHOLE batch's rows (d_dets is the lane's)
-      const size_t rows_left = (size_t)(L.B - L.img0) * args->max_det * (6 + c->nm);
-      int* counts2 = args->counts_after_dets ? reinterpret_cast<int*>(d_dets + rows_left) + L.img0 : nullptr;
+      int* counts2 = cad ? counts_behind(d_dets, left, args->max_det, 6 + c->nm, L.img0) : nullptr;
       e = launch_nms_stage(v, src, args, B, c->nc, c->nm, c->cH, c->cW, d_dets, d_counts, counts2, st);
       break;
     }
@@ -913,7 +603,14 @@ int launch_op(ym_ctx* c, const Launch& L, const Op& op, int B, const float* d_in
   return YM_OK;
 }
 
-// B images of H x W; `who`: the message's prefix ("" or "entry point: ")
+int check_ctx(const ym_ctx* c, const char* who, int task, const char* want) {
+  if (!c) return fail(YM_EINVAL, "null context");
+  if (!c->loaded) return fail(YM_ESTATE, "%s before ym_load_weights", who);
+  if (want && c->task != task)
+    return fail(YM_EINVAL, "%s: the loaded plan is a %s plan, not %s plan", who, ym_task_name(c->task), want);
+  return YM_OK;
+}
+
 int check_shape(int B, int H, int W, const char* who) {
   if (B < 1 || H < 32 || W < 32 || H % 32 || W % 32)
     return fail(YM_EINVAL, "%sinput shape (%d,3,%d,%d): H and W must be positive multiples of 32", who, B, H, W);
@@ -925,22 +622,20 @@ int check_nms_args(const ym_infer_args* args, int nc, int task) {
   if (args->max_det > 1024) return fail(YM_EINVAL, "max_det %d > 1024 is not supported", args->max_det);
   if (args->counts_after_dets != 0 && args->counts_after_dets != 1) return fail(YM_EINVAL, "counts_after_dets is 0 or 1");
   if (args->multi_label != 0 && args->multi_label != 1) return fail(YM_EINVAL, "multi_label is 0 or 1");
-  if (args->multi_label && task == kTaskObb)
-    return fail(YM_EINVAL, "multi_label: obb plans are not supported (validation mode is for detect plans)");
-  if (args->multi_label && nc > 1) {  // (nc == 1: the single-label path, as upstream's multi_label &= nc > 1)
-    if (task != 0)
-      return fail(YM_EINVAL, "multi_label: %s plans are not supported (validation mode is for detect plans)",
-                  ym_task_name(task));
+  // (nc == 1: the single-label path, as upstream's multi_label &= nc > 1; obb plans refuse it whatever nc is)
+  if (args->multi_label && (task == kTaskObb || (nc > 1 && task != 0)))
+    return fail(YM_EINVAL, "multi_label: %s plans are not supported (validation mode is for detect plans)",
+                ym_task_name(task));
+  if (args->multi_label && nc > 1) {
     if (nc > 128) return fail(YM_EINVAL, "multi_label: nc %d > 128 is not supported", nc);
     if (args->max_nms > kMlCap) return fail(YM_EINVAL, "multi_label: max_nms %d > %d is not supported", args->max_nms, kMlCap);
   }
   return YM_OK;
 }
 
-int check_call(ym_ctx* c, const float* d_in, int B, int H, int W, const ym_infer_args* args, float* d_dets,
-               int* d_counts) {
-  if (!c) return fail(YM_EINVAL, "null context");
-  if (!c->loaded) return fail(YM_ESTATE, "ym_infer before ym_load_weights");
+static int check_call(ym_ctx* c, const float* d_in, int B, int H, int W, const ym_infer_args* args, float* d_dets,
+                      int* d_counts) {
+  if (int rc = check_ctx(c, "ym_infer")) return rc;
   if (!d_in || !d_dets || !d_counts || !args) return fail(YM_EINVAL, "null pointer argument");
   if (int rc = check_shape(B, H, W, "")) return rc;
   if (int rc = check_nms_args(args, c->nc, c->task)) return rc;
@@ -948,12 +643,20 @@ int check_call(ym_ctx* c, const float* d_in, int B, int H, int W, const ym_infer
   return YM_OK;
 }
 
+int begin_launch(ym_ctx* c, int B, int H, int W, hipStream_t st, Launch& L) {
+  HIPCK(hipSetDevice(c->device));
+  if (int rc = ensure_workspace(c, B, H, W)) return rc;
+  L = Launch{};
+  L.B = B;
+  return c->order_after_last(st);
+}
+
 // `reps` calls of launch(stream) captured on the private stream as one graph, replayed on `st`: once warm, then
 // `timed` times between two events (device-bound even for tiny kernels).  Returns a HIP failure as YM_EHIP; else
 // launch_rc is the first non-zero result of `launch` (nothing was replayed) or 0 with the timed replays' total in ms.
 // Graph, exec and events are destroyed on every path.
 template <typename F>
-int time_captured(ym_ctx* c, hipStream_t st, int reps, int timed, F&& launch, int& launch_rc, float& ms) {
+static int time_captured(ym_ctx* c, hipStream_t st, int reps, int timed, F&& launch, int& launch_rc, float& ms) {
   hipGraph_t g = nullptr;
   hipGraphExec_t ge = nullptr;
   hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -981,8 +684,6 @@ int time_captured(ym_ctx* c, hipStream_t st, int reps, int timed, F&& launch, in
   if (launch_rc != 0) return YM_OK;  // (the caller skips or reports it)
   return e == hipSuccess ? YM_OK : fail(YM_EHIP, "timed graph replay: %s", hipGetErrorString(e));
 }
-
-}  // namespace
 
 extern "C" {
 
@@ -1304,7 +1005,7 @@ static void embed_args(const ym_ctx* c, int B, int H, int W, bool with_ptrs, Emb
   a.B = B;
   a.out = c->embed_out;
   a.ld = (long)c->embed_ld;
-  a.part = c->d_embed;
+  a.part = static_cast<float*>(c->embed.p);
   int col = 0;
   for (int i = 0; i < a.n; ++i) {
     const ym_embed_view& v = c->embed_views[i];
@@ -1325,10 +1026,8 @@ static int launch_embed(ym_ctx* c, int B, hipStream_t st) {
   EmbedArgs a;
   embed_args(c, B, c->cH, c->cW, true, a);
   const long need = ym_embed_part_floats(a);
-  if (need < 0 || (size_t)need > c->embed_floats) return fail(YM_EINVAL, "ym_embed: bad view table");
-  const hipError_t e = ym_launch_embed(a, st);
-  if (e != hipSuccess) return fail(YM_EHIP, "embed pooling launch: %s", hipGetErrorString(e));
-  return YM_OK;
+  if (need < 0 || (size_t)need * sizeof(float) > c->embed.bytes) return fail(YM_EINVAL, "ym_embed: bad view table");
+  return launched(ym_launch_embed(a, st), "embed pooling launch");
 }
 
 // One step of a forward's op loop: op i alone, or (`pair_ok`) ops i and i + 1 as one launch where the fused stem or the
@@ -1397,15 +1096,6 @@ static int launch_forward(ym_ctx* c, const Launch& call, const float* d_in, cons
     }
   }
   return embed && call.pool ? launch_embed(c, B, st) : YM_OK;  // (ym_embed runs one lane: everything above is on `st`)
-}
-
-// Behind check_call, for every entry point that launches ops: device, workspace, stream order; L: one whole-batch launch
-static int begin_launch(ym_ctx* c, int B, int H, int W, hipStream_t st, Launch& L) {
-  HIPCK(hipSetDevice(c->device));
-  if (int rc = ensure_workspace(c, B, H, W)) return rc;
-  L = Launch{};
-  L.B = B;
-  return c->order_after_last(st);
 }
 
 // ym_infer, (skip_nms) ym_tta_forward and (stop >= 0) ym_embed
@@ -1500,10 +1190,7 @@ int ym_infer(ym_ctx* c, const float* d_in, int B, int H, int W, const ym_infer_a
 // ---------------------------------------------------------------------------------- oriented boxes
 int ym_obb_nms(ym_ctx* c, const float* d_rows, int B, int H, int W, const ym_infer_args* args, float* d_dets,
                int* d_counts, void* stream) {
-  if (!c) return fail(YM_EINVAL, "null context");
-  if (!c->loaded) return fail(YM_ESTATE, "ym_obb_nms before ym_load_weights");
-  if (c->task != kTaskObb)
-    return fail(YM_EINVAL, "ym_obb_nms: the loaded plan is a %s plan, not an obb plan", ym_task_name(c->task));
+  if (int rc = check_ctx(c, "ym_obb_nms", kTaskObb, "an obb")) return rc;
   if (!d_rows || !args || !d_dets || !d_counts) return fail(YM_EINVAL, "null pointer argument");
   if (int rc = check_shape(B, H, W, "ym_obb_nms: ")) return rc;
   if (int rc = check_nms_args(args, c->nc, c->task)) return rc;
@@ -1512,43 +1199,32 @@ int ym_obb_nms(ym_ctx* c, const float* d_rows, int B, int H, int W, const ym_inf
   if (int rc = begin_launch(c, B, H, W, st, L)) return rc;
   // the candidate counts start at 0 (the forward's input op clears them; this entry point is never captured)
   HIPCK(hipMemsetAsync(nms_view(c->d_arena, c->nms, 0).counts, 0, (size_t)B * 4, st));
-  int* c2 = args->counts_after_dets ? reinterpret_cast<int*>(d_dets + (size_t)B * args->max_det * 7) : nullptr;
+  int* c2 = args->counts_after_dets ? counts_behind(d_dets, B, args->max_det, 7, 0) : nullptr;
   const ObbArgs a = obb_args(c, d_rows, 0, B, args, d_dets, d_counts, c2);
-  hipError_t e = ym_launch_obb_decode(a, st);
-  if (e == hipSuccess) e = ym_launch_obb_nms(a, st);
-  if (e != hipSuccess) return fail(YM_EHIP, "ym_obb_nms launch: %s", hipGetErrorString(e));
+  if (int rc = launched(ym_launch_obb_decode(a, st), "ym_obb_nms launch")) return rc;
+  if (int rc = launched(ym_launch_obb_nms(a, st), "ym_obb_nms launch")) return rc;
   return c->mark_last(st);
 }
 
 // ---------------------------------------------------------------------------------- classification
 int ym_classify(ym_ctx* c, const float* d_in, int B, int H, int W, const ym_infer_args* args, float* d_probs, int ld,
                 float* d_logits, int* d_topk, float* d_topk_conf, void* stream) {
-  if (!c) return fail(YM_EINVAL, "null context");
-  if (!c->loaded) return fail(YM_ESTATE, "ym_classify before ym_load_weights");
-  if (c->task != kTaskClassify)
-    return fail(YM_EINVAL, "ym_classify: the loaded plan is a %s plan, not a classify plan", ym_task_name(c->task));
+  if (int rc = check_ctx(c, "ym_classify", kTaskClassify, "a classify")) return rc;
   if (!d_in || !args || !d_probs || !d_topk || !d_topk_conf) return fail(YM_EINVAL, "null pointer argument");
   if (ld < c->nc) return fail(YM_EINVAL, "ym_classify: row stride %d below the %d classes", ld, c->nc);
-  // what reaches the forward: the /255 rule's inputs and the launch mode; one lane; no detection output is written
-  ym_infer_args fa{};
-  fa.conf = 0.25f; fa.max_wh = 7680.f; fa.iou = 0.7; fa.max_det = 300; fa.max_nms = 30000;
-  fa.in_eps = args->in_eps; fa.use_graph = args->use_graph; fa.lanes = 1; fa.d_batch_max = args->d_batch_max;
-  ClsOut out;
-  out.probs = d_probs; out.ld = ld; out.logits = d_logits; out.topk = d_topk; out.topk_conf = d_topk_conf;
-  float* nodets = reinterpret_cast<float*>(c->d_misc + kMiscNoDets);
-  return infer_impl(c, d_in, B, H, W, &fa, nodets, reinterpret_cast<int*>(nodets), stream, false, -1, &out);
+  const ym_infer_args fa = forward_only_args(args);  // (no detection output is written)
+  const ClsOut out{d_probs, ld, d_logits, d_topk, d_topk_conf};
+  return infer_impl(c, d_in, B, H, W, &fa, no_dets(c), reinterpret_cast<int*>(no_dets(c)), stream, false, -1, &out);
 }
 
 // ---------------------------------------------------------------------------------- test-time augmentation
 int ym_tta_shape(int H, int W, int pass, int* Hs, int* Ws, int* hc, int* wc) {
   if (int rc = check_shape(1, H, W, "ym_tta_shape: ")) return rc;
   if (pass < 0 || pass >= kTtaPasses) return fail(YM_EINVAL, "ym_tta_shape: pass is 0..%d", kTtaPasses - 1);
-  int v[4];
+  int v[4], *const out[4] = {Hs, Ws, hc, wc};
   ym_tta_pass_shape(H, W, pass, v[0], v[1], v[2], v[3]);
-  if (Hs) *Hs = v[0];
-  if (Ws) *Ws = v[1];
-  if (hc) *hc = v[2];
-  if (wc) *wc = v[3];
+  for (int i = 0; i < 4; ++i)
+    if (out[i]) *out[i] = v[i];
   return YM_OK;
 }
 
@@ -1562,9 +1238,7 @@ int ym_tta_scale(ym_ctx* c, const float* d_in, int B, int H, int W, int pass, co
   a.in = d_in; a.B = B; a.H = H; a.W = W; a.out = d_out;
   ym_tta_pass_shape(H, W, pass, a.Hs, a.Ws, a.hc, a.wc);
   a.flip = kTtaFlip[pass]; a.batch_max = d_max; a.eps = in_eps;
-  const hipError_t e = ym_launch_tta_scale(a, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(YM_EHIP, "tta scale launch: %s", hipGetErrorString(e));
-  return YM_OK;
+  return launched(ym_launch_tta_scale(a, static_cast<hipStream_t>(stream)), "tta scale launch");
 }
 
 int ym_tta_forward(ym_ctx* c, const float* d_in, int B, int H, int W, const ym_infer_args* args, void* stream) {
@@ -1575,15 +1249,13 @@ int ym_tta_forward(ym_ctx* c, const float* d_in, int B, int H, int W, const ym_i
   fa.multi_label = 0;
   fa.counts_after_dets = 0;
   // (the NMS stage is the only reader of the outputs: any device words do, they are never written)
-  float* nodets = reinterpret_cast<float*>(c->d_misc + kMiscNoDets);
-  return infer_impl(c, d_in, B, H, W, &fa, nodets, reinterpret_cast<int*>(nodets), stream, true, -1);
+  return infer_impl(c, d_in, B, H, W, &fa, no_dets(c), reinterpret_cast<int*>(no_dets(c)), stream, true, -1);
 }
 
 // ---------------------------------------------------------------------------------- feature embeddings
 int ym_embed(ym_ctx* c, const float* d_in, int B, int H, int W, const ym_infer_args* args, const ym_embed_view* views,
              int n_views, float* d_out, long long out_stride, void* stream) {
-  if (!c) return fail(YM_EINVAL, "null context");
-  if (!c->loaded) return fail(YM_ESTATE, "ym_embed before ym_load_weights");
+  if (int rc = check_ctx(c, "ym_embed")) return rc;
   if (!d_in || !args || !views || !d_out) return fail(YM_EINVAL, "null pointer argument");
   if (c->task == kTaskObb) return fail(YM_EINVAL, "ym_embed: obb plans are not supported");
   if (ym_dt_q8(c->dtype))
@@ -1625,27 +1297,11 @@ int ym_embed(ym_ctx* c, const float* d_in, int B, int H, int W, const ym_infer_a
   embed_args(c, B, H, W, false, ea);
   const long need = ym_embed_part_floats(ea);
   if (need < 0) return fail(YM_EINVAL, "ym_embed: bad view table");
-  if ((size_t)need > c->embed_floats) {  // the chunk partials grow: no captured pooling stage may keep the old ones
-    c->clear_graphs();
-    if (c->d_embed) {
-      HIPCK(hipDeviceSynchronize());
-      HIPCK(hipFree(c->d_embed));
-      c->d_embed = nullptr;
-      c->embed_floats = 0;
-    }
-    const hipError_t e = hipMalloc(&c->d_embed, (size_t)need * sizeof(float));
-    if (e != hipSuccess) {
-      c->d_embed = nullptr;
-      return fail(YM_ENOMEM, "embed partials hipMalloc(%ld floats): %s", need, hipGetErrorString(e));
-    }
-    c->embed_floats = (size_t)need;
-  }
-  // what reaches the truncated forward: the /255 rule's inputs and the launch mode; one lane; no output is written
-  ym_infer_args fa{};
-  fa.conf = 0.25f; fa.max_wh = 7680.f; fa.iou = 0.7; fa.max_det = 300; fa.max_nms = 30000;
-  fa.in_eps = args->in_eps; fa.use_graph = args->use_graph; fa.lanes = 1; fa.d_batch_max = args->d_batch_max;
-  float* nodets = reinterpret_cast<float*>(c->d_misc + kMiscNoDets);
-  return infer_impl(c, d_in, B, H, W, &fa, nodets, reinterpret_cast<int*>(nodets), stream, false, stop);
+  const size_t part_bytes = (size_t)need * sizeof(float);
+  if (part_bytes > c->embed.bytes) c->clear_graphs();  // the chunk partials grow: no captured pooling stage may keep the old ones
+  if (int rc = c->embed.grow(part_bytes, "embed partials hipMalloc(%zu floats)", (size_t)need)) return rc;
+  const ym_infer_args fa = forward_only_args(args);  // (the truncated forward; no output is written)
+  return infer_impl(c, d_in, B, H, W, &fa, no_dets(c), reinterpret_cast<int*>(no_dets(c)), stream, false, stop);
 }
 
 // the merged scratch of ctxs[0] for B images of an H x W frame: Am merged anchors, multi-label regions on demand
@@ -1726,17 +1382,15 @@ int ym_tta_nms(ym_ctx* const* ctxs, int B, int H, int W, const ym_infer_args* ar
   m.boxes = v.boxes; m.scores = v.scores; m.cls = v.cls; m.keys = v.keys; m.counts = v.counts;
   m.rows = ml ? v.rows : nullptr;
   m.Am = Am; m.kstride = v.kstride; m.B = B;
-  m.conf = args->conf; m.has_classes = args->has_classes;
-  for (int i = 0; i < 4; ++i) m.classes[i] = args->classes[i];
+  set_filter(m, args);
   m.img_w = (float)W;
   if (!ml) HIPCK(hipMemsetAsync(m.counts, 0, (size_t)B * 4, st));
-  hipError_t e = ym_launch_tta_merge(m, st);
-  if (e != hipSuccess) return fail(YM_EHIP, "tta merge launch: %s", hipGetErrorString(e));
+  if (int rc = launched(ym_launch_tta_merge(m, st), "tta merge launch")) return rc;
   // no extras (detect plans: nm = 0); multi-label thresholds the merged class rows
   const NmsSource src{nullptr, 0, 0, m.rows, c->nc, 0};
-  int* counts2 = args->counts_after_dets ? reinterpret_cast<int*>(d_dets + (size_t)B * args->max_det * 6) : nullptr;
-  e = launch_nms_stage(v, src, args, B, c->nc, 0, H, W, d_dets, d_counts, counts2, st);
-  if (e != hipSuccess) return fail(YM_EHIP, "tta NMS launch: %s", hipGetErrorString(e));
+  int* counts2 = args->counts_after_dets ? counts_behind(d_dets, B, args->max_det, 6, 0) : nullptr;
+  const hipError_t e = launch_nms_stage(v, src, args, B, c->nc, 0, H, W, d_dets, d_counts, counts2, st);
+  if (int rc = launched(e, "tta NMS launch")) return rc;
   // the merge read every pass's arena: a later forward of any of them on another stream waits for this call
   for (int p = 0; p < kTtaPasses; ++p)
     if (int rc = ctxs[p]->mark_last(st)) return rc;
@@ -1746,19 +1400,14 @@ int ym_tta_nms(ym_ctx* const* ctxs, int B, int H, int W, const ym_infer_args* ar
 int ym_tta_counts(ym_ctx* c, int* dst, int B) {
   if (!c || !dst || B < 1) return fail(YM_EINVAL, "bad ym_tta_counts arguments");
   if (!c->tta.d || B > c->tta.B) return fail(YM_ESTATE, "no merged scratch for %d images yet (run ym_tta_nms first)", B);
-  HIPCK(hipSetDevice(c->device));
-  HIPCK(hipDeviceSynchronize());
-  HIPCK(hipMemcpy(dst, c->tta.d + c->tta.ws.counts.off, (size_t)B * 4, hipMemcpyDefault));
-  return YM_OK;
+  return read_back(c->device, dst, c->tta.d + c->tta.ws.counts.off, (size_t)B * 4);
 }
 
 int ym_input_max(ym_ctx* c, const float* d_in, size_t n, float* d_max, void* stream) {
   if (!c || !d_in || !d_max || n == 0) return fail(YM_EINVAL, "bad ym_input_max arguments");
   HIPCK(hipSetDevice(c->device));
-  const hipError_t e = ym_launch_input_max(d_in, (long)n, reinterpret_cast<float*>(c->d_misc + kMiscStats), d_max,
-                                           static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(YM_EHIP, "input max: %s", hipGetErrorString(e));
-  return YM_OK;
+  return launched(ym_launch_input_max(d_in, (long)n, reinterpret_cast<float*>(c->d_misc + kMiscStats), d_max,
+                                      static_cast<hipStream_t>(stream)), "input max");
 }
 
 int ym_calibrate(ym_ctx* c, const float* d_in, int B, int H, int W, const ym_infer_args* args, float* d_dets,
@@ -1963,15 +1612,11 @@ int ym_read_buffer(ym_ctx* c, int b, void* dst, size_t bytes) {
   if (!c->d_arena) return fail(YM_ESTATE, "no workspace yet (run ym_infer first)");
   const size_t cap = (size_t)c->cB * c->buf_P(b) * c->bufs[b].C * c->elem(b);
   if (bytes > cap) return fail(YM_EINVAL, "read of %zu bytes exceeds buffer size %zu", bytes, cap);
-  HIPCK(hipSetDevice(c->device));
-  HIPCK(hipDeviceSynchronize());
-  HIPCK(hipMemcpy(dst, c->bptr(b, 0), bytes, hipMemcpyDefault));
-  return YM_OK;
+  return read_back(c->device, dst, c->bptr(b, 0), bytes);
 }
 
 int ym_kpt_shape(ym_ctx* c, int* K, int* ndim) {
-  if (!c) return fail(YM_EINVAL, "null context");
-  if (!c->loaded) return fail(YM_ESTATE, "ym_kpt_shape before ym_load_weights");
+  if (int rc = check_ctx(c, "ym_kpt_shape")) return rc;
   if (K) *K = c->kpt_K;
   if (ndim) *ndim = c->kpt_ndim;
   return YM_OK;
@@ -2003,617 +1648,7 @@ int ym_read_scratch(ym_ctx* c, int which, void* dst, size_t bytes) {
     default: return fail(YM_EINVAL, "unknown scratch region %d", which);
   }
   if (bytes > cap) return fail(YM_EINVAL, "read of %zu bytes exceeds region size %zu", bytes, cap);
-  HIPCK(hipSetDevice(c->device));
-  HIPCK(hipDeviceSynchronize());
-  HIPCK(hipMemcpy(dst, c->d_arena + off, bytes, hipMemcpyDefault));
-  return YM_OK;
-}
-
-int ym_letterbox(ym_ctx* c, const void* d_src, int h, int w, int row_bytes, int bgr, int uh, int uw, int top,
-                 int left, float* d_dst, int Hn, int Wn, void* stream) {
-  if (!c) return fail(YM_EINVAL, "null context");
-  if (!d_src || !d_dst || h < 1 || w < 1 || uh < 1 || uw < 1 || top < 0 || left < 0 || top + uh > Hn ||
-      left + uw > Wn || row_bytes < 3 * w)
-    return fail(YM_EINVAL, "bad ym_letterbox geometry (%dx%d -> %dx%d at (%d, %d) in %dx%d)", h, w, uh, uw, top, left,
-                Hn, Wn);
-  HIPCK(hipSetDevice(c->device));
-  LetterboxArgs a{};
-  a.src = static_cast<const unsigned char*>(d_src);
-  a.h = h; a.w = w; a.row_bytes = row_bytes; a.bgr = bgr ? 1 : 0;
-  a.uh = uh; a.uw = uw; a.top = top; a.left = left;
-  a.scale_x = 1.0 / ((double)uw / w);  // cv2: scale_x = 1. / inv_scale_x, inv_scale_x = (double)dsize.width / ssize.width
-  a.scale_y = 1.0 / ((double)uh / h);
-  a.dst = d_dst; a.Hn = Hn; a.Wn = Wn;
-  hipError_t e = ym_launch_letterbox(a, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(YM_EHIP, "letterbox launch: %s", hipGetErrorString(e));
-  return YM_OK;
-}
-
-int ym_classify_pre(ym_ctx* c, const void* d_images, const ym_cls_pre_desc* d_desc, const ym_cls_pre_desc* h_desc,
-                    int B, int imgsz, float* d_dst, void* stream) {
-  if (!c) return fail(YM_EINVAL, "null context");
-  if (!d_images || !d_desc || !h_desc || !d_dst) return fail(YM_EINVAL, "ym_classify_pre: null pointer");
-  if (reinterpret_cast<uintptr_t>(d_images) & 15) return fail(YM_EINVAL, "ym_classify_pre: d_images not 16-byte aligned");
-  if (B < 1 || B > 65535) return fail(YM_EINVAL, "ym_classify_pre: B %d outside 1..65535", B);
-  if (imgsz < 32 || imgsz % 32) return fail(YM_EINVAL, "ym_classify_pre: imgsz %d is no positive multiple of 32", imgsz);
-  ClsPreArgs a{};
-  a.KH = a.KV = 3;
-  for (int b = 0; b < B; ++b) {
-    const ym_cls_pre_desc& d = h_desc[b];
-    if (d.off < 0 || d.off % 16 || d.h < 1 || d.w < 1 || d.rh < 1 || d.rw < 1 || (d.bgr != 0 && d.bgr != 1))
-      return fail(YM_EINVAL, "ym_classify_pre: image %d: bad descriptor (off %lld, %dx%d -> %dx%d, bgr %d)", b, d.off,
-                  d.h, d.w, d.rh, d.rw, d.bgr);
-    if (d.row_bytes < 3 * (long long)d.w)
-      return fail(YM_EINVAL, "ym_classify_pre: image %d: row_bytes %d below 3 * w = %lld", b, d.row_bytes,
-                  3 * (long long)d.w);
-    if (d.top < 0 || d.left < 0 || (long long)d.top + imgsz > d.rh || (long long)d.left + imgsz > d.rw)
-      return fail(YM_EINVAL, "ym_classify_pre: image %d: crop window %d at (%d, %d) outside %dx%d", b, imgsz, d.top,
-                  d.left, d.rh, d.rw);
-    if (d.h > (long long)kClsPreMaxScale * d.rh || d.w > (long long)kClsPreMaxScale * d.rw)
-      return fail(YM_EINVAL, "ym_classify_pre: image %d: %dx%d -> %dx%d reduces by more than %d", b, d.h, d.w, d.rh,
-                  d.rw, kClsPreMaxScale);
-    a.KH = std::max(a.KH, ym_cls_pre_taps(d.w, d.rw));
-    a.KV = std::max(a.KV, ym_cls_pre_taps(d.h, d.rh));
-  }
-  HIPCK(hipSetDevice(c->device));
-  a.images = static_cast<const unsigned char*>(d_images);
-  a.desc = d_desc; a.dst = d_dst; a.B = B; a.imgsz = imgsz;
-  hipError_t e = ym_launch_cls_pre(a, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(YM_EHIP, "classify_pre launch: %s", hipGetErrorString(e));
-  return YM_OK;
-}
-
-static int launch_masks(ym_ctx* c, MaskArgs& a, int B, int H, int W, void* stream) {
-  if (!c) return fail(YM_EINVAL, "null context");
-  if (c->task != 1 || c->proto_buf < 0) return fail(YM_ESTATE, "ym_masks needs a segment plan");
-  if (!c->d_arena || B > c->cB || H != c->cH || W != c->cW)
-    return fail(YM_ESTATE, "ym_masks must follow ym_infer of the same (B, H, W) (workspace %dx%dx%d)", c->cB, c->cH,
-                c->cW);
-  HIPCK(hipSetDevice(c->device));
-  a.proto = reinterpret_cast<const float*>(c->bptr(c->proto_buf, 0));
-  a.MH = c->buf_H(c->proto_buf); a.MW = c->buf_Wd(c->proto_buf); a.nm = c->nm;
-  a.no = 6 + c->nm; a.B = B; a.H = H; a.W = W;
-  if (a.total == 0) return YM_OK;
-  if (!ym_masks_fused(a)) {  // the two-kernel path: (total, MH, MW) prototype-resolution scratch
-    const size_t need = (size_t)a.total * a.MH * a.MW * sizeof(float);
-    if (need > c->lowres_bytes) {
-      if (c->d_lowres) HIPCK(hipFree(c->d_lowres));
-      c->d_lowres = nullptr;
-      hipError_t e = hipMalloc(&c->d_lowres, need);
-      if (e != hipSuccess) return fail(YM_ENOMEM, "mask scratch hipMalloc(%zu): %s", need, hipGetErrorString(e));
-      c->lowres_bytes = need;
-    }
-    a.lowres = c->d_lowres;
-  }
-  const hipError_t e = ym_launch_masks(a, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(YM_EHIP, "mask kernels: %s", hipGetErrorString(e));
-  return YM_OK;
-}
-
-int ym_masks(ym_ctx* c, const float* d_dets, int B, int max_det, const int* d_offsets, int total, int H, int W,
-             unsigned char* d_masks, int* d_nonempty, void* stream) {
-  if (total < 0 || max_det < 1 || (total > 0 && (!d_dets || !d_offsets || !d_masks || !d_nonempty)))
-    return fail(YM_EINVAL, "bad ym_masks arguments");
-  MaskArgs a{};
-  a.dets = d_dets; a.max_det = max_det; a.offsets = d_offsets; a.total = total;
-  a.masks = d_masks; a.nonempty = d_nonempty;
-  return launch_masks(c, a, B, H, W, stream);
-}
-
-int ym_masks_slots(ym_ctx* c, const float* d_dets, int B, int max_det, const int* d_counts, int cap, int H, int W,
-                   unsigned char* d_masks, int* d_flags, void* stream) {
-  if (B < 1 || cap < 1 || max_det < 1 || cap > max_det || !d_dets || !d_counts || !d_masks || !d_flags)
-    return fail(YM_EINVAL, "bad ym_masks_slots arguments");
-  MaskArgs a{};
-  a.dets = d_dets; a.max_det = max_det; a.counts = d_counts; a.cap = cap; a.total = B * cap;
-  a.masks = d_masks; a.nonempty = d_flags;
-  return launch_masks(c, a, B, H, W, stream);
-}
-
-int ym_masks_native(ym_ctx* c, const float* d_dets, int det_stride, int B, int max_det, const int* d_offsets, int total,
-                    int H, int W, const int* shapes, const int* d_shapes, const long long* d_mask_offsets,
-                    unsigned char* d_masks, int* d_nonempty, void* stream) {
-  if (!c) return fail(YM_EINVAL, "null context");
-  if (B < 1 || total < 0 || max_det < 1 || !shapes || !d_dets || !d_offsets || !d_shapes || !d_mask_offsets ||
-      (total > 0 && (!d_masks || !d_nonempty)))
-    return fail(YM_EINVAL, "bad ym_masks_native arguments");
-  long long max_bytes = 0;
-  for (int b = 0; b < B; ++b) {
-    const long long h0 = shapes[2 * b], w0 = shapes[2 * b + 1];
-    if (h0 < 1 || w0 < 1 || h0 * w0 > (1ll << 30))
-      return fail(YM_EINVAL, "ym_masks_native: native size %lld x %lld of image %d (1 x 1 .. 2^30 pixels)", h0, w0, b);
-    max_bytes = std::max(max_bytes, h0 * w0);
-  }
-  if (c->task != 1 || c->proto_buf < 0) return fail(YM_ESTATE, "ym_masks_native needs a segment plan");
-  if (det_stride < 6 + c->nm) return fail(YM_EINVAL, "ym_masks_native: row stride %d below %d", det_stride, 6 + c->nm);
-  if (!c->d_arena || B > c->cB || H != c->cH || W != c->cW)
-    return fail(YM_ESTATE, "ym_masks_native must follow ym_infer of the same (B, H, W) (workspace %dx%dx%d)", c->cB,
-                c->cH, c->cW);
-  if (total == 0) return YM_OK;
-  HIPCK(hipSetDevice(c->device));
-  MaskNativeArgs a{};
-  a.proto = reinterpret_cast<const float*>(c->bptr(c->proto_buf, 0));
-  a.MH = c->buf_H(c->proto_buf); a.MW = c->buf_Wd(c->proto_buf); a.nm = c->nm;
-  a.dets = d_dets; a.max_det = max_det; a.stride = det_stride;
-  a.offsets = d_offsets; a.B = B; a.total = total;
-  a.shapes = d_shapes; a.byte_off = d_mask_offsets; a.masks = d_masks; a.nonempty = d_nonempty;
-  const hipError_t e = ym_launch_masks_native(a, max_bytes, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(YM_EHIP, "native mask kernel: %s", hipGetErrorString(e));
-  return YM_OK;
-}
-
-// ---------------------------------------------------------------------------------------------- RCCL (xGMI)
-// The init-time weight broadcast of the batch-sharded multi-GPU path: RCCL is resolved at run time
-// (dlopen of the process's already-loaded librccl — torch's, when the host is Python — else the ROCm one), so
-// libyolomi.so itself has no link-time dependency on it.  Only the four entry points below are used.
-namespace {
-struct Rccl {
-  typedef int (*GetUniqueId)(void*);
-  typedef int (*CommInitRank)(void**, int, ym_rccl_id, int);
-  typedef int (*CommDestroy)(void*);
-  typedef int (*CommUserRank)(void*, int*);
-  typedef int (*CommCount)(void*, int*);
-  typedef int (*Broadcast)(const void*, void*, size_t, int, int, void*, hipStream_t);
-  typedef int (*AllReduce)(const void*, void*, size_t, int, int, void*, hipStream_t);
-  typedef const char* (*ErrStr)(int);
-  GetUniqueId get_id = nullptr;
-  CommInitRank init = nullptr;
-  CommDestroy destroy = nullptr;
-  CommUserRank user_rank = nullptr;
-  CommCount count = nullptr;
-  Broadcast bcast = nullptr;
-  AllReduce allreduce = nullptr;
-  ErrStr err = nullptr;
-  bool ok = false;
-};
-
-const Rccl* rccl() {
-  static Rccl r = [] {
-    Rccl x;
-    void* h = nullptr;
-    for (const char* n : {"librccl.so.1", "librccl.so"})
-      if (!h) h = dlopen(n, RTLD_NOW | RTLD_NOLOAD);
-    for (const char* n : {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"})
-      if (!h) h = dlopen(n, RTLD_NOW | RTLD_LOCAL);
-    if (!h) return x;
-    x.get_id = (Rccl::GetUniqueId)dlsym(h, "ncclGetUniqueId");
-    x.init = (Rccl::CommInitRank)dlsym(h, "ncclCommInitRank");
-    x.destroy = (Rccl::CommDestroy)dlsym(h, "ncclCommDestroy");
-    x.user_rank = (Rccl::CommUserRank)dlsym(h, "ncclCommUserRank");
-    x.count = (Rccl::CommCount)dlsym(h, "ncclCommCount");
-    x.bcast = (Rccl::Broadcast)dlsym(h, "ncclBroadcast");
-    x.allreduce = (Rccl::AllReduce)dlsym(h, "ncclAllReduce");
-    x.err = (Rccl::ErrStr)dlsym(h, "ncclGetErrorString");
-    x.ok = x.get_id && x.init && x.destroy && x.user_rank && x.count && x.bcast && x.allreduce && x.err;
-    return x;
-  }();
-  return r.ok ? &r : nullptr;
-}
-
-#define RCCLCK(x)                                                                                       \
-  do {                                                                                                  \
-    const int r_ = (x);                                                                                 \
-    if (r_ != 0) return fail(YM_EHIP, "%s: RCCL error %d (%s)", #x, r_, R->err ? R->err(r_) : "?");     \
-  } while (0)
-constexpr int kNcclUint8 = 1, kNcclUint64 = 5;  // ncclDataType_t
-constexpr int kNcclSum = 0;                       // ncclRedOp_t
-constexpr size_t kBcastChunk = 16u << 20;         // blob bytes per broadcast (one staging buffer per rank)
-}  // namespace
-
-int ym_rccl_get_unique_id(ym_rccl_id* id) {
-  if (!id) return fail(YM_EINVAL, "null id");
-  const Rccl* R = rccl();
-  if (!R) return fail(YM_ESTATE, "RCCL (librccl.so) is not available in this process");
-  RCCLCK(R->get_id(id));
-  return YM_OK;
-}
-
-int ym_rccl_comm_init(int device, int nranks, const ym_rccl_id* id, int rank, void** comm) {
-  if (!id || !comm || nranks < 1 || rank < 0 || rank >= nranks) return fail(YM_EINVAL, "bad ym_rccl_comm_init arguments");
-  const Rccl* R = rccl();
-  if (!R) return fail(YM_ESTATE, "RCCL (librccl.so) is not available in this process");
-  HIPCK(hipSetDevice(device));
-  *comm = nullptr;
-  RCCLCK(R->init(comm, nranks, *id, rank));
-  return YM_OK;
-}
-
-int ym_rccl_comm_destroy(void* comm) {
-  if (!comm) return YM_OK;
-  const Rccl* R = rccl();
-  if (!R) return fail(YM_ESTATE, "RCCL (librccl.so) is not available in this process");
-  RCCLCK(R->destroy(comm));
-  return YM_OK;
-}
-
-// ---- the init-time weight broadcast: one rank's side, shared by the two transports
-// (ym_broadcast_weights: RCCL, one rank per process; ym_broadcast_weights_local: every rank's context in this process,
-// the fake backend of SURVEY §4.4) — staging buffer, the root's upload, a receiver's copy-out and load, and the
-// verdict every rank agrees on.  The transports only move the chunk between staging buffers and sum control words.
-struct BcastRank {
-  ym_ctx* c = nullptr;
-  int rank = -1;
-  bool hip_ok = true, copy_ok = true;
-  char* d = nullptr;  // kBcastChunk staging bytes on the context's device
-  std::vector<char> h;  // a receiver's copy of the blob
-  int rc = YM_OK;
-  BcastRank() = default;
-  BcastRank(const BcastRank&) = delete;
-  BcastRank& operator=(const BcastRank&) = delete;
-  ~BcastRank() {
-    if (d) (void)hipFree(d);
-  }
-  // step (1): this rank's contribution to {the root's blob size (0: the root has no weights), staging failures}
-  void open(int root, unsigned long long h1[2]) {
-    hip_ok = hipSetDevice(c->device) == hipSuccess;
-    const bool alloc_ok = hip_ok && hipMalloc(&d, kBcastChunk) == hipSuccess;
-    if (!alloc_ok) d = nullptr;
-    h1[0] += (rank == root && c->loaded) ? (unsigned long long)c->blob_host.size() : 0ull;
-    h1[1] += alloc_ok ? 0ull : 1ull;
-    copy_ok = hip_ok;
-  }
-  // step (2), per chunk: the root uploads it into its staging buffer before the transport moves it ...
-  void put(int root, unsigned long long off, size_t len, hipStream_t st) {
-    if (rank == root)
-      copy_ok = copy_ok && hipMemcpyAsync(d, c->blob_host.data() + off, len, hipMemcpyHostToDevice, st) == hipSuccess;
-  }
-  // ... and a receiver copies it out after (the staging buffer is reused by the next chunk)
-  void get(int root, unsigned long long off, size_t len, hipStream_t st) {
-    if (rank != root)
-      copy_ok = copy_ok && hipMemcpyAsync(h.data() + off, d, len, hipMemcpyDeviceToHost, st) == hipSuccess;
-    copy_ok = copy_ok && hipStreamSynchronize(st) == hipSuccess;
-  }
-  // step (3): a receiver loads what it got; returns this rank's failure count for the verdict all-reduce
-  unsigned long long load(int root, unsigned long long nbytes) {
-    rc = copy_ok ? YM_OK : fail(YM_EHIP, "blob staging copy failed");
-    if (rc == YM_OK && rank != root) rc = ym_load_weights(c, h.data(), nbytes);
-    return rc == YM_OK ? 0ull : 1ull;
-  }
-};
-
-// The identical-on-every-rank verdict on step (1)'s sums: YM_OK or the error every rank returns before step (2).
-static int bcast_check(const unsigned long long h1[2], bool is_root, int root) {
-  if (h1[0] == 0)
-    return fail(YM_ESTATE, is_root ? "the root context has no weights to broadcast"
-                                   : "the root rank %d has no weights to broadcast", root);
-  if (h1[0] < sizeof(PlanHeader) || h1[0] > (1ull << 34)) return fail(YM_EBLOB, "broadcast blob size %llu", h1[0]);
-  if (h1[1]) return fail(YM_ENOMEM, "%llu rank(s) could not allocate the %zu-byte staging buffer", h1[1], kBcastChunk);
-  return YM_OK;
-}
-
-// The root rank's loaded blob (plan + weights, exactly the bytes its ym_load_weights received) goes to every rank
-// of `comm` over RCCL (xGMI) and each non-root rank loads it into `c` (ym_load_weights), so every rank ends with an
-// identical model without touching the file system.  Synchronous.
-// Every rank issues the same sequence of collectives whatever fails locally, so no rank is left waiting inside RCCL
-// for one that returned early: (1) an all-reduce (sum) of {root's blob size (0: the root has no weights), ranks
-// whose staging buffer failed to allocate}; only if both are valid, (2) the blob broadcast in kBcastChunk pieces
-// and (3) an all-reduce of the per-rank copy / load failures, so every rank returns the same verdict.  Errors in the
-// arguments themselves (null pointers, root out of range) are identical on every rank and return before any
-// collective; an RCCL error is communicator-wide.
-int ym_broadcast_weights(ym_ctx* c, void* comm, int root, void* stream) {
-  if (!c || !comm) return fail(YM_EINVAL, "null argument");
-  const Rccl* R = rccl();
-  if (!R) return fail(YM_ESTATE, "RCCL (librccl.so) is not available in this process");
-  int rank = -1, n = 0;
-  RCCLCK(R->user_rank(comm, &rank));
-  RCCLCK(R->count(comm, &n));
-  if (root < 0 || root >= n) return fail(YM_EINVAL, "root %d out of range (%d ranks)", root, n);
-  const hipStream_t st = static_cast<hipStream_t>(stream);
-  BcastRank me;
-  me.c = c;
-  me.rank = rank;
-  // control words in the context's scratch (allocated by ym_create, so nothing can fail before step 1)
-  unsigned long long* dctl = reinterpret_cast<unsigned long long*>(c->d_misc + kMiscBcast);
-  auto allreduce_sum = [&](unsigned long long* h, int cnt) -> int {
-    me.hip_ok = me.hip_ok && hipMemcpyAsync(dctl, h, 8 * cnt, hipMemcpyHostToDevice, st) == hipSuccess;
-    const int r = R->allreduce(dctl, dctl, cnt, kNcclUint64, kNcclSum, comm, st);
-    if (r) return r;
-    me.hip_ok = me.hip_ok && hipMemcpyAsync(h, dctl, 8 * cnt, hipMemcpyDeviceToHost, st) == hipSuccess &&
-                hipStreamSynchronize(st) == hipSuccess;
-    return 0;
-  };
-  unsigned long long h1[2] = {0ull, 0ull};
-  me.open(root, h1);
-  int r = allreduce_sum(h1, 2);  // (1)
-  if (r) return fail(YM_EHIP, "ncclAllReduce(size): %s", R->err(r));
-  if (int e = bcast_check(h1, rank == root, root)) return e;
-  const unsigned long long nbytes = h1[0];
-  if (rank != root) me.h.resize(nbytes);
-  for (unsigned long long off = 0; off < nbytes; off += kBcastChunk) {  // (2)
-    const size_t len = (size_t)std::min<unsigned long long>(kBcastChunk, nbytes - off);
-    me.put(root, off, len, st);
-    r = R->bcast(me.d, me.d, len, kNcclUint8, root, comm, st);
-    if (r) return fail(YM_EHIP, "ncclBroadcast(blob): %s", R->err(r));
-    me.get(root, off, len, st);
-  }
-  unsigned long long h3[1] = {me.load(root, nbytes)};  // (3)
-  r = allreduce_sum(h3, 1);
-  if (r) return fail(YM_EHIP, "ncclAllReduce(status): %s", R->err(r));
-  if (me.rc != YM_OK) return me.rc;
-  if (h3[0]) return fail(YM_EBLOB, "the weight broadcast failed on %llu other rank(s)", h3[0]);
-  return YM_OK;
-}
-
-// The fake backend of the same broadcast (N ranks as N contexts of this process, e.g. on one GPU):
-// rank i is ctxs[i]; the all-reduces are host sums and the chunk moves from the root's staging buffer to every
-// other rank's by a device-to-device copy on `stream`, between the same BcastRank put / get / load steps the RCCL
-// transport runs.  Returns the status of the first failing rank (every rank's context is left loaded or not as in
-// the RCCL path); on success every context holds the root's blob.
-int ym_broadcast_weights_local(ym_ctx* const* ctxs, int n, int root, void* stream) {
-  if (!ctxs || n < 1) return fail(YM_EINVAL, "null / empty context list");
-  if (root < 0 || root >= n) return fail(YM_EINVAL, "root %d out of range (%d ranks)", root, n);
-  for (int i = 0; i < n; ++i)
-    if (!ctxs[i]) return fail(YM_EINVAL, "null context for rank %d", i);
-  const hipStream_t st = static_cast<hipStream_t>(stream);
-  std::vector<BcastRank> ranks(n);
-  unsigned long long h1[2] = {0ull, 0ull};
-  for (int i = 0; i < n; ++i) {  // (1)
-    ranks[i].c = ctxs[i];
-    ranks[i].rank = i;
-    ranks[i].open(root, h1);
-  }
-  if (int e = bcast_check(h1, true, root)) return e;
-  const unsigned long long nbytes = h1[0];
-  for (int i = 0; i < n; ++i)
-    if (i != root) ranks[i].h.resize(nbytes);
-  for (unsigned long long off = 0; off < nbytes; off += kBcastChunk) {  // (2)
-    const size_t len = (size_t)std::min<unsigned long long>(kBcastChunk, nbytes - off);
-    ranks[root].put(root, off, len, st);
-    for (int i = 0; i < n; ++i)
-      if (i != root)
-        ranks[i].copy_ok = ranks[i].copy_ok && ranks[root].copy_ok &&
-                           hipMemcpyAsync(ranks[i].d, ranks[root].d, len, hipMemcpyDeviceToDevice, st) == hipSuccess;
-    for (int i = 0; i < n; ++i) ranks[i].get(root, off, len, st);
-  }
-  unsigned long long h3 = 0;  // (3)
-  for (int i = 0; i < n; ++i) h3 += ranks[i].load(root, nbytes);
-  for (int i = 0; i < n; ++i)
-    if (ranks[i].rc != YM_OK) return ranks[i].rc;
-  return h3 ? fail(YM_EBLOB, "the weight broadcast failed on %llu rank(s)", h3) : YM_OK;
-}
-
-// ---------------------------------------------------------------------------------------------- tracking
-// ByteTrack state of `streams` video streams in device memory; ym_track_update is one launch of csrc/ym_track.hip.
-static_assert(YM_TRACK_CAPACITY == kTrackCap && YM_TRACK_MAX_DET == kTrackMaxDet && YM_TRACK_MAX_STRIDE == kTrackMaxStride &&
-                  YM_TRACK_STATE_WORDS <= (int)(sizeof(TrackHead) / sizeof(int)), "yolomi.h states ym_track.h's limits");
-struct ym_tracker {
-  int device = 0, streams = 0, cap = 0;
-  ym_track_cfg cfg{};
-  TrackSlot* d_slots = nullptr;
-  TrackHead* d_heads = nullptr;
-  ~ym_tracker() {
-    if (d_slots || d_heads) (void)hipSetDevice(device);
-    if (d_slots) (void)hipFree(d_slots);
-    if (d_heads) (void)hipFree(d_heads);
-  }
-};
-
-int ym_track_create(ym_ctx* c, int streams, const ym_track_cfg* cfg, ym_tracker** out) {
-  if (!c || !cfg || !out) return fail(YM_EINVAL, "ym_track_create: null context, cfg or out");
-  if (streams < 1 || streams > YM_TRACK_MAX_STREAMS)
-    return fail(YM_EINVAL, "ym_track_create: %d streams (1..%d)", streams, YM_TRACK_MAX_STREAMS);
-  const double th[4] = {cfg->track_high_thresh, cfg->track_low_thresh, cfg->new_track_thresh, cfg->match_thresh};
-  for (double t : th)
-    if (!(t >= 0.0 && t <= 1.0)) return fail(YM_EINVAL, "ym_track_create: threshold %g outside [0, 1]", t);
-  if (cfg->track_buffer < 0 || cfg->capacity < 0 || cfg->capacity > YM_TRACK_CAPACITY)
-    return fail(YM_EINVAL, "ym_track_create: track_buffer %d (>= 0), capacity %d (0..%d)", cfg->track_buffer,
-                cfg->capacity, YM_TRACK_CAPACITY);
-  HIPCK(hipSetDevice(c->device));
-  ym_tracker* t = new ym_tracker();
-  t->device = c->device;
-  t->streams = streams;
-  t->cap = cfg->capacity ? cfg->capacity : YM_TRACK_CAPACITY;
-  t->cfg = *cfg;
-  const size_t sb = (size_t)streams * t->cap * sizeof(TrackSlot), hb = (size_t)streams * sizeof(TrackHead);
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&t->d_slots), sb);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&t->d_heads), hb);
-  if (e == hipSuccess) e = hipMemset(t->d_slots, 0, sb);
-  if (e == hipSuccess) e = hipMemset(t->d_heads, 0, hb);
-  if (e == hipSuccess) e = hipDeviceSynchronize();  // the first update may come on a non-blocking stream
-  if (e != hipSuccess) {
-    delete t;
-    return fail(e == hipErrorOutOfMemory ? YM_ENOMEM : YM_EHIP, "ym_track_create: %s", hipGetErrorString(e));
-  }
-  *out = t;
-  return YM_OK;
-}
-
-void ym_track_destroy(ym_tracker* t) { delete t; }
-
-int ym_track_reset(ym_tracker* t, void* stream) {
-  if (!t) return fail(YM_EINVAL, "null tracker");
-  HIPCK(hipSetDevice(t->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  HIPCK(hipMemsetAsync(t->d_slots, 0, (size_t)t->streams * t->cap * sizeof(TrackSlot), st));
-  HIPCK(hipMemsetAsync(t->d_heads, 0, (size_t)t->streams * sizeof(TrackHead), st));
-  return YM_OK;
-}
-
-int ym_track_update(ym_tracker* t, const float* d_dets, int det_stride, int B, int max_det, const int* d_counts,
-                    float* d_tracks, int* d_idx, int* d_track_counts, void* stream) {
-  if (!t) return fail(YM_EINVAL, "null tracker");
-  if (!d_dets || !d_counts || !d_tracks || !d_idx || !d_track_counts)
-    return fail(YM_EINVAL, "ym_track_update: null pointer");
-  if (B != t->streams) return fail(YM_EINVAL, "ym_track_update: batch %d, but the tracker holds %d streams", B, t->streams);
-  if (max_det < 1 || max_det > YM_TRACK_MAX_DET)
-    return fail(YM_EINVAL, "ym_track_update: max_det %d (1..%d)", max_det, YM_TRACK_MAX_DET);
-  if (det_stride < 6 || det_stride > YM_TRACK_MAX_STRIDE)
-    return fail(YM_EINVAL, "ym_track_update: row stride %d (6..%d)", det_stride, YM_TRACK_MAX_STRIDE);
-  HIPCK(hipSetDevice(t->device));
-  TrackArgs a{};
-  a.slots = t->d_slots; a.heads = t->d_heads; a.cap = t->cap;
-  a.dets = d_dets; a.det_stride = det_stride; a.max_det = max_det; a.counts = d_counts;
-  a.tracks = d_tracks; a.idx = d_idx; a.track_counts = d_track_counts;
-  a.high = (float)t->cfg.track_high_thresh; a.low = (float)t->cfg.track_low_thresh;
-  a.new_thresh = (float)t->cfg.new_track_thresh; a.match = t->cfg.match_thresh;
-  a.max_time_lost = t->cfg.track_buffer; a.fuse = t->cfg.fuse_score ? 1 : 0;
-  const hipError_t e = ym_launch_track(a, B, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(YM_EHIP, "track kernel: %s", hipGetErrorString(e));
-  return YM_OK;
-}
-
-int ym_track_read_state(ym_tracker* t, int* state, int n_streams) {
-  if (!t || !state) return fail(YM_EINVAL, "null tracker or state");
-  if (n_streams < 1 || n_streams > t->streams)
-    return fail(YM_EINVAL, "ym_track_read_state: %d streams of %d", n_streams, t->streams);
-  HIPCK(hipSetDevice(t->device));
-  HIPCK(hipDeviceSynchronize());
-  std::vector<TrackHead> h(n_streams);
-  HIPCK(hipMemcpy(h.data(), t->d_heads, (size_t)n_streams * sizeof(TrackHead), hipMemcpyDeviceToHost));
-  for (int b = 0; b < n_streams; ++b) {
-    int* o = state + (size_t)b * YM_TRACK_STATE_WORDS;
-    o[0] = h[b].frame_id; o[1] = h[b].issued + 1; o[2] = h[b].n_tracked;
-    o[3] = h[b].n_lost; o[4] = h[b].n_unconfirmed; o[5] = h[b].drops;
-  }
-  return YM_OK;
-}
-
-// ---------------------------------------------------------------------------------- annotated frames
-int ym_annotate(ym_ctx* c, const void* d_frames, int frames_are_f32_chw, int B, int H, int W, const float* d_dets,
-                int max_det, const int* d_counts, const unsigned char* d_masks, const long long* d_mask_offsets,
-                int mask_h, int mask_w, const int* d_mask_geo, const unsigned char* d_names, const ym_annotate_args* args,
-                unsigned char* d_out, void* stream) {
-  if (!c) return fail(YM_EINVAL, "null context");
-  if (!d_frames || !d_dets || !d_counts || !args || !d_out) return fail(YM_EINVAL, "ym_annotate: null pointer argument");
-  if (!args->d_font) return fail(YM_EINVAL, "ym_annotate: no font table (ym_annotate_args.d_font)");
-  if (B < 1 || B > 65535 || H < 1 || W < 1 || H > YM_ANNOT_MAX_SIDE || W > YM_ANNOT_MAX_SIDE)
-    return fail(YM_EINVAL, "ym_annotate: batch %d of %d x %d frames (1..65535 of 1..%d a side)", B, H, W, YM_ANNOT_MAX_SIDE);
-  if (max_det < 1 || max_det > (1 << 20)) return fail(YM_EINVAL, "ym_annotate: max_det %d", max_det);
-  if (args->line_width < 1 || args->line_width > kAnnotMaxLw || args->kpt_radius < 0 || args->kpt_radius > kAnnotMaxLw)
-    return fail(YM_EINVAL, "ym_annotate: line width %d (1..%d), keypoint radius %d (0..%d)", args->line_width, kAnnotMaxLw,
-                args->kpt_radius, kAnnotMaxLw);
-  if (args->K < 0 || args->K > kAnnotMaxK || (args->K > 0 && args->ndim != 2 && args->ndim != 3))
-    return fail(YM_EINVAL, "ym_annotate: keypoint shape (%d, %d) (K 0..%d, ndim 2 | 3)", args->K, args->ndim, kAnnotMaxK);
-  const int tracked = args->tracked ? 1 : 0;
-  if (args->det_stride < 6 + tracked + args->K * (args->K ? args->ndim : 0) || args->det_stride > (1 << 16))
-    return fail(YM_EINVAL, "ym_annotate: row stride %d below the %d values of a row with %d x %d keypoints",
-                args->det_stride, 6 + tracked + args->K * args->ndim, args->K, args->ndim);
-  if (args->color_mode != YM_ANNOT_COLOR_CLASS && args->color_mode != YM_ANNOT_COLOR_INSTANCE)
-    return fail(YM_EINVAL, "ym_annotate: color_mode %d", args->color_mode);
-  if (args->flags & ~(YM_ANNOT_BOXES | YM_ANNOT_LABELS | YM_ANNOT_CONF | YM_ANNOT_MASKS | YM_ANNOT_KPT_LINE | YM_ANNOT_CLIP_KPTS))
-    return fail(YM_EINVAL, "ym_annotate: unknown switch bits 0x%x", args->flags);
-  if (args->nc < 0 || (args->nc > 0 && !d_names)) return fail(YM_EINVAL, "ym_annotate: %d class names, null table", args->nc);
-  if (d_masks && (!d_mask_offsets || mask_h < 1 || mask_w < 1 || mask_h > YM_ANNOT_MAX_SIDE || mask_w > YM_ANNOT_MAX_SIDE ||
-                  args->mask_cap < 0))
-    return fail(YM_EINVAL, "ym_annotate: masks of %d x %d bytes, offsets %p, cap %d", mask_h, mask_w,
-                (const void*)d_mask_offsets, args->mask_cap);
-  HIPCK(hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const size_t need = (size_t)B * max_det;
-  if (need > c->annot_recs) {  // (an earlier call may still read the old records)
-    if (c->d_annot) {
-      HIPCK(hipDeviceSynchronize());
-      HIPCK(hipFree(c->d_annot));
-      c->d_annot = nullptr;
-      c->annot_recs = 0;
-    }
-    const hipError_t e = hipMalloc(&c->d_annot, need * sizeof(AnnotRec));
-    if (e != hipSuccess) {
-      c->d_annot = nullptr;
-      return fail(YM_ENOMEM, "ym_annotate: %zu records: %s", need, hipGetErrorString(e));
-    }
-    c->annot_recs = need;
-  }
-  AnnotArgs a{};
-  a.st.H = H; a.st.W = W; a.st.lw = args->line_width; a.st.radius = args->kpt_radius; a.st.flags = args->flags;
-  a.st.by_instance = args->color_mode == YM_ANNOT_COLOR_INSTANCE; a.st.tracked = tracked;
-  a.st.K = args->K; a.st.ndim = args->K ? args->ndim : 0; a.st.nc = args->nc;
-  a.st.det_stride = args->det_stride; a.st.max_det = max_det;
-  a.frames = d_frames; a.f32_chw = frames_are_f32_chw ? 1 : 0; a.B = B;
-  a.dets = d_dets; a.counts = d_counts;
-  a.masks = d_masks; a.mask_offsets = d_mask_offsets; a.mask_h = mask_h; a.mask_w = mask_w;
-  a.mask_cap = args->mask_cap ? args->mask_cap : max_det; a.mask_geo = d_mask_geo;
-  a.names = d_names; a.font = static_cast<const unsigned char*>(args->d_font);
-  a.recs = c->d_annot; a.out = d_out;
-  const hipError_t e = ym_launch_annotate(a, st);
-  if (e != hipSuccess) return fail(YM_EHIP, "annotate kernels: %s", hipGetErrorString(e));
-  return YM_OK;
-}
-
-// ---------------------------------------------------------------------------------- instance polygons
-int ym_mask_contours(ym_ctx* c, const unsigned char* d_masks, int n, int H, int W, long long plane_stride, int* d_points,
-                     long long cap_points, long long* d_offsets, void* stream) {
-  if (!c) return fail(YM_EINVAL, "null context");
-  if (!d_offsets || (n > 0 && !d_masks) || (cap_points > 0 && !d_points))
-    return fail(YM_EINVAL, "ym_mask_contours: null pointer argument");
-  if (n < 0 || H < 1 || W < 1 || (long long)H * W > kContourMaxPixels || cap_points < 0)
-    return fail(YM_EINVAL, "ym_mask_contours: %d planes of %d x %d (1 x 1 .. 2^27 pixels), capacity %lld", n, H, W, cap_points);
-  if (plane_stride < (long long)H * W)
-    return fail(YM_EINVAL, "ym_mask_contours: plane stride %lld below %d x %d", plane_stride, H, W);
-  HIPCK(hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const long long words = ym_ct_words(H, W);
-  const bool in_lds = words <= kContourLdsWords;
-  const size_t sel_bytes = ((size_t)n * sizeof(CtSel) + 255) & ~(size_t)255;
-  const size_t need = sel_bytes + (in_lds ? 0 : (size_t)n * (size_t)words * sizeof(uint32_t));
-  if (need > c->contour_bytes) {  // (an earlier call may still use the old scratch)
-    if (c->d_contour) {
-      HIPCK(hipDeviceSynchronize());
-      HIPCK(hipFree(c->d_contour));
-      c->d_contour = nullptr;
-      c->contour_bytes = 0;
-    }
-    const hipError_t e = hipMalloc(&c->d_contour, need);
-    if (e != hipSuccess) {
-      c->d_contour = nullptr;
-      return fail(YM_ENOMEM, "ym_mask_contours: %zu scratch bytes: %s", need, hipGetErrorString(e));
-    }
-    c->contour_bytes = need;
-  }
-  const hipError_t e = ym_launch_contours(d_masks, plane_stride, n, H, W,
-                                          in_lds ? nullptr : reinterpret_cast<uint32_t*>(c->d_contour + sel_bytes),
-                                          reinterpret_cast<CtSel*>(c->d_contour), d_points, cap_points, d_offsets, st);
-  if (e != hipSuccess) return fail(YM_EHIP, "contour kernels: %s", hipGetErrorString(e));
-  return YM_OK;
-}
-
-// ---------------------------------------------------------------------------------- run-length encoding
-int ym_mask_rle(ym_ctx* c, const unsigned char* d_masks, int n, int H, int W, long long plane_stride, unsigned int* d_counts,
-                long long cap_counts, unsigned char* d_bytes, long long cap_bytes, long long* d_run_offsets,
-                long long* d_byte_offsets, long long* d_area, void* stream) {
-  if (!c) return fail(YM_EINVAL, "null context");
-  if (!d_run_offsets || !d_byte_offsets || (n > 0 && (!d_masks || !d_area)) || (cap_counts > 0 && !d_counts) ||
-      (cap_bytes > 0 && !d_bytes))
-    return fail(YM_EINVAL, "ym_mask_rle: null pointer argument");
-  if (n < 0 || H < 1 || W < 1 || (long long)H * W > kRleMaxPixels || cap_counts < 0 || cap_bytes < 0)
-    return fail(YM_EINVAL, "ym_mask_rle: %d planes of %d x %d (1 x 1 .. 2^27 pixels), capacities %lld, %lld", n, H, W,
-                cap_counts, cap_bytes);
-  if (plane_stride < (long long)H * W)
-    return fail(YM_EINVAL, "ym_mask_rle: plane stride %lld below %d x %d", plane_stride, H, W);
-  const RleGeom g = ym_rle_geom(H, W);
-  const long long strips = (long long)n * g.strips;
-  if (strips > 0x7fffffffll) return fail(YM_EINVAL, "ym_mask_rle: %d planes of %d strips", n, g.strips);
-  HIPCK(hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t agg_bytes = pad((size_t)strips * sizeof(RleAgg)), set_bytes = pad((size_t)strips * sizeof(int));
-  const size_t total_bytes = pad((size_t)n * sizeof(RleAgg));
-  const size_t need = 2 * agg_bytes + set_bytes + total_bytes + (size_t)strips * g.CS * g.JS * sizeof(uint32_t);
-  if (need > c->rle_bytes) {  // (an earlier call may still use the old scratch)
-    if (c->d_rle) {
-      HIPCK(hipDeviceSynchronize());
-      HIPCK(hipFree(c->d_rle));
-      c->d_rle = nullptr;
-      c->rle_bytes = 0;
-    }
-    const hipError_t e = hipMalloc(&c->d_rle, need);
-    if (e != hipSuccess) {
-      c->d_rle = nullptr;
-      return fail(YM_ENOMEM, "ym_mask_rle: %zu scratch bytes: %s", need, hipGetErrorString(e));
-    }
-    c->rle_bytes = need;
-  }
-  RleScratch ws;
-  char* at = c->d_rle;
-  ws.own = reinterpret_cast<RleAgg*>(at);
-  ws.prefix = reinterpret_cast<RleAgg*>(at += agg_bytes);
-  ws.set = reinterpret_cast<int*>(at += agg_bytes);
-  ws.total = reinterpret_cast<RleAgg*>(at += set_bytes);
-  ws.words = reinterpret_cast<uint32_t*>(at += total_bytes);
-  const hipError_t e = ym_launch_rle(d_masks, plane_stride, n, g, ws, cap_counts > 0 ? d_counts : nullptr, cap_counts,
-                                     cap_bytes > 0 ? d_bytes : nullptr, cap_bytes, d_run_offsets, d_byte_offsets, d_area, st);
-  if (e != hipSuccess) return fail(YM_EHIP, "rle kernels: %s", hipGetErrorString(e));
-  return YM_OK;
+  return read_back(c->device, dst, c->d_arena + off, bytes);
 }
 
 int ym_sync(ym_ctx* c) {

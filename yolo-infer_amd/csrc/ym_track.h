@@ -1,4 +1,4 @@
-// Multi-object tracking behind the NMS (csrc/ym_track.hip; driven by ym_track_update in ym_runtime.cpp): Ultralytics
+// Multi-object tracking behind the NMS (csrc/ym_track.hip; driven by ym_track_update in ym_rt_track.cpp): Ultralytics
 // BYTETracker.update with bytetrack.yaml's defaults, one workgroup per stream, tracker state resident in device memory.
 //
 // This header holds what the kernel and a stand-alone host program share (tests/track_check.cpp includes only this

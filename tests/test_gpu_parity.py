@@ -848,9 +848,10 @@ NMS_VARIANTS = {"default": {}, "agnostic": {"agnostic": True}, "small_max_wh": {
 @pytest.mark.parametrize("dtype,B", [("f32", 2), ("x3", 8)])
 def test_nms_blocked_path_equals_per_box_path(dtype, B, variant):
     """csrc/ym_nms.hip nms_image's blocked path (NMS_BM = 512 < candidates <= NMS_BLK_MAX = 12,224 after max_nms:
-    keys sorted in LDS, then blocks of NMS_BLK = 256 candidates filtered against the kept list and scanned through
-    their own IoU bit matrix) against the one-box-per-barrier path it replaced (ym_set_debug(YM_DBG_NMS, 9)), on the
-    same forward's candidates at the validator's conf 0.001 and at 0.02 / 0.004: bit-identical rows and counts (greedy
+    keys sorted in LDS, then csrc/ym_nms_scan.h nms_blocked_scan: blocks of NMS_BLK = 256 candidates filtered against
+    the kept list and scanned through their own IoU bit matrix) against the one-box-per-barrier path it replaced
+    (ym_set_debug(YM_DBG_NMS, 9)), on the same forward's candidates at the validator's conf 0.001 and at 0.02 /
+    0.004: bit-identical rows and counts (greedy
     NMS is a function of the sorted candidates alone).  Variants: the class filter (cf) applies only when
     boxes of different classes cannot intersect — default max_wh 7680 with and without a `classes` filter (cf on),
     agnostic NMS and max_wh 64 (cf off: every kept box is tested)."""

@@ -1,6 +1,7 @@
 // Single-label class-offset greedy NMS on gfx950 (torchvision's result), one workgroup per image, and the
-// multi-workgroup presort of its keys.  The multi-label path: csrc/ym_nms_ml.hip.
-#include "ym_common.h"
+// multi-workgroup presort of its keys.  The multi-label path: csrc/ym_nms_ml.hip.  The steps the two share (the
+// one-wave word scan, the blocked greedy scan, the box / row / count helpers): csrc/ym_nms_scan.h.
+#include "ym_nms_scan.h"
 
 namespace {
 
@@ -13,20 +14,12 @@ namespace {
 constexpr int NMS_LDS = 4096;
 // (NMS_BM = 512, ym_common.h) bit-matrix path: 512 x 8 words of 64 bits (32 KB) behind the first 512 boxes
 // blocked path (NMS_BM < n, up to NMS_BLK_MAX candidates after max_nms, e.g. the validator's conf 0.001 at 640²: up to
-// A = 8,400): the keys sorted in LDS, then the greedy scan in blocks of NMS_BLK candidates in score order — a block's
-// candidates are first tested against every box kept by earlier blocks (the kept list in LDS), the survivors'
-// intra-block IoU bit matrix is built by all waves, and one wave scans it in order (as the bit-matrix path).
-// Candidate j is kept iff no kept i < j has IoU > iou: torchvision's greedy result, with a few barriers per block
-// instead of one per kept box.  Class filter (not agnostic, iou >= 0, max_wh above the boxes' coordinate range, nc <=
-// NMS_NC): boxes of different classes are offset cls * max_wh apart and cannot intersect (IoU 0, never > iou), so a
-// candidate is tested only against kept boxes of its class (per-class lists) and a bit-matrix word only where the
-// word holds a box of row i's class (per-word class masks).
+// A = 8,400): the keys sorted in LDS, then nms_blocked_scan (ym_nms_scan.h) over them, with its class filter when
+// also nc <= NMS_NC.
 // (NMS_SORT = 16384, ym_common.h: keys sorted in LDS, 128 KB, the whole LDS arena)
-constexpr int NMS_BLK = 256;     // candidates per block (bit matrix 256 x 4 words)
 constexpr int NMS_KEEP = 512;    // kept boxes held in LDS: max_det up to this on the blocked path
-constexpr int NMS_NC = 128;      // classes of the class filter
-constexpr int NMS_W = NMS_BLK / 64;
-// the block / kept-list regions (u64 units) sit at the end of the arena, behind the sorted keys they leave in place
+// the scan's block / kept-list regions and the block's anchor indices (u64 units) sit at the end of the arena, behind
+// the sorted keys they leave in place
 constexpr int NR_BB = 0, NR_BA = NR_BB + 2 * NMS_BLK, NR_BAI = NR_BA + NMS_BLK / 2, NR_BSUP = NR_BAI + NMS_BLK / 2,
               NR_BCLS = NR_BSUP + NMS_BLK / 2, NR_BMASK = NR_BCLS + NMS_BLK / 2, NR_CCM = NR_BMASK + NMS_BLK * NMS_W,
               NR_KB = NR_CCM + NMS_W * NMS_NC, NR_KA = NR_KB + 2 * NMS_KEEP, NR_KNEXT = NR_KA + NMS_KEEP / 2,
@@ -57,13 +50,28 @@ __device__ __forceinline__ void write_det(const NmsArgs& a, float* r, size_t anc
   } else {
     for (int m = 0; m < a.nm; ++m) r[6 + m] = a.anchors[anc * a.no_tot + a.mask_off + m];
   }
-  r[0] = fminf(fmaxf(v.x, 0.f), a.img_w);
-  r[1] = fminf(fmaxf(v.y, 0.f), a.img_h);
-  r[2] = fminf(fmaxf(v.z, 0.f), a.img_w);
-  r[3] = fminf(fmaxf(v.w, 0.f), a.img_h);
-  r[4] = sc;
-  r[5] = (float)cl;
+  nms_write_row6(r, v, sc, (float)cl, a.img_w, a.img_h);
 }
+
+// candidate i of the score order (ym_nms_scan.h, nms_blocked_scan's source): the anchor of sorted key i.  Class and
+// score are the anchor's; the block keeps its anchor indices (4 bytes per candidate) for the rows.
+struct AnchorSrc {
+  const NmsArgs& a;
+  const unsigned long long* keys;  // the sorted keys, in LDS
+  int* bai;                        // [NMS_BLK] anchor indices of the block
+  size_t ib;                       // the image's first anchor
+  float* out;
+  int rowlen;
+  __device__ __forceinline__ void cand(int i, int t, float4& box, int& cls) const {
+    const unsigned ai = nms_key_index(keys[i]);
+    box = a.boxes[ib + ai];
+    cls = a.cls[ib + ai];
+    bai[t] = (int)ai;
+  }
+  __device__ __forceinline__ void write_row(int t, int idx) const {
+    write_det(a, out + (size_t)idx * rowlen, ib + (size_t)bai[t]);
+  }
+};
 
 __global__ __launch_bounds__(NMS_T) void nms_image(const NmsArgs a) {
   // one LDS arena (128 KB), carved per path: keys [NMS_LDS], boxes [NMS_LDS], areas [NMS_LDS], flags [NMS_LDS] for the
@@ -104,14 +112,13 @@ __global__ __launch_bounds__(NMS_T) void nms_image(const NmsArgs a) {
       }
     }
     const int ne = n < a.max_nms ? n : a.max_nms;
-    const unsigned ai = 0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull);
+    const unsigned ai = nms_key_index(key);
     float4 bx = make_float4(0.f, 0.f, 0.f, 0.f);
     float ar = 0.f;
     if (lane < ne) {
-      const float4 v = a.boxes[ib + ai];
-      const float off = a.agnostic ? 0.0f : (float)a.cls[ib + ai] * a.max_wh;
-      bx = make_float4(v.x + off, v.y + off, v.z + off, v.w + off);
-      ar = __fmul_rn(__fsub_rn(bx.z, bx.x), __fsub_rn(bx.w, bx.y));
+      const NmsBox o = nms_offset_box(a.boxes[ib + ai], a.cls[ib + ai], a.agnostic, a.max_wh);
+      bx = o.b;
+      ar = o.area;
     }
     int sup = lane >= ne;
     int keep = 0, kept = 0;
@@ -130,10 +137,7 @@ __global__ __launch_bounds__(NMS_T) void nms_image(const NmsArgs a) {
       const int pos = __popcll(km & ((1ull << lane) - 1ull));
       write_det(a, out + (size_t)pos * rowlen, ib + ai);
     }
-    if (lane == 0) {
-      a.out_counts[b] = kept;
-      if (a.counts2) a.counts2[b] = kept;
-    }
+    if (lane == 0) nms_store_count(a.out_counts, a.counts2, b, kept);
     return;
   }
   if (n <= NMS_BM) {
@@ -162,12 +166,10 @@ __global__ __launch_bounds__(NMS_T) void nms_image(const NmsArgs a) {
     const int ne = n < a.max_nms ? n : a.max_nms;
     const int W = (ne + 63) >> 6;
     if (tid < ne) {
-      const unsigned ai = 0xFFFFFFFFu - (unsigned)(sorted[tid] & 0xFFFFFFFFull);
-      const float4 v = a.boxes[ib + ai];
-      const float off = a.agnostic ? 0.0f : (float)a.cls[ib + ai] * a.max_wh;
-      const float4 o = make_float4(v.x + off, v.y + off, v.z + off, v.w + off);
-      sbx[tid] = o;
-      sar[tid] = __fmul_rn(__fsub_rn(o.z, o.x), __fsub_rn(o.w, o.y));
+      const unsigned ai = nms_key_index(sorted[tid]);
+      const NmsBox o = nms_offset_box(a.boxes[ib + ai], a.cls[ib + ai], a.agnostic, a.max_wh);
+      sbx[tid] = o.b;
+      sar[tid] = o.area;
     }
     __syncthreads();
     if (a.dbg == 3) return;
@@ -185,67 +187,29 @@ __global__ __launch_bounds__(NMS_T) void nms_image(const NmsArgs a) {
     if (a.dbg == 4) return;
     __shared__ int keep_bm[NMS_BM], kept_bm;
     if (tid < 64) {
-      // greedy scan, 64 candidates per block: lane w holds removed-word w.  Within block k the decisions are a
-      // wave-uniform chain on scalar registers: rem (the block's removed bits) and each row's own diagonal word are
-      // read into SGPRs (readfirstlane / readlane), so a row costs a few scalar instructions, no exec-mask branch;
-      // the block's kept rows are then written in parallel and OR-reduced across the wave into the later words.
+      // greedy scan, 64 rows per word (nms_scan_word, ym_nms_scan.h); the removed words live in LDS, and a word's
+      // kept rows are written in parallel, then OR their later mask words into the later removed words
       const int lane = tid, cap = a.max_det;
-      // the removed words live in LDS: a kept row ORs its later mask words in with ds_or_b64 (one LDS atomic per
-      // word, no cross-lane reduction)
       __shared__ unsigned long long rem_w[NMS_BM / 64];
       if (lane < W) rem_w[lane] = 0ull;
       int kept = 0;
       for (int k = 0; k < W && kept < cap; ++k) {
         const int row = 64 * k + lane;
-        const unsigned long long diag = row < ne ? mask[row * W + k] : 0ull;
-        const unsigned dlo = (unsigned)diag, dhi = (unsigned)(diag >> 32);
-        const unsigned long long remv = rem_w[k];
-        unsigned long long remk =
-            ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)(remv >> 32)) << 32) |
-            (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)remv);
         const int jn = ne - 64 * k < 64 ? ne - 64 * k : 64;
-        // visit only the rows that are kept: the next one is the lowest bit of the block's not-yet-removed rows
-        // (a row's diagonal word only has bits above the row, so rows below it are final)
-        unsigned long long keepbits = 0;
-        int kk = kept;
-        unsigned long long avail = ~remk & (jn == 64 ? ~0ull : ((1ull << jn) - 1ull));
-        while (avail && kk < cap) {
-          const int j = __builtin_ctzll(avail);
-          keepbits |= 1ull << j;
-          ++kk;
-          remk |= ((unsigned long long)(unsigned)__builtin_amdgcn_readlane(dhi, j) << 32) |
-                  (unsigned long long)(unsigned)__builtin_amdgcn_readlane(dlo, j);
-          avail &= ~remk & ~((2ull << j) - 1ull);
-        }
+        const int q0 = kept;
+        const unsigned long long keepbits = nms_scan_word(row < ne ? mask[row * W + k] : 0ull, rem_w[k], jn, cap, kept);
         const bool mine = (keepbits >> lane) & 1ull;
-        if (mine) keep_bm[kept + __popcll(keepbits & ((1ull << lane) - 1ull))] = row;
-        // the block's kept rows OR their later mask words into the removed words: an OR across the wave (shuffles),
-        // one LDS write per word (per-lane LDS atomics on one address serialised, ~35 per block)
-        for (int w = k + 1; w < W; ++w) {
-          const unsigned long long v = mine ? mask[row * W + w] : 0ull;
-          unsigned vlo = (unsigned)v, vhi = (unsigned)(v >> 32);
-#pragma unroll
-          for (int o = 32; o > 0; o >>= 1) {
-            vlo |= (unsigned)__shfl_xor((int)vlo, o);
-            vhi |= (unsigned)__shfl_xor((int)vhi, o);
-          }
-          if (lane == 0) rem_w[w] |= ((unsigned long long)vhi << 32) | vlo;
-        }
-        kept = kk;
+        if (mine) keep_bm[q0 + nms_keep_slot(keepbits, lane)] = row;
+        for (int w = k + 1; w < W; ++w) nms_or_word(mine ? mask[row * W + w] : 0ull, &rem_w[w], lane);
       }
       if (lane == 0) kept_bm = kept;
     }
     __syncthreads();
     if (a.dbg == 5) return;
     const int kept = kept_bm;
-    for (int q = tid; q < kept; q += NMS_T) {
-      const unsigned ai = 0xFFFFFFFFu - (unsigned)(sorted[keep_bm[q]] & 0xFFFFFFFFull);
-      write_det(a, out + (size_t)q * rowlen, ib + ai);
-    }
-    if (tid == 0) {
-      a.out_counts[b] = kept;
-      if (a.counts2) a.counts2[b] = kept;
-    }
+    for (int q = tid; q < kept; q += NMS_T)
+      write_det(a, out + (size_t)q * rowlen, ib + nms_key_index(sorted[keep_bm[q]]));
+    if (tid == 0) nms_store_count(a.out_counts, a.counts2, b, kept);
     return;
   }
   if (n <= NMS_SORT && (n < a.max_nms ? n : a.max_nms) <= NMS_BLK_MAX && a.max_det <= NMS_KEEP && a.dbg != 9) {
@@ -260,159 +224,41 @@ __global__ __launch_bounds__(NMS_T) void nms_image(const NmsArgs a) {
     if (!(a.presorted && n > NMS_BM && n <= NMS_SORT)) bitonic_sort_desc(arena, n2, tid);
     if (a.dbg == 10) return;  // timing only: + the sort
     const int ne = n < a.max_nms ? n : a.max_nms;  // the sorted keys stay in arena[0, ne); the regions follow them
-    constexpr int W = NMS_W;
     unsigned long long* reg = arena + NMS_BLK_MAX;
-    float4* bb = reinterpret_cast<float4*>(reg + NR_BB);          // [NMS_BLK] class-offset boxes
-    float* ba = reinterpret_cast<float*>(reg + NR_BA);            // [NMS_BLK] areas
-    int* bai = reinterpret_cast<int*>(reg + NR_BAI);              // [NMS_BLK] anchor indices
-    unsigned* bsup = reinterpret_cast<unsigned*>(reg + NR_BSUP);  // [NMS_BLK] removed flags
-    int* bcls = reinterpret_cast<int*>(reg + NR_BCLS);            // [NMS_BLK] the class list each joins
-    unsigned long long* bmask = reg + NR_BMASK;                   // [NMS_BLK][W]
-    unsigned long long* ccm = reg + NR_CCM;                       // [W][NMS_NC] lanes of word w holding class c
-    float4* kb = reinterpret_cast<float4*>(reg + NR_KB);          // [NMS_KEEP] kept boxes
-    float* ka = reinterpret_cast<float*>(reg + NR_KA);            // [NMS_KEEP] their areas
-    int* knext = reinterpret_cast<int*>(reg + NR_KNEXT);          // [NMS_KEEP] per-class kept lists
-    int* khead = reinterpret_cast<int*>(reg + NR_KHEAD);          // [NMS_NC]
     __shared__ int blk_keep[NMS_BLK], blk_kept;
-    __shared__ unsigned long long blk_rem[W];
-    // class filter: exact when the class offsets separate every pair of boxes (decoded coordinates lie within
-    // +-reg_max * stride of the image: the 2,048 margin covers 16 bins x 64 px)
-    const bool cf = !a.agnostic && a.iou >= 0.0 && a.nc <= NMS_NC &&
-                    (double)a.max_wh >= (double)a.img_w + (double)a.img_h + 2048.0;
-    const int cap = a.max_det;  // <= NMS_KEEP
-    for (int i = tid; i < W * NMS_NC; i += NMS_T) ccm[i] = 0ull;
-    if (tid < NMS_NC) khead[tid] = -1;
-    __syncthreads();
-    int kept = 0;  // uniform: every thread reads blk_kept after the block's barrier
-    for (int b0 = 0; b0 < ne && kept < cap; b0 += NMS_BLK) {
-      const int nb = ne - b0 < NMS_BLK ? ne - b0 : NMS_BLK;
-      if (tid < nb) {
-        const unsigned ai = 0xFFFFFFFFu - (unsigned)(arena[b0 + tid] & 0xFFFFFFFFull);
-        const float4 v = a.boxes[ib + ai];
-        const int cl = a.cls[ib + ai];
-        const float off = a.agnostic ? 0.0f : (float)cl * a.max_wh;
-        const float4 o = make_float4(v.x + off, v.y + off, v.z + off, v.w + off);
-        bb[tid] = o;
-        ba[tid] = __fmul_rn(__fsub_rn(o.z, o.x), __fsub_rn(o.w, o.y));
-        bai[tid] = (int)ai;
-        const int c = cf ? cl : 0;
-        bcls[tid] = c;
-        if (cf) atomicOr(&ccm[(tid >> 6) * NMS_NC + c], 1ull << (tid & 63));
-      }
-      if (tid < NMS_BLK) bsup[tid] = tid >= nb;
-      __syncthreads();
-      if (tid < nb) {  // suppression by the boxes kept in earlier blocks (of this candidate's class)
-        bool sj = false;
-        for (int q = khead[bcls[tid]]; q >= 0 && !sj; q = knext[q]) sj = iou_gt(kb[q], ka[q], bb[tid], ba[tid], a.iou);
-        if (sj) bsup[tid] = 1u;
-      }
-      __syncthreads();
-      {  // the survivors' bit matrix: wave item (i, w) tests row i against boxes 64 w .. 64 w + 63 (ballot = word w);
-         // a word without a box of row i's class (or past i) is zero without a test
-        const int wv = tid >> 6, ln = tid & 63;
-        for (int pq = wv; pq < nb * W; pq += NMS_T / 64) {
-          const int i = pq / W, w = pq - i * W;
-          const int j = 64 * w + ln;
-          const int lo = i + 1 - 64 * w;  // lanes >= lo lie past row i
-          const unsigned long long past = lo <= 0 ? ~0ull : (lo >= 64 ? 0ull : ~0ull << lo);
-          const int hiw = nb - 64 * w;    // lanes < hiw lie inside the block
-          const unsigned long long in = hiw >= 64 ? ~0ull : (hiw <= 0 ? 0ull : ((1ull << hiw) - 1ull));
-          const unsigned long long cand = (cf ? ccm[w * NMS_NC + bcls[i]] : ~0ull) & past & in;
-          unsigned long long bits = 0ull;
-          if (!bsup[i] && cand) {  // (uniform)
-            const bool sij = ((cand >> ln) & 1ull) && !bsup[j] && iou_gt(bb[i], ba[i], bb[j], ba[j], a.iou);
-            bits = __ballot(sij);
-          }
-          if (ln == 0) bmask[pq] = bits;
-        }
-      }
-      __syncthreads();
-      if (tid < 64) {  // one wave: the block's greedy scan (the bit-matrix path's), removed words seeded by bsup
-        const int lane = tid;
-#pragma unroll
-        for (int w = 0; w < W; ++w) {
-          const unsigned long long r = __ballot(bsup[64 * w + lane] != 0u);
-          if (lane == 0) blk_rem[w] = r;
-        }
-        int kk = kept;
-        for (int k2 = 0; k2 < W && kk < cap; ++k2) {
-          const int jn = nb - 64 * k2 < 64 ? nb - 64 * k2 : 64;
-          if (jn <= 0) break;
-          const int row = 64 * k2 + lane;
-          const unsigned long long diag = row < nb ? bmask[row * W + k2] : 0ull;
-          const unsigned dlo = (unsigned)diag, dhi = (unsigned)(diag >> 32);
-          const unsigned long long remv = blk_rem[k2];
-          unsigned long long remk =
-              ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)(remv >> 32)) << 32) |
-              (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)remv);
-          unsigned long long keepbits = 0;
-          const int q0 = kk - kept;
-          unsigned long long avail = ~remk & (jn == 64 ? ~0ull : ((1ull << jn) - 1ull));
-          while (avail && kk < cap) {
-            const int j = __builtin_ctzll(avail);
-            keepbits |= 1ull << j;
-            ++kk;
-            remk |= ((unsigned long long)(unsigned)__builtin_amdgcn_readlane(dhi, j) << 32) |
-                    (unsigned long long)(unsigned)__builtin_amdgcn_readlane(dlo, j);
-            avail &= ~remk & ~((2ull << j) - 1ull);
-          }
-          const bool mine = (keepbits >> lane) & 1ull;
-          if (mine) blk_keep[q0 + __popcll(keepbits & ((1ull << lane) - 1ull))] = row;
-          for (int w = k2 + 1; w < W; ++w) {
-            const unsigned long long v = mine ? bmask[row * W + w] : 0ull;
-            unsigned vlo = (unsigned)v, vhi = (unsigned)(v >> 32);
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-              vlo |= (unsigned)__shfl_xor((int)vlo, o);
-              vhi |= (unsigned)__shfl_xor((int)vhi, o);
-            }
-            if (lane == 0) blk_rem[w] |= ((unsigned long long)vhi << 32) | vlo;
-          }
-        }
-        if (lane == 0) blk_kept = kk;
-      } else if (cf) {  // the other waves clear the class masks for the next block
-        for (int i = tid - 64; i < W * NMS_NC; i += NMS_T - 64) ccm[i] = 0ull;
-      }
-      __syncthreads();
-      const int kept2 = blk_kept;
-      for (int q = tid; q < kept2 - kept; q += NMS_T) {  // the block's kept boxes join their class lists; rows written
-        const int r = blk_keep[q], idx = kept + q;
-        kb[idx] = bb[r];
-        ka[idx] = ba[r];
-        knext[idx] = atomicExch(&khead[bcls[r]], idx);
-        write_det(a, out + (size_t)idx * rowlen, ib + (size_t)bai[r]);
-      }
-      kept = kept2;
-      __syncthreads();  // the kept lists are complete before the next block reads them; the block regions are free
-    }
-    if (tid == 0) {
-      a.out_counts[b] = kept;
-      if (a.counts2) a.counts2[b] = kept;
-    }
+    __shared__ unsigned long long blk_rem[NMS_W];
+    NmsBlockLds L;
+    L.bb = reinterpret_cast<float4*>(reg + NR_BB);
+    L.ba = reinterpret_cast<float*>(reg + NR_BA);
+    L.bsup = reinterpret_cast<unsigned*>(reg + NR_BSUP);
+    L.bcls = reinterpret_cast<int*>(reg + NR_BCLS);
+    L.bmask = reg + NR_BMASK;
+    L.ccm = reg + NR_CCM;
+    L.kb = reinterpret_cast<float4*>(reg + NR_KB);  // [NMS_KEEP], as ka and knext
+    L.ka = reinterpret_cast<float*>(reg + NR_KA);
+    L.knext = reinterpret_cast<int*>(reg + NR_KNEXT);
+    L.khead = reinterpret_cast<int*>(reg + NR_KHEAD);
+    L.blk_keep = blk_keep;
+    L.blk_kept = &blk_kept;
+    L.blk_rem = blk_rem;
+    const bool cf = a.nc <= NMS_NC && nms_class_filter(a.agnostic, a.iou, a.max_wh, a.img_w, a.img_h);
+    const AnchorSrc src{a, arena, reinterpret_cast<int*>(reg + NR_BAI), ib, out, rowlen};
+    const int kept = nms_blocked_scan(a, L, ne, a.max_det /* <= NMS_KEEP */, cf, tid, src);
+    if (tid == 0) nms_store_count(a.out_counts, a.counts2, b, kept);
     return;
   }
-  int n2 = 1;
-  while (n2 < n) n2 <<= 1;
-  const bool lds = n2 <= NMS_LDS;
-  unsigned long long* k = lds ? sk : gk;
-  if (lds) {
-    for (int i = tid; i < n2; i += NMS_T) sk[i] = i < n ? gk[i] : 0ull;
-  } else {
-    for (int i = n + tid; i < n2; i += NMS_T) gk[i] = 0ull;  // keys have a power-of-two stride >= A
-  }
-  __syncthreads();
-  if (n > 1) bitonic_sort_desc(k, n2, tid);
+  // the per-box path: keys sorted in LDS up to NMS_LDS of them (after padding), else in place in their global row
+  unsigned long long* k = nms_sort_keys(gk, sk, NMS_LDS, n, tid);
+  const bool lds = k == sk;
   if (n > a.max_nms) n = a.max_nms;
   float4* bx = lds ? sbx : a.sboxes + (size_t)b * a.A;
   float* ar = lds ? sar : a.sareas + (size_t)b * a.A;
   unsigned char* sup = lds ? ssup : a.sup + (size_t)b * a.A;
   for (int i = tid; i < n; i += NMS_T) {
-    const unsigned ai = 0xFFFFFFFFu - (unsigned)(k[i] & 0xFFFFFFFFull);
-    const float4 v = a.boxes[ib + ai];
-    const float off = a.agnostic ? 0.0f : (float)a.cls[ib + ai] * a.max_wh;
-    const float4 o = make_float4(v.x + off, v.y + off, v.z + off, v.w + off);
-    bx[i] = o;
-    ar[i] = __fmul_rn(__fsub_rn(o.z, o.x), __fsub_rn(o.w, o.y));
+    const unsigned ai = nms_key_index(k[i]);
+    const NmsBox o = nms_offset_box(a.boxes[ib + ai], a.cls[ib + ai], a.agnostic, a.max_wh);
+    bx[i] = o.b;
+    ar[i] = o.area;
     sup[i] = 0;
   }
   __syncthreads();
@@ -432,15 +278,9 @@ __global__ __launch_bounds__(NMS_T) void nms_image(const NmsArgs a) {
     __syncthreads();
   }
   __syncthreads();
-  for (int q = tid; q < kept; q += NMS_T) {
-    const int i = keep_pos[q];
-    const unsigned ai = 0xFFFFFFFFu - (unsigned)(k[i] & 0xFFFFFFFFull);
-    write_det(a, out + (size_t)q * rowlen, ib + ai);
-  }
-  if (tid == 0) {
-    a.out_counts[b] = kept;
-    if (a.counts2) a.counts2[b] = kept;
-  }
+  for (int q = tid; q < kept; q += NMS_T)
+    write_det(a, out + (size_t)q * rowlen, ib + nms_key_index(k[keep_pos[q]]));
+  if (tid == 0) nms_store_count(a.out_counts, a.counts2, b, kept);
 }
 
 }  // namespace

@@ -17,13 +17,11 @@
 //   3. ml_sort_chunks / ml_sort_merge: 2,048-key chunks sorted in LDS, then every key ranked against the other chunks
 //      (the scheme of nms_presort_* in csrc/ym_nms.hip; 32,768 keys do not fit in LDS at once, so the other chunks
 //      pass through it one at a time).
-//   4. nms_ml_image: nms_image's blocked greedy scan (blocks of 256 candidates in score order against the kept list,
-//      an intra-block bit matrix, one wave scanning it) with the class and the score taken from the key, the sorted
-//      keys read from global memory and up to 1,024 kept boxes.  Same arithmetic: iou_gt (csrc/ym_common.h), offset
-//      cls * max_wh added in fp32, rows clipped as write_det does.
+//   4. nms_ml_image: nms_blocked_scan (csrc/ym_nms_scan.h), the scan nms_image's blocked path runs, over the sorted
+//      keys in global memory, with the class and the score taken from the key and up to 1,024 kept boxes.
 // Every pass recomputes the scores from the fp32 anchor buffer with decode_anchors' ym_sigmoid on the same logit, so a
 // pair that is also its anchor's single-label candidate has the bit-identical score; boxes are decode_anchors' own.
-#include "ym_common.h"
+#include "ym_nms_scan.h"
 
 namespace {
 
@@ -262,163 +260,61 @@ __global__ __launch_bounds__(NMS_T) void ml_sort_merge(const MlArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------- NMS
-constexpr int MB_BLK = 256;    // candidates per block
 constexpr int MB_KEEP = 1024;  // kept boxes in LDS: max_det up to this
-constexpr int MB_NC = 128;     // classes of the class filter (and of the key's class field)
-constexpr int MB_W = MB_BLK / 64;
+
+// candidate i of the score order (ym_nms_scan.h, nms_blocked_scan's source): sorted key i of the image's global row.
+// Class and score are the key's; the block keeps its keys (8 bytes per candidate) for the rows.
+struct PairSrc {
+  const NmsArgs& a;
+  const unsigned long long* keys;  // the sorted selected keys, in global memory
+  unsigned long long* bkey;        // [NMS_BLK] keys of the block
+  size_t ib;                       // the image's first anchor
+  float* out;
+  __device__ __forceinline__ unsigned anchor(unsigned pair) const {
+    const unsigned ai = pair >> 7;
+    return ai < (unsigned)a.A ? ai : 0;  // (a selected key always names an anchor of the image)
+  }
+  __device__ __forceinline__ void cand(int i, int t, float4& box, int& cls) const {
+    const unsigned long long key = keys[i];
+    const unsigned pair = nms_key_index(key);
+    box = a.boxes[ib + anchor(pair)];
+    cls = (int)(pair & 127u);
+    bkey[t] = key;
+  }
+  __device__ __forceinline__ void write_row(int t, int idx) const {
+    const unsigned long long key = bkey[t];
+    const unsigned pair = nms_key_index(key);
+    nms_write_row6(out + (size_t)idx * 6, a.boxes[ib + anchor(pair)], __uint_as_float((unsigned)(key >> 32)),
+                   (float)(pair & 127u), a.img_w, a.img_h);
+  }
+};
 
 // NmsArgs as nms_image takes them, except: keys = the sorted selected keys (kstride per image), counts = their
 // number per image; scores / cls are unused (both come from the key); nm = 0.
 __global__ __launch_bounds__(NMS_T) void nms_ml_image(const NmsArgs a) {
-  __shared__ float4 bb[MB_BLK];                    // class-offset boxes of the block
-  __shared__ float ba[MB_BLK];                     // areas
-  __shared__ unsigned long long bkey[MB_BLK];      // keys
-  __shared__ unsigned bsup[MB_BLK];                // removed flags
-  __shared__ int bcls[MB_BLK];                     // the class list each joins
-  __shared__ unsigned long long bmask[MB_BLK * MB_W];
-  __shared__ unsigned long long ccm[MB_W * MB_NC];  // lanes of word w holding class c
-  __shared__ float4 kb[MB_KEEP];                   // kept boxes
+  __shared__ float4 bb[NMS_BLK];
+  __shared__ float ba[NMS_BLK];
+  __shared__ unsigned long long bkey[NMS_BLK];
+  __shared__ unsigned bsup[NMS_BLK];
+  __shared__ int bcls[NMS_BLK];
+  __shared__ unsigned long long bmask[NMS_BLK * NMS_W];
+  __shared__ unsigned long long ccm[NMS_W * NMS_NC];
+  __shared__ float4 kb[MB_KEEP];
   __shared__ float ka[MB_KEEP];
-  __shared__ int knext[MB_KEEP];                   // per-class kept lists
-  __shared__ int khead[MB_NC];
-  __shared__ int blk_keep[MB_BLK], blk_kept;
-  __shared__ unsigned long long blk_rem[MB_W];
-  constexpr int W = MB_W;
+  __shared__ int knext[MB_KEEP];
+  __shared__ int khead[NMS_NC];
+  __shared__ int blk_keep[NMS_BLK], blk_kept;
+  __shared__ unsigned long long blk_rem[NMS_W];
   const int b = blockIdx.x, tid = threadIdx.x;
   int ne = a.counts[b];
   if (ne > a.max_nms) ne = a.max_nms;
   if (ne > a.kstride) ne = a.kstride;
   if (ne < 0) ne = 0;
-  const unsigned long long* gk = a.keys + (size_t)b * a.kstride;
-  const size_t ib = (size_t)b * a.A;
-  float* out = a.dets + (size_t)b * a.max_det * 6;
-  // class filter: as nms_image's (exact when the class offsets separate every pair of boxes); otherwise every
-  // candidate joins list 0 and is tested against every kept box
-  const bool cf = !a.agnostic && a.iou >= 0.0 && (double)a.max_wh >= (double)a.img_w + (double)a.img_h + 2048.0;
-  const int cap = a.max_det < MB_KEEP ? a.max_det : MB_KEEP;
-  for (int i = tid; i < W * MB_NC; i += NMS_T) ccm[i] = 0ull;
-  if (tid < MB_NC) khead[tid] = -1;
-  __syncthreads();
-  int kept = 0;  // uniform: every thread reads blk_kept after the block's barrier
-  for (int b0 = 0; b0 < ne && kept < cap; b0 += MB_BLK) {
-    const int nb = ne - b0 < MB_BLK ? ne - b0 : MB_BLK;
-    if (tid < nb) {
-      const unsigned long long key = gk[b0 + tid];
-      const unsigned idx = 0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull);
-      unsigned ai = idx >> 7;
-      if (ai >= (unsigned)a.A) ai = 0;  // (a selected key always names an anchor of the image)
-      const int cl = (int)(idx & 127u);
-      const float4 v = a.boxes[ib + ai];
-      const float off = a.agnostic ? 0.0f : (float)cl * a.max_wh;
-      const float4 o = make_float4(v.x + off, v.y + off, v.z + off, v.w + off);
-      bb[tid] = o;
-      ba[tid] = __fmul_rn(__fsub_rn(o.z, o.x), __fsub_rn(o.w, o.y));
-      bkey[tid] = key;
-      const int c = cf ? cl : 0;
-      bcls[tid] = c;
-      if (cf) atomicOr(&ccm[(tid >> 6) * MB_NC + c], 1ull << (tid & 63));
-    }
-    if (tid < MB_BLK) bsup[tid] = tid >= nb;
-    __syncthreads();
-    if (tid < nb) {  // suppression by the boxes kept in earlier blocks (of this candidate's class list)
-      bool sj = false;
-      for (int q = khead[bcls[tid]]; q >= 0 && !sj; q = knext[q]) sj = iou_gt(kb[q], ka[q], bb[tid], ba[tid], a.iou);
-      if (sj) bsup[tid] = 1u;
-    }
-    __syncthreads();
-    {  // the survivors' bit matrix: wave item (i, w) tests row i against boxes 64 w .. 64 w + 63 (ballot = word w)
-      const int wv = tid >> 6, ln = tid & 63;
-      for (int pq = wv; pq < nb * W; pq += NMS_T / 64) {
-        const int i = pq / W, w = pq - i * W;
-        const int j = 64 * w + ln;
-        const int lo = i + 1 - 64 * w;  // lanes >= lo lie past row i
-        const unsigned long long past = lo <= 0 ? ~0ull : (lo >= 64 ? 0ull : ~0ull << lo);
-        const int hiw = nb - 64 * w;    // lanes < hiw lie inside the block
-        const unsigned long long in = hiw >= 64 ? ~0ull : (hiw <= 0 ? 0ull : ((1ull << hiw) - 1ull));
-        const unsigned long long cand = (cf ? ccm[w * MB_NC + bcls[i]] : ~0ull) & past & in;
-        unsigned long long bits = 0ull;
-        if (!bsup[i] && cand) {  // (uniform)
-          const bool sij = ((cand >> ln) & 1ull) && !bsup[j] && iou_gt(bb[i], ba[i], bb[j], ba[j], a.iou);
-          bits = __ballot(sij);
-        }
-        if (ln == 0) bmask[pq] = bits;
-      }
-    }
-    __syncthreads();
-    if (tid < 64) {  // one wave: the block's greedy scan, removed words seeded by bsup
-      const int lane = tid;
-#pragma unroll
-      for (int w = 0; w < W; ++w) {
-        const unsigned long long r = __ballot(bsup[64 * w + lane] != 0u);
-        if (lane == 0) blk_rem[w] = r;
-      }
-      int kk = kept;
-      for (int k2 = 0; k2 < W && kk < cap; ++k2) {
-        const int jn = nb - 64 * k2 < 64 ? nb - 64 * k2 : 64;
-        if (jn <= 0) break;
-        const int row = 64 * k2 + lane;
-        const unsigned long long diag = row < nb ? bmask[row * W + k2] : 0ull;
-        const unsigned dlo = (unsigned)diag, dhi = (unsigned)(diag >> 32);
-        const unsigned long long remv = blk_rem[k2];
-        unsigned long long remk =
-            ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)(remv >> 32)) << 32) |
-            (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)remv);
-        unsigned long long keepbits = 0;
-        const int q0 = kk - kept;
-        unsigned long long avail = ~remk & (jn == 64 ? ~0ull : ((1ull << jn) - 1ull));
-        while (avail && kk < cap) {
-          const int j = __builtin_ctzll(avail);
-          keepbits |= 1ull << j;
-          ++kk;
-          remk |= ((unsigned long long)(unsigned)__builtin_amdgcn_readlane(dhi, j) << 32) |
-                  (unsigned long long)(unsigned)__builtin_amdgcn_readlane(dlo, j);
-          avail &= ~remk & ~((2ull << j) - 1ull);
-        }
-        const bool mine = (keepbits >> lane) & 1ull;
-        if (mine) blk_keep[q0 + __popcll(keepbits & ((1ull << lane) - 1ull))] = row;
-        for (int w = k2 + 1; w < W; ++w) {
-          const unsigned long long v = mine ? bmask[row * W + w] : 0ull;
-          unsigned vlo = (unsigned)v, vhi = (unsigned)(v >> 32);
-#pragma unroll
-          for (int o = 32; o > 0; o >>= 1) {
-            vlo |= (unsigned)__shfl_xor((int)vlo, o);
-            vhi |= (unsigned)__shfl_xor((int)vhi, o);
-          }
-          if (lane == 0) blk_rem[w] |= ((unsigned long long)vhi << 32) | vlo;
-        }
-      }
-      if (lane == 0) blk_kept = kk;
-    } else if (cf) {  // the other waves clear the class masks for the next block
-      for (int i = tid - 64; i < W * MB_NC; i += NMS_T - 64) ccm[i] = 0ull;
-    }
-    __syncthreads();
-    const int kept2 = blk_kept;  // <= cap <= MB_KEEP; kept2 - kept <= nb <= MB_BLK
-    for (int q = tid; q < kept2 - kept; q += NMS_T) {  // the block's kept boxes join their class lists; rows written
-      const int r = blk_keep[q], idx = kept + q;
-      kb[idx] = bb[r];
-      ka[idx] = ba[r];
-      knext[idx] = atomicExch(&khead[bcls[r]], idx);
-      // the row, clipped as write_det does; score and class from the key
-      const unsigned long long key = bkey[r];
-      const unsigned pidx = 0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull);
-      unsigned ai = pidx >> 7;
-      if (ai >= (unsigned)a.A) ai = 0;
-      const float4 v = a.boxes[ib + ai];
-      float* o = out + (size_t)idx * 6;
-      o[0] = fminf(fmaxf(v.x, 0.f), a.img_w);
-      o[1] = fminf(fmaxf(v.y, 0.f), a.img_h);
-      o[2] = fminf(fmaxf(v.z, 0.f), a.img_w);
-      o[3] = fminf(fmaxf(v.w, 0.f), a.img_h);
-      o[4] = __uint_as_float((unsigned)(key >> 32));
-      o[5] = (float)(pidx & 127u);
-    }
-    kept = kept2;
-    __syncthreads();  // the kept lists are complete before the next block reads them; the block regions are free
-  }
-  if (tid == 0) {
-    a.out_counts[b] = kept;
-    if (a.counts2) a.counts2[b] = kept;
-  }
+  const NmsBlockLds L{bb, ba, bsup, bcls, bmask, ccm, kb, ka, knext, khead, blk_keep, &blk_kept, blk_rem};
+  const PairSrc src{a, a.keys + (size_t)b * a.kstride, bkey, (size_t)b * a.A, a.dets + (size_t)b * a.max_det * 6};
+  const bool cf = nms_class_filter(a.agnostic, a.iou, a.max_wh, a.img_w, a.img_h);
+  const int kept = nms_blocked_scan(a, L, ne, a.max_det < MB_KEEP ? a.max_det : MB_KEEP, cf, tid, src);
+  if (tid == 0) nms_store_count(a.out_counts, a.counts2, b, kept);
 }
 
 }  // namespace
@@ -428,7 +324,7 @@ const void* ym_nms_ml_kernel() { return reinterpret_cast<const void*>(&nms_ml_im
 // stop_after (YM_DBG_NMS 21 / 22, timing only): 21 = the candidate stage and the selection, 22 = + the sort
 hipError_t ym_launch_nms_ml(const MlArgs& m0, const NmsArgs& n, hipStream_t st) {
   MlArgs m = m0;
-  if (m.nc < 2 || m.nc > MB_NC || m.B < 1 || m.A < 1 || m.max_nms < 1 || m.cap < ML_CH || m.cap % ML_CH || m.cap > ML_MAXCH * ML_CH ||
+  if (m.nc < 2 || m.nc > NMS_NC || m.B < 1 || m.A < 1 || m.max_nms < 1 || m.cap < ML_CH || m.cap % ML_CH || m.cap > ML_MAXCH * ML_CH ||
       m.max_nms > m.cap || (long)m.A * 128 >= (1L << 30) || n.nm != 0 || n.max_det > MB_KEEP || n.kstride != m.cap)
     return hipErrorInvalidValue;
   m.div_nc = ym_fdiv(m.nc);

@@ -19,7 +19,7 @@
 //
 // Plain fp32: the pair function is a transcendental chain (log, exp, sqrt, two divisions) over five sums, not a GEMM,
 // so matrix instructions have nothing to multiply.  The >= comparison is made in one place, probiou_ge.
-#include "ym_common.h"
+#include "ym_nms_scan.h"
 
 namespace {
 
@@ -164,27 +164,14 @@ __global__ __launch_bounds__(NMS_T) void obb_sort_gather(const ObbArgs a) {
   unsigned long long* gk = a.keys + (size_t)b * a.kstride;
   int n = a.counts[b];
   if (n > a.A) n = a.A;
-  int n2 = 1;
-  while (n2 < n) n2 <<= 1;
-  const bool lds = n2 <= NMS_SORT;
   // the presort kernels take exactly the images with NMS_BM < n <= NMS_SORT (ym_nms.hip); every other image is sorted
   // here: in LDS, or (n above NMS_SORT) in place in its key row, whose stride is a power of two >= A
   const bool sorted = a.presort && n > NMS_BM && n <= NMS_SORT;
-  const unsigned long long* k = gk;
-  if (!sorted) {
-    if (lds) {
-      for (int i = tid; i < n2; i += NMS_T) arena[i] = i < n ? gk[i] : 0ull;
-    } else {
-      for (int i = n + tid; i < n2; i += NMS_T) gk[i] = 0ull;
-    }
-    __syncthreads();
-    if (n > 1) bitonic_sort_desc(lds ? arena : gk, n2, tid);
-    if (lds) k = arena;
-  }
+  const unsigned long long* k = sorted ? gk : nms_sort_keys(gk, arena, NMS_SORT, n, tid);
   const int ne = n < a.max_nms ? n : a.max_nms;
   const size_t ib = (size_t)b * a.A;
   for (int i = tid; i < ne; i += NMS_T) {
-    unsigned anc = 0xFFFFFFFFu - (unsigned)(k[i] & 0xFFFFFFFFull);
+    unsigned anc = nms_key_index(k[i]);
     if (anc >= (unsigned)a.A) anc = 0;  // (not a key obb_decode wrote: never read out of bounds)
     const float4 v = a.boxes[ib + anc], c = a.cov[ib + anc];
     const int cl = a.cls[ib + anc];
@@ -211,7 +198,7 @@ __global__ __launch_bounds__(OBB_T) void obb_nms_flags(const ObbArgs a) {
   if (live) { j0 = src[2 * j]; j1 = src[2 * j + 1]; }
   const int cj = __float_as_int(j1.z);
   // different classes are cls * max_wh apart in x and cannot overlap: nms_image's class filter, under its condition
-  const bool cf = !a.agnostic && a.iou >= 0.0 && (double)a.max_wh >= (double)a.img_w + (double)a.img_h + 2048.0;
+  const bool cf = nms_class_filter(a.agnostic, a.iou, a.max_wh, a.img_w, a.img_h);
   bool sup = false;
   float4 p0 = j0, p1 = j0;
   if (tid < ne) { p0 = src[2 * tid]; p1 = src[2 * tid + 1]; }  // tile 0

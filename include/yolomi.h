@@ -256,6 +256,26 @@ int ym_masks_native(ym_ctx* ctx, const float* d_dets, int det_stride, int B, int
 int ym_letterbox(ym_ctx* ctx, const void* d_src, int h, int w, int row_bytes, int bgr, int uh, int uw, int top,
                  int left, float* d_dst, int Hn, int Wn, void* stream);
 
+/* Frame batches (csrc/ym_letterbox_batch.hip): ym_letterbox's work, bit for bit, for B HWC uint8 frames that live in
+ * device memory (decoded video, camera buffers), as ONE launch that writes the whole (B, 3, Hn, Wn) fp32 batch: frame
+ * b's descriptor says where its pixels are (src: any address, rows row_bytes apart, pixels 3 bytes apart) and, as
+ * ym_letterbox's arguments, how it lies in the canvas; frames of different sizes share the launch.  scale_x / scale_y
+ * are 1.0 / ((double)uw / w) and 1.0 / ((double)uh / h), computed by the caller in double exactly so.  d_desc / h_desc:
+ * the B descriptors on the device, which the kernel reads, and the same on the host, where they are validated.  The
+ * kernel reads source bytes of the frames only (16-byte loads where a whole word lies inside a frame, single bytes at
+ * its two ends).  YM_EINVAL, before any launch: a null pointer, B outside 1..65535, Hn < 1, Wn no positive multiple
+ * of 4, d_dst not 16-byte aligned, and per frame ym_letterbox's checks (a null src, a size below 1, a negative offset,
+ * a window that leaves the canvas, row_bytes < 3 * w), bgr outside 0..1, or a scale that is not the value above.
+ * Asynchronous on `stream`. */
+typedef struct {
+  const void* src;               /* the frame's first byte, in device memory */
+  int h, w, row_bytes, bgr;      /* the frame; bgr = 1 for cv2 order */
+  int uh, uw, top, left;         /* resized (unpadded) size and its offset in the canvas */
+  double scale_x, scale_y;       /* 1.0 / ((double)uw / w), 1.0 / ((double)uh / h) */
+} ym_letterbox_desc;
+int ym_letterbox_batch(ym_ctx* ctx, const ym_letterbox_desc* d_desc, const ym_letterbox_desc* h_desc, int B,
+                       float* d_dst, int Hn, int Wn, void* stream);
+
 /* Test-time augmentation for detect plans (Ultralytics predict / val with augment=True, DetectionModel._predict_augment):
  * three passes at scales (1, 0.83, 0.67), the middle one mirrored along W, their decoded heads de-scaled, de-flipped,
  * clipped (_clip_augmented: pass 0 loses its last A0 / 21 anchors, pass 2 its first (A2 / 21) * 16) and concatenated in

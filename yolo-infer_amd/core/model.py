@@ -286,8 +286,21 @@ class YOLO11Model:
 
     # ------------------------------------------------------------------ hot path
     def _as_batch(self, source, imgsz: int = 640):
-        """(batch tensor on the device, LoadTensor eps, image-source info or None).  Tensors follow LoadTensor; paths,
-        directories, HWC uint8 BGR ndarrays and PIL images are letterboxed on the GPU (yolomi/preprocess.py)."""
+        """(batch tensor on the device, LoadTensor eps, image-source info or None).  Float tensors follow LoadTensor;
+        paths, directories, HWC uint8 BGR ndarrays and PIL images are letterboxed on the GPU (yolomi/preprocess.py), and
+        so are frames that are there already — a (B, H, W, 3) uint8 tensor or a list of (H, W, 3) ones, BGR, on the
+        model's device — by one launch for the batch (letterbox_frames)."""
+        from yolomi.preprocess import is_frame_source
+        if is_frame_source(source):  # uint8 HWC frames on the device: one launch, then the ndarray sources' path
+            from yolomi.preprocess import batch_geometry, letterbox_frames
+            frames = list(source.unbind(0)) if isinstance(source, torch.Tensor) else list(source)
+            stream = torch.cuda.current_stream(self._dev).cuda_stream
+            geo = batch_geometry(frames, imgsz)
+            im, shapes = letterbox_frames(self.model.engine.rt, frames, self._dev, imgsz, 32, stream, geo=geo)
+            # Results.orig_img: a copy on the device (the caller may reuse its frame buffers), moved to the host on access
+            kept = list(source.clone().unbind(0)) if isinstance(source, torch.Tensor) else [f.clone() for f in frames]
+            return im, torch.finfo(torch.float32).eps, (kept, [f"image{i}.jpg" for i in range(len(frames))], shapes,
+                                                        [(g[0], g[1], g[2], g[4]) for g in geo])
         if isinstance(source, (list, tuple)) and source and all(isinstance(s, torch.Tensor) for s in source):
             source = torch.stack(list(source))
         if not isinstance(source, torch.Tensor):
@@ -334,6 +347,10 @@ class YOLO11Model:
         ignored = [k for k in ("conf", "iou", "max_det", "augment", "retina_masks") if k in kwargs]
         if ignored:
             logger.debug(f"classify: {', '.join(ignored)} ignored")
+        from yolomi.preprocess import is_frame_source
+        if is_frame_source(source):
+            raise NotImplementedError("classify models do not take uint8 device frames (classify_transforms reads host "
+                                      "images): pass ndarrays, or a preprocessed float (B, 3, H, W) tensor")
         t0 = time.perf_counter()
         eng = self.model.engine
         imgs = paths = None

@@ -552,6 +552,11 @@ struct LetterboxArgs {
   float* dst; int Hn, Wn;                              // one image of the fp32 NCHW batch (3 planes of Hn x Wn)
 };
 
+struct LetterboxBatchArgs {            // csrc/ym_letterbox_batch.hip: LetterboxArgs' work for a batch, one launch
+  const ym_letterbox_desc* desc;       // (B) on the device
+  float* dst; int B, Hn, Wn;           // the (B, 3, Hn, Wn) fp32 batch, 16-byte aligned; Wn a multiple of 4
+};
+
 constexpr int kClsPreMaxScale = 64;  // ym_cls_pre.hip: the largest source / resized ratio per axis (LDS tables, stage)
 struct ClsPreArgs {                  // csrc/ym_cls_pre.hip: classify_transforms for a batch, one launch
   const unsigned char* images;       // the packed HWC uint8 images, 16-byte aligned
@@ -624,6 +629,7 @@ void ym_debug_add(int key, int d);
 const void* ym_nms_kernel();  // the NMS kernel's function (graph replays re-point its output rows: ym_infer)
 hipError_t ym_launch_stem(int dtype, const ConvArgs& a, hipStream_t st);
 hipError_t ym_launch_letterbox(const LetterboxArgs& a, hipStream_t st);
+hipError_t ym_launch_letterbox_batch(const LetterboxBatchArgs& a, hipStream_t st);  // ym_letterbox_batch.hip
 hipError_t ym_launch_cls_pre(const ClsPreArgs& a, hipStream_t st);  // ym_cls_pre.hip
 int ym_cls_pre_taps(int in, int out);  // Pillow's ksize of one axis: 2 * ceil(max(in / out, 1)) + 1
 hipError_t ym_launch_spin(int usec, hipStream_t st);  // profiling: park the stream for usec (wall clock)

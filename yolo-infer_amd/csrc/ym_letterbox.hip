@@ -6,27 +6,9 @@
 // One thread per output pixel; the source (a few MB) is read through L2 with 3-byte gathers — HBM-bound at the
 // output write (12 B per pixel), far below the network's cost.
 #include "ym_common.h"
+#include "ym_letterbox_axis.h"
 
 namespace {
-
-__device__ __forceinline__ double opaque_d(double x) {
-  asm volatile("" : "+v"(x));
-  return x;
-}
-
-// source index pair and 11-bit weights of destination index d (oracle/letterbox.py _axis)
-__device__ __forceinline__ void axis(int d, int src, double scale, int& s0, int& s1, int& a0, int& a1, bool& edge) {
-  float f = (float)(opaque_d((d + 0.5) * scale) - 0.5);  // (double) (d + .5)·scale − .5 in two roundings, to float
-  int s = (int)floorf(f);
-  f -= (float)s;
-  edge = false;
-  if (s < 0) { f = 0.f; s = 0; }
-  if (s >= src - 1) { f = 0.f; s = src - 1; edge = true; }
-  a0 = (int)rintf((1.f - f) * 2048.f);
-  a1 = (int)rintf(f * 2048.f);
-  s0 = s;
-  s1 = s + 1 < src ? s + 1 : src - 1;
-}
 
 __global__ __launch_bounds__(256) void letterbox_u8(const LetterboxArgs a) {
   const int i = blockIdx.x * 256 + threadIdx.x;

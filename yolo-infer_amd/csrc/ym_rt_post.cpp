@@ -38,6 +38,30 @@ int ym_letterbox(ym_ctx* c, const void* d_src, int h, int w, int row_bytes, int 
   return launched(ym_launch_letterbox(a, static_cast<hipStream_t>(stream)), "letterbox launch");
 }
 
+int ym_letterbox_batch(ym_ctx* c, const ym_letterbox_desc* d_desc, const ym_letterbox_desc* h_desc, int B,
+                       float* d_dst, int Hn, int Wn, void* stream) {
+  if (!c) return fail(YM_EINVAL, "null context");
+  if (!d_desc || !h_desc || !d_dst) return fail(YM_EINVAL, "ym_letterbox_batch: null pointer");
+  if (B < 1 || B > 65535) return fail(YM_EINVAL, "ym_letterbox_batch: B %d outside 1..65535", B);
+  if (Hn < 1 || Wn < 4 || Wn % 4) return fail(YM_EINVAL, "ym_letterbox_batch: bad canvas %dx%d (Wn: a multiple of 4)", Hn, Wn);
+  if (reinterpret_cast<uintptr_t>(d_dst) & 15) return fail(YM_EINVAL, "ym_letterbox_batch: d_dst not 16-byte aligned");
+  for (int b = 0; b < B; ++b) {
+    const ym_letterbox_desc& d = h_desc[b];
+    if (!d.src || d.h < 1 || d.w < 1 || d.uh < 1 || d.uw < 1 || d.top < 0 || d.left < 0 ||
+        (long long)d.top + d.uh > Hn || (long long)d.left + d.uw > Wn || d.row_bytes < 3 * (long long)d.w ||
+        (d.bgr != 0 && d.bgr != 1))
+      return fail(YM_EINVAL, "ym_letterbox_batch: frame %d: bad geometry (%dx%d, rows %d bytes -> %dx%d at (%d, %d) in "
+                  "%dx%d, bgr %d)", b, d.h, d.w, d.row_bytes, d.uh, d.uw, d.top, d.left, Hn, Wn, d.bgr);
+    if (d.scale_x != 1.0 / ((double)d.uw / d.w) || d.scale_y != 1.0 / ((double)d.uh / d.h))
+      return fail(YM_EINVAL, "ym_letterbox_batch: frame %d: scales (%.17g, %.17g) are not 1 / (uw / w), 1 / (uh / h)", b,
+                  d.scale_x, d.scale_y);
+  }
+  HIPCK(hipSetDevice(c->device));
+  LetterboxBatchArgs a{};
+  a.desc = d_desc; a.dst = d_dst; a.B = B; a.Hn = Hn; a.Wn = Wn;
+  return launched(ym_launch_letterbox_batch(a, static_cast<hipStream_t>(stream)), "letterbox_batch launch");
+}
+
 int ym_classify_pre(ym_ctx* c, const void* d_images, const ym_cls_pre_desc* d_desc, const ym_cls_pre_desc* h_desc,
                     int B, int imgsz, float* d_dst, void* stream) {
   if (!c) return fail(YM_EINVAL, "null context");

@@ -6,6 +6,8 @@ has the same shape, else every image goes to imgsz x imgsz), stacks them, flips 
 divides by 255.  Here the geometry is computed on the host (`letterbox_geometry`, the same arithmetic as
 `LetterBox.__call__`), each image is copied to the device once, and `ym_letterbox` (csrc/ym_letterbox.hip) writes
 its slot of the fp32 NCHW batch.  Detections are mapped back with `scale_boxes` (upstream `ops.scale_boxes`).
+Frames that are on the device already (uint8 HWC tensors) skip the copy: `letterbox_frames` writes the whole batch
+with one `ym_letterbox_batch` launch (csrc/ym_letterbox_batch.hip), the same bits.
 Classify models take upstream's `classify_transforms` instead: `classify_batch` (Pillow, on the host: the reference)
 and `classify_batch_gpu` (`ym_classify_pre`, csrc/ym_cls_pre.hip: one copy and one launch per batch, the same bits).
 Reference call sites: /root/reference/demos/detection_demo.py:87-93, 190-196 (path / ndarray sources).
@@ -98,6 +100,65 @@ def letterbox_batch(rt, imgs: Sequence[np.ndarray], device: torch.device, imgsz:
         rt.letterbox(im.data_ptr(), h, w, im.stride(0), True, g[0], g[1], g[2], g[4], out[i].data_ptr(), Hn, Wn,
                      stream)
     return out, [im.shape[:2] for im in imgs]
+
+
+# ym_letterbox_desc (include/yolomi.h): one frame of a ym_letterbox_batch launch
+LB_DESC = np.dtype([("src", "<u8"), ("h", "<i4"), ("w", "<i4"), ("row_bytes", "<i4"), ("bgr", "<i4"), ("uh", "<i4"),
+                    ("uw", "<i4"), ("top", "<i4"), ("left", "<i4"), ("scale_x", "<f8"), ("scale_y", "<f8")])
+
+
+def is_frame_source(source) -> bool:
+    """A predict() source of device frames: a (B, H, W, 3) uint8 tensor or a list of (H, W, 3) uint8 tensors."""
+    if isinstance(source, torch.Tensor):
+        return source.dtype == torch.uint8 and source.dim() == 4 and source.shape[3] == 3
+    return (isinstance(source, (list, tuple)) and len(source) > 0 and all(
+        isinstance(s, torch.Tensor) and s.dtype == torch.uint8 and s.dim() == 3 and s.shape[2] == 3 for s in source))
+
+
+def frames_desc(frames: Sequence[torch.Tensor], geo: Sequence[Tuple], bgr: bool = True) -> np.ndarray:
+    """The LB_DESC table of (H, W, 3) uint8 frames with their batch_geometry: each frame's address and row stride as
+    they are (no copy), the scales in double as ym_letterbox forms them."""
+    desc = np.zeros(len(frames), dtype=LB_DESC)
+    for i, (f, g) in enumerate(zip(frames, geo)):
+        if f.dtype != torch.uint8 or f.dim() != 3 or f.shape[2] != 3 or f.shape[0] < 1 or f.shape[1] < 1:
+            raise TypeError(f"frame {i}: expected a non-empty (H, W, 3) uint8 tensor, got {tuple(f.shape)} {f.dtype}")
+        if f.stride(2) != 1 or f.stride(1) != 3 or f.stride(0) < 3 * f.shape[1]:
+            raise ValueError(f"frame {i}: strides {tuple(f.stride())} are not interleaved HWC rows (channel stride 1, "
+                             f"pixel stride 3, row stride >= 3 * W); make the frame contiguous")
+        h, w = int(f.shape[0]), int(f.shape[1])
+        desc[i] = (f.data_ptr(), h, w, f.stride(0), int(bool(bgr)), g[0], g[1], g[2], g[4], 1.0 / (g[1] / w),
+                   1.0 / (g[0] / h))
+    return desc
+
+
+def letterbox_frames(rt, frames, device: torch.device, imgsz: int = 640, stride: int = 32, stream: int = 0,
+                     bgr: bool = True, geo: Sequence[Tuple] = None) -> Tuple[torch.Tensor, List[Tuple[int, int]]]:
+    """letterbox_batch for frames that already live on `device`: a (B, H, W, 3) uint8 tensor or a list of (H, W, 3)
+    uint8 tensors (any row stride; slices of wider tensors as they are).  The geometry is batch_geometry's; one small
+    descriptor table goes up through pinned memory and ONE ym_letterbox_batch launch (csrc/ym_letterbox_batch.hip)
+    writes the (B, 3, Hn, Wn) fp32 batch — no host sync, no copy of a pixel, the same bits as letterbox_batch.  The
+    table is copied on the current stream of `device`, which `stream` should be."""
+    device = torch.device(device)
+    frames = list(frames.unbind(0)) if isinstance(frames, torch.Tensor) and frames.dim() == 4 else list(frames)
+    if not frames:
+        raise ValueError("letterbox_frames: no frames")
+    for i, f in enumerate(frames):
+        if not isinstance(f, torch.Tensor):
+            raise TypeError(f"frame {i}: expected a torch.Tensor, got {type(f).__name__}")
+        if f.device != device:
+            raise ValueError(f"frame {i} is on {f.device}: frames must be on the model's device ({device}); pass "
+                             f"host images as ndarrays")
+    if geo is None:
+        geo = batch_geometry(frames, imgsz, stride)
+    desc = frames_desc(frames, geo, bgr)
+    uh, uw, t, b, l, r = geo[0]
+    Hn, Wn = uh + t + b, uw + l + r
+    host = torch.empty(desc.nbytes, dtype=torch.uint8, pin_memory=device.type == "cuda")
+    host.numpy()[:] = desc.view(np.uint8)
+    dtab = host.to(device, non_blocking=True)  # (the pinned block is recycled only once this copy has run)
+    out = torch.empty((len(frames), 3, Hn, Wn), dtype=torch.float32, device=device)
+    rt.letterbox_batch(dtab.data_ptr(), desc.ctypes.data, len(frames), out.data_ptr(), Hn, Wn, stream)
+    return out, [tuple(f.shape[:2]) for f in frames]
 
 
 def classify_geometry(h: int, w: int, imgsz: int = 224) -> Tuple[int, int, int, int]:

@@ -276,6 +276,37 @@ typedef struct {
 int ym_letterbox_batch(ym_ctx* ctx, const ym_letterbox_desc* d_desc, const ym_letterbox_desc* h_desc, int B,
                        float* d_dst, int Hn, int Wn, void* stream);
 
+/* NV12 frame batches (csrc/ym_letterbox_nv12.hip): ym_letterbox_batch's work for B frames as a hardware decoder hands
+ * them out — a full-resolution Y plane and a half-resolution plane of interleaved U, V bytes, each with a pitch of its
+ * own — as ONE launch with no converted frame in between.  The result is, bit for bit, ym_letterbox_batch's (bgr = 1)
+ * for the frame converted to packed BGR by this integer rule (OpenCV's COLOR_YUV2BGR_NV12 form; int32 arithmetic, >> an
+ * arithmetic shift), with Y at (r, c) and U, V the bytes 2 * (c / 2) and 2 * (c / 2) + 1 of uv row r / 2:
+ *   yy = max(0, Y - y_off) * CY
+ *   R = clamp_u8((yy + (1 << 19) + CVR * (V - 128)) >> 20)
+ *   G = clamp_u8((yy + (1 << 19) + CVG * (V - 128) + CUG * (U - 128)) >> 20)
+ *   B = clamp_u8((yy + (1 << 19) + CUB * (U - 128)) >> 20)
+ * coef = (y_off, CY, CUB, CUG, CVG, CVR): the standard and range are the caller's (yolomi.preprocess.nv12_coefficients
+ * holds BT.601 / BT.709, limited and full range).  d_desc / h_desc and the canvas are as ym_letterbox_batch's.  The
+ * kernel reads bytes of the two planes only: [y, y + (h - 1) * y_pitch + w) and [uv, uv + (h / 2 - 1) * uv_pitch + w).
+ * YM_EINVAL, before any launch: everything ym_letterbox_batch refuses, a null plane, an odd h or w, a pitch below w,
+ * y_off outside 0..255, CY <= 0, or coefficients whose sums could leave int32
+ * (255 * CY + 128 * max(|CUB|, |CUG| + |CVG|, |CVR|) + 2^19 >= 2^31).  Asynchronous on `stream`. */
+typedef struct {
+  const void* y;  const void* uv;        /* the planes' first bytes, in device memory */
+  int h, w, y_pitch, uv_pitch;           /* h, w even; pitches >= w */
+  int uh, uw, top, left;                 /* resized (unpadded) size and its offset in the canvas */
+  double scale_x, scale_y;               /* as ym_letterbox_desc */
+} ym_nv12_desc;
+int ym_letterbox_nv12(ym_ctx* ctx, const ym_nv12_desc* d_desc, const ym_nv12_desc* h_desc, int B,
+                      const int coef[6], float* d_dst, int Hn, int Wn, void* stream);
+
+/* The conversion alone: one NV12 frame to packed (h, w, 3) uint8 BGR at d_bgr, rows row_bytes >= 3 * w apart, by the
+ * rule above (Results.orig_img, plot() and save() of NV12 sources; not on the per-frame path).  YM_EINVAL: a null
+ * pointer, an odd or non-positive h or w, a pitch below w, row_bytes < 3 * w, or coef as above.  Asynchronous on
+ * `stream`. */
+int ym_nv12_to_bgr(ym_ctx* ctx, const void* y, const void* uv, int h, int w, int y_pitch, int uv_pitch,
+                   const int coef[6], void* d_bgr, int row_bytes, void* stream);
+
 /* Test-time augmentation for detect plans (Ultralytics predict / val with augment=True, DetectionModel._predict_augment):
  * three passes at scales (1, 0.83, 0.67), the middle one mirrored along W, their decoded heads de-scaled, de-flipped,
  * clipped (_clip_augmented: pass 0 loses its last A0 / 21 anchors, pass 2 its first (A2 / 21) * 16) and concatenated in

@@ -289,8 +289,19 @@ class YOLO11Model:
         """(batch tensor on the device, LoadTensor eps, image-source info or None).  Float tensors follow LoadTensor;
         paths, directories, HWC uint8 BGR ndarrays and PIL images are letterboxed on the GPU (yolomi/preprocess.py), and
         so are frames that are there already — a (B, H, W, 3) uint8 tensor or a list of (H, W, 3) ones, BGR, on the
-        model's device — by one launch for the batch (letterbox_frames)."""
-        from yolomi.preprocess import is_frame_source
+        model's device — by one launch for the batch (letterbox_frames).  NV12Frames (decoder surfaces on the device) are
+        converted and letterboxed by one launch too (letterbox_nv12)."""
+        from yolomi.preprocess import NV12Frames, is_frame_source
+        if isinstance(source, NV12Frames):  # Y and UV planes on the device: one launch, then the ndarray sources' path
+            from yolomi.preprocess import batch_geometry, letterbox_nv12
+            rt = self.model.engine.rt
+            stream = torch.cuda.current_stream(self._dev).cuda_stream
+            geo = batch_geometry(source.y, imgsz)
+            im, shapes = letterbox_nv12(rt, source, self._dev, imgsz, 32, stream, geo=geo)
+            kept = source.clone()  # Results.orig_img: device copies of the planes, converted to BGR on first access
+            return im, torch.finfo(torch.float32).eps, ([kept.image(rt, i) for i in range(len(kept))],
+                                                        [f"image{i}.jpg" for i in range(len(kept))], shapes,
+                                                        [(g[0], g[1], g[2], g[4]) for g in geo])
         if is_frame_source(source):  # uint8 HWC frames on the device: one launch, then the ndarray sources' path
             from yolomi.preprocess import batch_geometry, letterbox_frames
             frames = list(source.unbind(0)) if isinstance(source, torch.Tensor) else list(source)
@@ -347,8 +358,8 @@ class YOLO11Model:
         ignored = [k for k in ("conf", "iou", "max_det", "augment", "retina_masks") if k in kwargs]
         if ignored:
             logger.debug(f"classify: {', '.join(ignored)} ignored")
-        from yolomi.preprocess import is_frame_source
-        if is_frame_source(source):
+        from yolomi.preprocess import NV12Frames, is_frame_source
+        if is_frame_source(source) or isinstance(source, NV12Frames):
             raise NotImplementedError("classify models do not take uint8 device frames (classify_transforms reads host "
                                       "images): pass ndarrays, or a preprocessed float (B, 3, H, W) tensor")
         t0 = time.perf_counter()

@@ -536,9 +536,11 @@ class Results:
         """HWC uint8 copy of the input image, as upstream `convert_torch2numpy_batch` makes it
         ((x.permute(1,2,0)*255).clamp(0,255).to(uint8)); materialised (one device→host copy) on first access.  An
         image source's is the image itself; a device frame's (uint8 HWC tensor sources) is copied to the host on first
-        access too."""
+        access too, and an NV12 frame's (NV12Frames sources) is converted to BGR on the device first."""
         if isinstance(self._orig_img, torch.Tensor):  # a device frame source: its kept copy, moved on first access
             self._orig_img = self._orig_img.cpu().numpy()
+        elif hasattr(self._orig_img, "to_bgr"):  # an NV12 frame source: converted (ym_nv12_to_bgr) on first access
+            self._orig_img = self._orig_img.to_bgr()
         if self._orig_img is None and self._orig_tensor is not None:
             t = self._orig_tensor
             self._orig_img = (t.permute(1, 2, 0).contiguous() * 255).clamp_(0, 255).to(torch.uint8).cpu().numpy()

@@ -557,7 +557,21 @@ struct LetterboxBatchArgs {            // csrc/ym_letterbox_batch.hip: Letterbox
   float* dst; int B, Hn, Wn;           // the (B, 3, Hn, Wn) fp32 batch, 16-byte aligned; Wn a multiple of 4
 };
 
-constexpr int kClsPreMaxScale = 64;  // ym_cls_pre.hip: the largest source / resized ratio per axis (LDS tables, stage)
+struct Nv12Coef { int y_off, cy, cub, cug, cvg, cvr; };  // the YUV → BGR integers (2^20 fixed point), include/yolomi.h
+
+struct LetterboxNv12Args {             // csrc/ym_letterbox_nv12.hip: LetterboxBatchArgs' work for NV12 surfaces
+  const ym_nv12_desc* desc;            // (B) on the device
+  Nv12Coef coef;
+  float* dst; int B, Hn, Wn;           // the (B, 3, Hn, Wn) fp32 batch, 16-byte aligned; Wn a multiple of 4
+};
+
+struct Nv12ToBgrArgs {                 // csrc/ym_letterbox_nv12.hip: one NV12 frame to packed (h, w, 3) uint8 BGR
+  const unsigned char* y; const unsigned char* uv; int h, w, y_pitch, uv_pitch;  // h, w even
+  Nv12Coef coef;
+  unsigned char* bgr; int row_bytes;   // rows row_bytes >= 3 * w apart
+};
+
+constexpr int kClsPreMaxScale = 64;// ym_cls_pre.hip: the largest source / resized ratio per axis (LDS tables, stage)
 struct ClsPreArgs {                  // csrc/ym_cls_pre.hip: classify_transforms for a batch, one launch
   const unsigned char* images;       // the packed HWC uint8 images, 16-byte aligned
   const ym_cls_pre_desc* desc;       // (B) on the device
@@ -630,6 +644,8 @@ const void* ym_nms_kernel();  // the NMS kernel's function (graph replays re-poi
 hipError_t ym_launch_stem(int dtype, const ConvArgs& a, hipStream_t st);
 hipError_t ym_launch_letterbox(const LetterboxArgs& a, hipStream_t st);
 hipError_t ym_launch_letterbox_batch(const LetterboxBatchArgs& a, hipStream_t st);  // ym_letterbox_batch.hip
+hipError_t ym_launch_letterbox_nv12(const LetterboxNv12Args& a, hipStream_t st);    // ym_letterbox_nv12.hip
+hipError_t ym_launch_nv12_to_bgr(const Nv12ToBgrArgs& a, hipStream_t st);
 hipError_t ym_launch_cls_pre(const ClsPreArgs& a, hipStream_t st);  // ym_cls_pre.hip
 int ym_cls_pre_taps(int in, int out);  // Pillow's ksize of one axis: 2 * ceil(max(in / out, 1)) + 1
 hipError_t ym_launch_spin(int usec, hipStream_t st);  // profiling: park the stream for usec (wall clock)

@@ -2,6 +2,7 @@
 // annotator, contours and run-length encoding behind it.  None launches a plan op: each takes a context for its device,
 // the prototypes its last forward left (the mask stages) or a scratch buffer of its own that grows on demand.
 #include <algorithm>
+#include <cstdlib>
 #include "ym_runtime.h"
 #include "ym_annot.h"
 #include "ym_contour.h"
@@ -60,6 +61,58 @@ int ym_letterbox_batch(ym_ctx* c, const ym_letterbox_desc* d_desc, const ym_lett
   LetterboxBatchArgs a{};
   a.desc = d_desc; a.dst = d_dst; a.B = B; a.Hn = Hn; a.Wn = Wn;
   return launched(ym_launch_letterbox_batch(a, static_cast<hipStream_t>(stream)), "letterbox_batch launch");
+}
+
+// coef[6] of the NV12 entries → the kernels' Nv12Coef, refused when a converted channel's sum could leave int32
+static int nv12_coef(const char* who, const int* coef, Nv12Coef& k) {
+  if (!coef) return fail(YM_EINVAL, "%s: null coef", who);
+  k = Nv12Coef{coef[0], coef[1], coef[2], coef[3], coef[4], coef[5]};
+  const long long chroma = std::max({std::llabs((long long)k.cub), std::llabs((long long)k.cug) + std::llabs((long long)k.cvg),
+                                     std::llabs((long long)k.cvr)});
+  if (k.y_off < 0 || k.y_off > 255 || k.cy <= 0 || 255LL * k.cy + 128 * chroma + (1 << 19) >= (1LL << 31))
+    return fail(YM_EINVAL, "%s: bad coefficients (y_off %d, CY %d, CUB %d, CUG %d, CVG %d, CVR %d)", who, k.y_off, k.cy,
+                k.cub, k.cug, k.cvg, k.cvr);
+  return YM_OK;
+}
+
+int ym_letterbox_nv12(ym_ctx* c, const ym_nv12_desc* d_desc, const ym_nv12_desc* h_desc, int B, const int coef[6],
+                      float* d_dst, int Hn, int Wn, void* stream) {
+  if (!c) return fail(YM_EINVAL, "null context");
+  if (!d_desc || !h_desc || !d_dst) return fail(YM_EINVAL, "ym_letterbox_nv12: null pointer");
+  if (B < 1 || B > 65535) return fail(YM_EINVAL, "ym_letterbox_nv12: B %d outside 1..65535", B);
+  if (Hn < 1 || Wn < 4 || Wn % 4) return fail(YM_EINVAL, "ym_letterbox_nv12: bad canvas %dx%d (Wn: a multiple of 4)", Hn, Wn);
+  if (reinterpret_cast<uintptr_t>(d_dst) & 15) return fail(YM_EINVAL, "ym_letterbox_nv12: d_dst not 16-byte aligned");
+  LetterboxNv12Args a{};
+  if (int rc = nv12_coef("ym_letterbox_nv12", coef, a.coef)) return rc;
+  for (int b = 0; b < B; ++b) {
+    const ym_nv12_desc& d = h_desc[b];
+    if (!d.y || !d.uv || d.h < 2 || d.w < 2 || (d.h & 1) || (d.w & 1) || d.y_pitch < d.w || d.uv_pitch < d.w ||
+        d.uh < 1 || d.uw < 1 || d.top < 0 || d.left < 0 || (long long)d.top + d.uh > Hn || (long long)d.left + d.uw > Wn)
+      return fail(YM_EINVAL, "ym_letterbox_nv12: frame %d: bad geometry (%dx%d (both even), pitches %d / %d -> %dx%d at "
+                  "(%d, %d) in %dx%d)", b, d.h, d.w, d.y_pitch, d.uv_pitch, d.uh, d.uw, d.top, d.left, Hn, Wn);
+    if (d.scale_x != 1.0 / ((double)d.uw / d.w) || d.scale_y != 1.0 / ((double)d.uh / d.h))
+      return fail(YM_EINVAL, "ym_letterbox_nv12: frame %d: scales (%.17g, %.17g) are not 1 / (uw / w), 1 / (uh / h)", b,
+                  d.scale_x, d.scale_y);
+  }
+  HIPCK(hipSetDevice(c->device));
+  a.desc = d_desc; a.dst = d_dst; a.B = B; a.Hn = Hn; a.Wn = Wn;
+  return launched(ym_launch_letterbox_nv12(a, static_cast<hipStream_t>(stream)), "letterbox_nv12 launch");
+}
+
+int ym_nv12_to_bgr(ym_ctx* c, const void* y, const void* uv, int h, int w, int y_pitch, int uv_pitch, const int coef[6],
+                   void* d_bgr, int row_bytes, void* stream) {
+  if (!c) return fail(YM_EINVAL, "null context");
+  if (!y || !uv || !d_bgr || h < 2 || w < 2 || (h & 1) || (w & 1) || h > 4 * 65535 || y_pitch < w || uv_pitch < w ||
+      row_bytes < 3 * (long long)w)
+    return fail(YM_EINVAL, "bad ym_nv12_to_bgr geometry (%dx%d (both even), pitches %d / %d, BGR rows %d bytes)", h, w,
+                y_pitch, uv_pitch, row_bytes);
+  Nv12ToBgrArgs a{};
+  if (int rc = nv12_coef("ym_nv12_to_bgr", coef, a.coef)) return rc;
+  HIPCK(hipSetDevice(c->device));
+  a.y = static_cast<const unsigned char*>(y); a.uv = static_cast<const unsigned char*>(uv);
+  a.h = h; a.w = w; a.y_pitch = y_pitch; a.uv_pitch = uv_pitch;
+  a.bgr = static_cast<unsigned char*>(d_bgr); a.row_bytes = row_bytes;
+  return launched(ym_launch_nv12_to_bgr(a, static_cast<hipStream_t>(stream)), "nv12_to_bgr launch");
 }
 
 int ym_classify_pre(ym_ctx* c, const void* d_images, const ym_cls_pre_desc* d_desc, const ym_cls_pre_desc* h_desc,

@@ -94,6 +94,8 @@ def load_library(path: os.PathLike = LIB_PATH):
         "ym_masks_native": (I, [P, P, I, I, I, P, I, I, I, C.POINTER(I), P, P, P, P, P]),
         "ym_letterbox": (I, [P, P, I, I, I, I, I, I, I, I, P, I, I, P]),
         "ym_letterbox_batch": (I, [P, P, P, I, P, I, I, P]),
+        "ym_letterbox_nv12": (I, [P, P, P, I, C.POINTER(I), P, I, I, P]),
+        "ym_nv12_to_bgr": (I, [P, P, P, I, I, I, I, C.POINTER(I), P, I, P]),
         "ym_get_op_cfg": (I, [P, I, I, I, C.POINTER(I), I]),
         "ym_set_op_cfg": (I, [P, I, I, I, C.POINTER(I), I]),
         "ym_get_op_cfg_taken": (I, [P, I, I, I, C.POINTER(I), I]),
@@ -145,7 +147,7 @@ def load_library(path: os.PathLike = LIB_PATH):
 
 EXPORTED = ("ym_create", "ym_load_weights", "ym_broadcast_weights", "ym_broadcast_weights_local", "ym_rccl_get_unique_id", "ym_rccl_comm_init",
             "ym_rccl_comm_destroy", "ym_infer", "ym_obb_nms", "ym_input_max", "ym_calibrate", "ym_masks", "ym_masks_slots", "ym_masks_native",
-            "ym_letterbox", "ym_letterbox_batch", "ym_profile", "ym_profile_replay", "ym_tune", "ym_get_op_cfg", "ym_set_op_cfg", "ym_get_op_cfg_taken", "ym_get_op_variant",
+            "ym_letterbox", "ym_letterbox_batch", "ym_letterbox_nv12", "ym_nv12_to_bgr", "ym_profile", "ym_profile_replay", "ym_tune", "ym_get_op_cfg", "ym_set_op_cfg", "ym_get_op_cfg_taken", "ym_get_op_variant",
             "ym_op_variant_count", "ym_num_ops",
             "ym_op_name",
             "ym_num_buffers", "ym_buffer_info", "ym_read_buffer", "ym_sync", "ym_last_error", "ym_destroy",
@@ -403,6 +405,24 @@ class Runtime:
         V = C.c_void_p
         _check(self.lib.ym_letterbox_batch(self.ctx, V(desc_ptr or None), V(host_desc_ptr or None), B,
                                            V(dst_ptr or None), Hn, Wn, V(stream)))
+
+    def letterbox_nv12(self, desc_ptr: int, host_desc_ptr: int, B: int, coef, dst_ptr: int, Hn: int, Wn: int,
+                       stream: int):
+        """ym_letterbox_nv12: B NV12 device frames (ym_nv12_desc rows on the device and, for validation, on the host)
+        to the (B, 3, Hn, Wn) fp32 batch in one launch; coef: the six conversion integers (y_off, CY, CUB, CUG, CVG,
+        CVR) or None; asynchronous on `stream`."""
+        V = C.c_void_p
+        _check(self.lib.ym_letterbox_nv12(self.ctx, V(desc_ptr or None), V(host_desc_ptr or None), B,
+                                          (C.c_int * 6)(*coef) if coef is not None else None, V(dst_ptr or None), Hn,
+                                          Wn, V(stream)))
+
+    def nv12_to_bgr(self, y_ptr: int, uv_ptr: int, h: int, w: int, y_pitch: int, uv_pitch: int, coef, bgr_ptr: int,
+                    row_bytes: int, stream: int):
+        """ym_nv12_to_bgr: one NV12 device frame to packed (h, w, 3) uint8 BGR; asynchronous on `stream`."""
+        V = C.c_void_p
+        _check(self.lib.ym_nv12_to_bgr(self.ctx, V(y_ptr or None), V(uv_ptr or None), h, w, y_pitch, uv_pitch,
+                                       (C.c_int * 6)(*coef) if coef is not None else None, V(bgr_ptr or None),
+                                       row_bytes, V(stream)))
 
     def tune(self, x_ptr, B, H, W, args, dets_ptr, counts_ptr, stream, reps=8):
         _check(self.lib.ym_tune(self.ctx, C.c_void_p(x_ptr), B, H, W, C.byref(args), C.c_void_p(dets_ptr),

@@ -7,7 +7,9 @@ divides by 255.  Here the geometry is computed on the host (`letterbox_geometry`
 `LetterBox.__call__`), each image is copied to the device once, and `ym_letterbox` (csrc/ym_letterbox.hip) writes
 its slot of the fp32 NCHW batch.  Detections are mapped back with `scale_boxes` (upstream `ops.scale_boxes`).
 Frames that are on the device already (uint8 HWC tensors) skip the copy: `letterbox_frames` writes the whole batch
-with one `ym_letterbox_batch` launch (csrc/ym_letterbox_batch.hip), the same bits.
+with one `ym_letterbox_batch` launch (csrc/ym_letterbox_batch.hip), the same bits.  Decoder surfaces (NV12: a Y plane
+and an interleaved UV plane) go in as `NV12Frames`: `letterbox_nv12` converts and letterboxes them with one
+`ym_letterbox_nv12` launch (csrc/ym_letterbox_nv12.hip).
 Classify models take upstream's `classify_transforms` instead: `classify_batch` (Pillow, on the host: the reference)
 and `classify_batch_gpu` (`ym_classify_pre`, csrc/ym_cls_pre.hip: one copy and one launch per batch, the same bits).
 Reference call sites: /root/reference/demos/detection_demo.py:87-93, 190-196 (path / ndarray sources).
@@ -159,6 +161,154 @@ def letterbox_frames(rt, frames, device: torch.device, imgsz: int = 640, stride:
     out = torch.empty((len(frames), 3, Hn, Wn), dtype=torch.float32, device=device)
     rt.letterbox_batch(dtab.data_ptr(), desc.ctypes.data, len(frames), out.data_ptr(), Hn, Wn, stream)
     return out, [tuple(f.shape[:2]) for f in frames]
+
+
+# ym_nv12_desc (include/yolomi.h): one frame of a ym_letterbox_nv12 launch
+NV12_DESC = np.dtype([("y", "<u8"), ("uv", "<u8"), ("h", "<i4"), ("w", "<i4"), ("y_pitch", "<i4"), ("uv_pitch", "<i4"),
+                      ("uh", "<i4"), ("uw", "<i4"), ("top", "<i4"), ("left", "<i4"), ("scale_x", "<f8"),
+                      ("scale_y", "<f8")])
+# (standard, full_range) -> (y_off, cy, cub, cug, cvg, cvr), the decimals the fixed-point integers are rounded from
+NV12_STANDARDS = {("bt601", False): (16, 1.164, 2.018, -0.391, -0.813, 1.596),
+                  ("bt709", False): (16, 1.164, 2.112, -0.213, -0.533, 1.793),
+                  ("bt601", True): (0, 1.0, 1.772, -0.344, -0.714, 1.402),
+                  ("bt709", True): (0, 1.0, 1.8556, -0.1873, -0.4681, 1.5748)}
+
+
+def nv12_coefficients(standard: str = "bt601", full_range: bool = False) -> Tuple[int, ...]:
+    """(y_off, CY, CUB, CUG, CVG, CVR) of ym_letterbox_nv12 / ym_nv12_to_bgr: each coefficient round(c * 2**20).  BT.601
+    limited range gives OpenCV's own COLOR_YUV2BGR_NV12 integers."""
+    key = (str(standard).lower(), bool(full_range))
+    if key not in NV12_STANDARDS:
+        raise ValueError(f"unknown NV12 standard {standard!r}: 'bt601' or 'bt709'")
+    y_off, *c = NV12_STANDARDS[key]
+    return (y_off,) + tuple(int(round(v * (1 << 20))) for v in c)
+
+
+class NV12Frames:
+    """A predict() / track() / embed() source of decoded video as hardware decoders hand it out: per frame a (H, W) uint8
+    luma plane and a (H/2, W/2, 2) uint8 plane of interleaved U, V, on the model's device.  y: a (B, H, W) tensor or a
+    list of (H, W) ones; uv: a (B, H/2, W/2, 2) tensor or a list of (H/2, W/2, 2) ones.  Any row stride is taken (pitched
+    surfaces as they are, no copy); an element stride other than 1 in y or other than (2, 1) in uv is refused, as are odd
+    sizes.  standard / full_range choose the conversion integers (nv12_coefficients)."""
+
+    def __init__(self, y, uv, standard: str = "bt601", full_range: bool = False):
+        self.coef = nv12_coefficients(standard, full_range)
+        self.standard, self.full_range = str(standard).lower(), bool(full_range)
+        for name, p, nd in (("y", y, 3), ("uv", uv, 4)):
+            if isinstance(p, torch.Tensor) and p.dim() != nd:
+                raise TypeError(f"NV12Frames: {name} must be a ({'B, H, W' if nd == 3 else 'B, H/2, W/2, 2'}) tensor or a "
+                                f"list of planes, got shape {tuple(p.shape)}")
+            if not isinstance(p, (torch.Tensor, list, tuple)):
+                raise TypeError(f"NV12Frames: {name} must be a tensor or a list of tensors, got {type(p).__name__}")
+        self.y = list(y.unbind(0)) if isinstance(y, torch.Tensor) else list(y)
+        self.uv = list(uv.unbind(0)) if isinstance(uv, torch.Tensor) else list(uv)
+        if not self.y or len(self.y) != len(self.uv):
+            raise ValueError(f"NV12Frames: {len(self.y)} y planes and {len(self.uv)} uv planes (at least one of each, as "
+                             f"many of one as of the other)")
+        for i, (p, c) in enumerate(zip(self.y, self.uv)):
+            for name, t, nd in (("y", p, 2), ("uv", c, 3)):
+                if not isinstance(t, torch.Tensor):
+                    raise TypeError(f"frame {i}: {name} is a {type(t).__name__}, not a torch.Tensor")
+                if t.dtype != torch.uint8 or t.dim() != nd or (nd == 3 and t.shape[2] != 2):
+                    raise TypeError(f"frame {i}: {name} must be a uint8 {'(H, W)' if nd == 2 else '(H/2, W/2, 2)'} plane, "
+                                    f"got {tuple(t.shape)} {t.dtype}")
+            h, w = int(p.shape[0]), int(p.shape[1])
+            if h < 2 or w < 2 or h % 2 or w % 2:
+                raise ValueError(f"frame {i}: NV12 sizes are even and at least 2, got {h} x {w}")
+            if tuple(c.shape) != (h // 2, w // 2, 2):
+                raise ValueError(f"frame {i}: uv plane {tuple(c.shape)} does not belong to a {h} x {w} y plane (expected "
+                                 f"{(h // 2, w // 2, 2)})")
+            if c.device != p.device:
+                raise ValueError(f"frame {i}: y is on {p.device}, uv on {c.device}")
+            if p.stride(1) != 1 or p.stride(0) < w:
+                raise ValueError(f"frame {i}: y strides {tuple(p.stride())} are not rows of bytes (element stride 1, row "
+                                 f"stride >= W)")
+            if c.stride(2) != 1 or c.stride(1) != 2 or c.stride(0) < w:
+                raise ValueError(f"frame {i}: uv strides {tuple(c.stride())} are not rows of interleaved U, V bytes "
+                                 f"(strides (>= W, 2, 1))")
+
+    @classmethod
+    def from_surface(cls, t: torch.Tensor, standard: str = "bt601", full_range: bool = False) -> "NV12Frames":
+        """The usual decoder surface, (3H/2, W) uint8 or a (B, 3H/2, W) batch of them — H rows of Y, then H/2 rows of
+        interleaved U, V at the same pitch — split into views, with no copy."""
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() not in (2, 3):
+            raise TypeError("NV12Frames.from_surface: expected a (3H/2, W) or (B, 3H/2, W) uint8 tensor")
+        t = t.unsqueeze(0) if t.dim() == 2 else t
+        rows, w = int(t.shape[1]), int(t.shape[2])
+        if rows < 3 or rows % 3 or w < 2 or w % 2 or t.stride(2) != 1:
+            raise ValueError(f"NV12Frames.from_surface: {rows} x {w} is no 3H/2 x W surface of even H and W with "
+                             f"element stride 1")
+        h = rows // 3 * 2
+        return cls(t[:, :h], t[:, h:].unflatten(2, (w // 2, 2)), standard, full_range)
+
+    def __len__(self):
+        return len(self.y)
+
+    def clone(self) -> "NV12Frames":
+        """The same frames in memory of their own (decoders reuse their surfaces)."""
+        r = object.__new__(NV12Frames)
+        r.coef, r.standard, r.full_range = self.coef, self.standard, self.full_range
+        r.y, r.uv = [p.clone() for p in self.y], [c.clone() for c in self.uv]
+        return r
+
+    def image(self, rt, i: int) -> "NV12Image":
+        return NV12Image(rt, self.y[i], self.uv[i], self.coef)
+
+
+class NV12Image:
+    """One NV12 frame standing where an image source's HWC BGR ndarray stands (Results.orig_img): it has the image's
+    `shape`, and `to_bgr()` converts it with ym_nv12_to_bgr (csrc/ym_letterbox_nv12.hip) and moves it to the host."""
+
+    def __init__(self, rt, y: torch.Tensor, uv: torch.Tensor, coef):
+        self.rt, self.y, self.uv, self.coef = rt, y, uv, coef
+        self.shape = (int(y.shape[0]), int(y.shape[1]), 3)
+
+    def to_bgr_device(self, stream: int = None) -> torch.Tensor:
+        h, w, _ = self.shape
+        out = torch.empty(self.shape, dtype=torch.uint8, device=self.y.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(self.y.device).cuda_stream
+        self.rt.nv12_to_bgr(self.y.data_ptr(), self.uv.data_ptr(), h, w, self.y.stride(0), self.uv.stride(0), self.coef,
+                            out.data_ptr(), 3 * w, stream)
+        return out
+
+    def to_bgr(self) -> np.ndarray:
+        return self.to_bgr_device().cpu().numpy()
+
+
+def nv12_desc(frames: NV12Frames, geo: Sequence[Tuple]) -> np.ndarray:
+    """The NV12_DESC table of the frames with their batch_geometry: plane addresses and pitches as they are."""
+    desc = np.zeros(len(frames), dtype=NV12_DESC)
+    for i, (p, c, g) in enumerate(zip(frames.y, frames.uv, geo)):
+        h, w = int(p.shape[0]), int(p.shape[1])
+        desc[i] = (p.data_ptr(), c.data_ptr(), h, w, p.stride(0), c.stride(0), g[0], g[1], g[2], g[4],
+                   1.0 / (g[1] / w), 1.0 / (g[0] / h))
+    return desc
+
+
+def letterbox_nv12(rt, frames: NV12Frames, device: torch.device, imgsz: int = 640, stride: int = 32, stream: int = 0,
+                   geo: Sequence[Tuple] = None) -> Tuple[torch.Tensor, List[Tuple[int, int]]]:
+    """letterbox_frames for NV12Frames: the geometry is batch_geometry's of the luma planes, the descriptor table goes up
+    through pinned memory and ONE ym_letterbox_nv12 launch (csrc/ym_letterbox_nv12.hip) converts the taps the resize
+    uses and writes the (B, 3, Hn, Wn) fp32 batch — no host sync, no converted frame, the bits of letterbox_frames on the
+    frames converted to BGR by the integer rule of include/yolomi.h."""
+    device = torch.device(device)
+    if not isinstance(frames, NV12Frames):
+        raise TypeError(f"letterbox_nv12: expected NV12Frames, got {type(frames).__name__}")
+    for i, p in enumerate(frames.y):
+        if p.device != device:
+            raise ValueError(f"frame {i} is on {p.device}: frames must be on the model's device ({device})")
+    if geo is None:
+        geo = batch_geometry(frames.y, imgsz, stride)
+    desc = nv12_desc(frames, geo)
+    uh, uw, t, b, l, r = geo[0]
+    Hn, Wn = uh + t + b, uw + l + r
+    host = torch.empty(desc.nbytes, dtype=torch.uint8, pin_memory=device.type == "cuda")
+    host.numpy()[:] = desc.view(np.uint8)
+    dtab = host.to(device, non_blocking=True)  # (the pinned block is recycled only once this copy has run)
+    out = torch.empty((len(frames), 3, Hn, Wn), dtype=torch.float32, device=device)
+    rt.letterbox_nv12(dtab.data_ptr(), desc.ctypes.data, len(frames), frames.coef, out.data_ptr(), Hn, Wn, stream)
+    return out, [tuple(p.shape) for p in frames.y]
 
 
 def classify_geometry(h: int, w: int, imgsz: int = 224) -> Tuple[int, int, int, int]:
